@@ -5,16 +5,27 @@ One step = main_bayesian.py:73-80 of the reference: num_ens x net(x) + log_softm
 forward only, no_grad, inputs resident in HBM.  Synthetic data: torch.manual_seed(0), parameters from the
 layers' own reset_parameters with config_bayesian.priors, x ~ U[0,1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: re-executes itself under torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                  (N > 1: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: graphs built -> `preheat_ms` of untimed replays -> W warm-up steps -> EXACTLY K timed
+steps -> the result line (`value` and `ms_per_step` from that one block of K steps).  `--full` adds everything else described
+below: the CPU baseline, the cold block, the block statistics (`value` = their median), the rooflines and per-launch timings, the
+other BASELINE configurations, precisions and paths, the training step, and the SECONDARY line.
+`--dump-outputs DIR` writes what the timed path returned for the LAST timed step, DIR/log_outputs.npy ([B, C] float32) and
+DIR/kl.npy (float32 scalar).  Inputs are fixed by the arguments: parameters and x from torch.manual_seed(0), and the noise
+counters are wound back to the pipeline's first step after the time-boxed pre-heat, so the noise every warm-up and timed step
+draws depends on the arguments only (N = 1: the last timed step is step s = ceil(W / G) * G + K - 1, noise calls call0 + 10 s ..
+call0 + 10 s + 9, call0 = the device generator's call counter once the parameters are initialised).
 
 Launch structure of the timed region (N = 1): hipGraph replays; a graph holds `--steps-per-launch` (default 4) consecutive steps
 -- 4 batches x 10 draws = 40 slabs per layer launch, each step with its own noise calls, bit for bit what 4 separate replays
 compute (tests/test_gpu_steps_per_launch.py) -- and `--pipeline` (default 2) such graphs are in flight on separate HIP streams.
 A device-side call counter inside the graph advances the Philox noise on every replay.  The one-step-per-launch pipeline of
 rounds 1-3 (3 lanes) is timed beside it (`roofline.one_step_per_launch_ms`).
-Order of a run: CPU baseline (GPU idle, ~20 s) -> graphs built -> K steps timed COLD (`cold_first_block`, reported, never
+Order of a `--full` run: CPU baseline (GPU idle, ~20 s) -> graphs built -> K steps timed COLD (`cold_first_block`, reported, never
 `value`) -> `preheat_ms` of the same replays, untimed (the part clocks up under load; a 20-step region is 13 ms) -> W warm-up
 steps -> barrier + sync -> EXACTLY K timed steps -> sync + barrier.
 
@@ -332,6 +343,22 @@ def preheat(fn, seconds, dev):
     return round(1e3 * (time.perf_counter() - t0), 1)
 
 
+def rewind_noise(gstep, dev):
+    """Wind the noise of a GraphedMC / GraphedPipeline back to its first step: every lane's device-side call counter, the
+    pipeline's step index and the host-side call counter.  The time-boxed pre-heat replays a varying number of steps; after this
+    the warm-up and timed steps draw the same noise calls in every run with the same arguments (every rank does the same)."""
+    from bbb_hip import rng
+    lanes = getattr(gstep, "lanes", [gstep])
+    torch.cuda.synchronize(dev)
+    for lane in lanes:
+        assert lane.slot == 0, "rewind_noise: a partly filled group is pending"
+        lane.counter.fill_(lane.start)
+    if hasattr(gstep, "i"):
+        gstep.i = 0
+    rng.rewind((lanes[0].seed, lanes[0].call0))
+    torch.cuda.synchronize(dev)
+
+
 class LaunchRecorder:
     """Stands in for ensemble.Timers: keeps every bracketed launch (a closure over its operands) so that it can be replayed."""
     reps = 20
@@ -491,10 +518,12 @@ def reparam_region_probe(net, x, E, G, dev, n_params, reps=10):
 
 
 def run_config(cfg, steps, warmup, pipeline, dev, group=None, world=1, want_roofline=True, stat_blocks=0, timer_steps=5,
-               total_ens=None, steps_per_launch=1, preheat_s=0.4, cold_block=False, single_lane=True, rank=0, multi=None):
+               total_ens=None, steps_per_launch=1, preheat_s=0.4, cold_block=False, single_lane=True, rank=0, multi=None,
+               last_step=None):
     """Throughput of one configuration: hipGraph lanes, K timed steps between device syncs (max over ranks) -> dict.
     steps_per_launch = G > 1: every lane's graph holds G consecutive steps (GraphedPipeline).  cold_block: the K steps are also
-    timed once BEFORE the pre-heat (reported as cold_first_block, never the value)."""
+    timed once BEFORE the pre-heat (reported as cold_first_block, never the value).  last_step: a list that receives copies of
+    the (log_outputs, kl) the last timed step returned."""
     from bbb_hip import ensemble
     net, x = build_net(cfg, dev)
     E = cfg["E"] if total_ens is None else total_ens
@@ -589,12 +618,15 @@ def run_config(cfg, steps, warmup, pipeline, dev, group=None, world=1, want_roof
                     flush()
                     torch.cuda.synchronize(dev)
         out["preheat_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        rewind_noise(gstep, dev)
         for _ in range(warmup):
             step()
         flush()
         elapsed, (lo, kl) = timed_block(steps)
         lo, kl = lo.clone(), kl.clone()                  # (checked for finiteness AFTER the statistics blocks below: a host round trip here
-        if multi:                                        #  idles the part, and the block behind it measured 15 % low on every box)
+        if last_step is not None:                        #  idles the part, and the block behind it measured 15 % low on every box)
+            last_step.append((lo, kl))
+        if multi:
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=group)
             elapsed = t.item()
@@ -1133,8 +1165,15 @@ def main():
     ap.add_argument("--config", default="metric", choices=list(CONFIGS), help="which BASELINE configuration is the reported value")
     ap.add_argument("--gemm-mode", default="fp32", choices=["fp32", "bf16x3"],
                     help="bf16x3: the opt-in range-free split-bf16 GEMM mode for the WHOLE run (profiling it, or timing a sharded run with "
-                         "it); the default run reports it as the secondary object `split_bf16` next to the fp32 headline")
+                         "it); a --full run reports it as the secondary object `split_bf16` next to the fp32 headline")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baseline, cold block, block statistics, rooflines, the other configurations, "
+                         "precisions and paths, the training step, the SECONDARY line (without it: the headline measurement only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for the last timed step as DIR/log_outputs.npy and DIR/kl.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.no_graph:
+        ap.error("--dump-outputs: the eager profiling mode (--no-graph) does not keep its outputs")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # test hook (never set by the driver): run the N > 1 FLOW -- RCCL process group, sharded lanes with the recorded collective, barriers,
@@ -1179,7 +1218,7 @@ def main():
     # the reference's CPU path first, on rank 0, BEFORE the process group exists: the other ranks then
     # wait in the rendezvous (sleeping on a socket), not in a collective (spinning on the cores the baseline is being timed on)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and not args.no_extras and not args.no_graph:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not args.no_extras and not args.no_graph:
         cpu = cpu_baseline(20.0 if world == 1 else 10.0)
     group = None
     if multi:
@@ -1234,15 +1273,24 @@ def main():
             torch.distributed.destroy_process_group()
         return
 
-    extras = rank == 0 and not multi and not args.no_extras
+    extras = args.full and rank == 0 and not multi and not args.no_extras
     G = args.steps_per_launch
-    head, net, x = run_config(cfg, args.steps, args.warmup, args.pipeline, dev, group, world, want_roofline=not args.no_roofline,
-                              stat_blocks=5 if extras else 0, timer_steps=min(args.steps, 10), steps_per_launch=G,
-                              preheat_s=args.preheat_ms * 1e-3, cold_block=True, rank=rank, single_lane=extras, multi=multi)
+    last_step = []
+    head, net, x = run_config(cfg, args.steps, args.warmup, args.pipeline, dev, group, world,
+                              want_roofline=args.full and not args.no_roofline, stat_blocks=5 if extras else 0,
+                              timer_steps=min(args.steps, 10), steps_per_launch=G, preheat_s=args.preheat_ms * 1e-3,
+                              cold_block=args.full, rank=rank, single_lane=extras, multi=multi, last_step=last_step)
     n_params = sum(p.numel() for n, p in net.named_parameters() if n.endswith("_mu"))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        lo_last, kl_last = last_step[0]
+        np.save(os.path.join(args.dump_outputs, "log_outputs.npy"), lo_last.float().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "kl.npy"), kl_last.float().cpu().numpy())
+    del last_step
 
     weak = None
-    if multi and not args.no_extras:
+    if multi and args.full and not args.no_extras:
         w, _, _ = run_config(cfg, max(5, args.steps // 2), 3, args.pipeline, dev, group, world, want_roofline=False,
                              total_ens=cfg["E"] * max(world, 2 if self_group else 1), preheat_s=0.1, rank=rank, multi=multi)
         weak = {"value": w["value"], "unit": "samples/s", "ms_per_step": w["ms_per_step"], "num_ens_total": cfg["E"] * world}  # 10 draws per GPU

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline"
+BENCH="python $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline"
 # eager single-stream passes of the timed region's launches, nothing else in the process.  Round 4: a launch carries 4 steps
 # (bench.py --steps-per-launch 4, the default), so 4 warm-up + 8 timed steps = 3 passes = 12 MC steps; the bf16 configs[1] pass and
 # the one-step-per-launch comparison (EAGER1) keep 2 + 5 = 7 steps.
@@ -19,7 +19,7 @@ NSTEPS=12
 
 rm -rf /tmp/kt && mkdir -p /tmp/kt
 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- $BENCH > /tmp/kt/log.txt 2>&1
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline   ($TAG; fp32 headline, block statistics, single lane, kernel-timer pass, reparam probe, drop-in loop, BASELINE configs[1..4])"
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline   ($TAG; fp32 headline, block statistics, single lane, kernel-timer pass, reparam probe, drop-in loop, BASELINE configs[1..4])"
   grep '^{' /tmp/kt/log.txt | cut -c1-600
   DB=$(find /tmp/kt -name '*.db' | head -1)
   python $R/profiles/summarize_rocpd.py $DB

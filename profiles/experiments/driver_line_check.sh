@@ -1,9 +1,12 @@
 #!/usr/bin/env bash
-# The driver's own invocation, three times: length of the judged line and the quantities tests/test_gpu_bench_contract.py asserts on.
+# The driver's full invocation (--full), three times: length of the judged line and the quantities tests/test_gpu_bench_contract.py
+# asserts on.  The three lines are kept in $1 (default: a fresh temporary directory).
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
+OUT=${1:-$(mktemp -d)}
+mkdir -p "$OUT"
 for i in 1 2 3; do
-  python $R/bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $R/gpurun_out/r06_drv_$i.txt
-  python - "$R/gpurun_out/r06_drv_$i.txt" <<'PY'
+  python $R/bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/drv_$i.txt"
+  python - "$OUT/drv_$i.txt" <<'PY'
 import json, sys
 l = open(sys.argv[1]).read().strip()
 d = json.loads(l); r = d["roofline"]

@@ -1,6 +1,7 @@
 """bench.py's LAST stdout line is the contract's JSON object: under 2000 characters (the driver's record keeps a 2000-character
 tail), every judged number a scalar inside `roofline` / `cpu_baseline`; the bulky objects ride on an earlier `SECONDARY ` line.
-Run with -m gpu; short runs, CPU baseline leg skipped here except where stated -- the default invocation includes it."""
+Run with -m gpu; short runs, CPU baseline leg skipped here except where stated -- a --full invocation includes it.  A plain run
+(no --full) measures the headline only; what the other measurements assert on is asked for with --full."""
 import json
 import os
 import subprocess
@@ -24,7 +25,7 @@ def _split(stdout):
 
 
 def _run(extra, steps=("--steps", "4", "--warmup", "2"), cpu=False):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *steps] + ([] if cpu else ["--no-cpu-baseline"]) + extra,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *steps] + ([] if cpu else ["--no-cpu-baseline"]) + extra,
                        capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     return _split(p.stdout)
@@ -99,7 +100,7 @@ def test_bench_json_contract_default():
 
 
 def test_bench_driver_invocation_line_is_short_and_complete():
-    """The driver's own command (--steps 20 --warmup 5, CPU baseline included): the last line fits the record's 2000-character
+    """The driver's full command (--full --steps 20 --warmup 5, CPU baseline included): the last line fits the record's 2000-character
     tail with `cpu_baseline` inside, and the pre-heated 20-step figure is within 8 % of the block median of the same run."""
     j, sec = _run([], steps=("--steps", "20", "--warmup", "5"), cpu=True)
     cb = j["cpu_baseline"]
@@ -122,6 +123,46 @@ def test_bench_driver_invocation_line_is_short_and_complete():
     assert r["split_bf16_value"] > j["value"] and 0.3 < r["split_bf16_frac_of_bf16_peak"] < 1 and 0.7 < r["reparam_frac_of_write_roof"] < 1.3
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """The plain invocation: the headline only -- one JSON line, no SECONDARY line, no CPU baseline, cold block or roofline; `value`
+    and `ms_per_step` from EXACTLY --steps timed steps.  --dump-outputs writes what the last timed step returned, and the inputs are
+    fixed by the arguments: 3 warm-up steps fill one group of 4 (flushed), the 6 timed steps are steps 4..9, so the last one drew
+    noise calls call0 + 90 .. call0 + 99 (call0: the device generator's state once the parameters are initialised) whatever the
+    time-boxed pre-heat ran -- the eager step at those calls gives the same result."""
+    import numpy as np
+    import torch
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "3",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j, sec = _split(p.stdout)
+    assert sec is None
+    assert j["metric"] == "MC-forward samples/sec, BayesianAlexNet CIFAR-10 bs=512 num_ens=10" and j["unit"] == "samples/s"
+    assert j["higher_is_better"] is True and j["dtype"] == "f32" and j["steps"] == 6 and j["warmup"] == 3 and j["n_gpus"] == 1
+    assert abs(j["value"] - 512 * 10 / (j["ms_per_step"] * 1e-3)) <= 1e-3 * j["value"] and j["ms_per_step"] > 0
+    for k in ("cpu_baseline", "cold_first_block", "weak_scaling"):
+        assert k not in j, k
+    assert j["roofline"] is None and "4 steps per launch" in j["config"]["launch"]
+    assert sorted(os.listdir(d)) == ["kl.npy", "log_outputs.npy"]
+    lo, kl = np.load(d / "log_outputs.npy"), np.load(d / "kl.npy")
+    assert lo.shape == (512, 10) and lo.dtype == np.float32 and kl.shape == () and kl.dtype == np.float32
+    import bench
+    from bbb_hip import ensemble, rng
+    rng.use_device_generator()                          # (as in a fresh process: no stream pinned by an earlier test)
+    net, x = bench.build_net(bench.CONFIGS["metric"], torch.device("cuda", 0))
+    seed, call0 = rng.get_state()                       # what the bench's pipeline started from
+    try:
+        rng.manual_seed(seed, call=call0 + 90)
+        with torch.no_grad():
+            want_lo, want_kl = ensemble.mc_forward(net, x, 10)
+        torch.cuda.synchronize()
+    finally:
+        rng.use_device_generator()
+    want_lo = want_lo.cpu().numpy()
+    np.testing.assert_allclose(lo, want_lo, rtol=0, atol=1e-5 * float(np.abs(want_lo).max()))
+    assert abs(float(kl) - want_kl.item()) <= 1e-6 * abs(want_kl.item())
+
+
 def test_bench_json_contract_other_config_as_headline():
     j, _ = _run(["--config", "configs[1]", "--pipeline", "1", "--no-extras"])
     assert j["dtype"] == "bf16" and j["n_gpus"] == 1 and "3Conv3FC" in j["metric"]
@@ -135,7 +176,7 @@ def test_bench_n_gt_1_flow_rehearsed_on_one_device():
     (two processes share a GPU and gloo stages through the host); the flow is what is checked."""
     env = dict(os.environ, BBB_BENCH_DEVICE="0", BBB_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"],
+                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j, _ = _split(p.stdout)
@@ -173,7 +214,7 @@ def test_bench_multi_rank_flow_over_rccl_with_one_rank():
     env = dict(os.environ, BBB_BENCH_SELF_GROUP="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BBB_BENCH_BACKEND", "BBB_BENCH_DEVICE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j, _ = _split(p.stdout)
