@@ -2108,6 +2108,27 @@ def chwn_grad_as_weights(g, chunks=1):
 wgrad_in_place = [False]
 
 
+def wgrad_batch_chunks(E, Cout, Cin, kh, kw, B):
+    """The number S of batch chunks conv2d_chwn_weight_grad runs as extra draws: doubled while the role-swapped launch (E draws,
+    Cin already a multiple of 4) would occupy fewer than 512 workgroups and every chunk keeps an even share of >= 8 images."""
+    wgs = E * kh * kw * -(-Cout // 64) * -(-Cin // 64)
+    S = 1
+    while wgs * S < 512 and B % (2 * S) == 0 and B // (2 * S) >= 8:
+        S *= 2
+    return S
+
+
+def shared_input_k_slices(M, Jp, K):
+    """The number S of K slices conv2d_chwn_weight_grad_shared_input runs as the launch's draws (M = E * Cout rows, Jp im2col
+    columns, K = Ho * Wo * B): slices sized for the launcher's 128-wide tiles (>= 768 of them; 64-wide: 2.50 -> 2.48 ms per
+    512 x 10 step), each a multiple of 4 and >= 256 long."""
+    wgs = -(-M // 64) * -(-Jp // 128)
+    S = 1
+    while wgs * S < 768 and K % (2 * S) == 0 and (K // (2 * S)) % 4 == 0 and K // (2 * S) >= 256:
+        S *= 2
+    return S
+
+
 def conv2d_chwn_weight_grad(g_pre, x, w_shape, stride, padding, dilation, x_squares=False):
     """d loss / d w in the batch-innermost layout, again on the forward kernel with the roles swapped: the batch becomes the
     contraction channels, the layer's input channels the innermost ("image") axis, the output pixels the kernel taps:
@@ -2146,10 +2167,7 @@ def conv2d_chwn_weight_grad(g_pre, x, w_shape, stride, padding, dilation, x_squa
             square(xr[:Ex], out=xr[Ex:])
     else:
         xr = chwn_to_bhwc(x)                                            # [E|1, B, H, W, Cin]
-    wgs = E * kh * kw * -(-Cout // 64) * -(-Cin // 64)
-    S = 1
-    while wgs * S < 512 and B % (2 * S) == 0 and B // (2 * S) >= 8:
-        S *= 2
+    S = wgrad_batch_chunks(E, Cout, Cin, kh, kw, B)
     if S == 1 and wgrad_in_place[0] and current_config().gemm_mode != "bf16x3":
         # the output gradient [E, Cout, Ho, Wo, B] IS a tap-major weight operand (taps = output pixels, channels = images): read in
         # place, the contraction running (pixel, image) instead of (image, pixel) -- no transposed copy (250 MB per 512 x 10 step)
@@ -2205,10 +2223,7 @@ def conv2d_chwn_weight_grad_shared_input(g_pre, x_nchw, w_shape, stride, padding
     if tuple(xk.shape) != (P_, B, Jp) or not xk.is_contiguous():
         raise _lib.BBBHipError("conv2d_chwn_weight_grad_shared_input: geometry mismatch")
     M = E * Cout
-    wgs = -(-M // 64) * -(-Jp // 128)            # slices sized for the launcher's 128-wide tiles (>= 768 of them; 64-wide: 2.50 -> 2.48 ms per 512 x 10 step)
-    S = 1
-    while wgs * S < 768 and K % (2 * S) == 0 and (K // (2 * S)) % 4 == 0 and K // (2 * S) >= 256:
-        S *= 2
+    S = shared_input_k_slices(M, Jp, K)
     Ks = K // S
     d = ConvDesc()
     d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = Jp, Ks, 1, 1, M, 1, 1

@@ -899,3 +899,26 @@ def test_outgrown_scratch_buffers_are_retired_not_freed():
     gc.collect()
     assert sk not in ops._scratch and not any(k == sk for k, _ in ops._retired)
     assert ops.scratch_scope(object()).tok is None
+
+
+def test_train_fuzz_branch_coverage():
+    """The fixed case lists of test_gpu_train_fuzz.py reach every branch of the training backward's launchers: weight-gradient
+    batch chunks S == 1 / S >= 2 (shared and per-draw x, and S >= 4), the kh' > kh slice of a strided role-swapped launch (with and
+    without chunks), zero-plane channel padding, the x_squares pair, shared-input K slices S == 1 / S >= 2 with the im2col built
+    or handed in, the three g_pre pitch forms, and pools with overlap, gaps and floor-dropped rows / columns on H != W.  The S
+    choices are ops' own helpers, the ones the launchers call."""
+    import test_gpu_train_fuzz as T
+    conv = set().union(*(T.conv_branches(c) for c in T.CONV_CASES.values()))
+    assert {"wgrad-S1-shared", "wgrad-S1-perdraw", "wgrad-S2+-shared", "wgrad-S2+-perdraw", "wgrad-S4+", "wgrad-khslice-S1",
+            "wgrad-khslice-S2+", "wgrad-cinpad", "wgrad-xsquares", "dgrad-plain", "dgrad-flipped", "dgrad-q0"} <= conv, conv
+    shared = set().union(*(T.shared_branches(c) for c in T.SHARED_CASES.values()))
+    assert {"shared-S1", "shared-S2+", "gpre-contiguous", "gpre-padded-view", "gpre-copied", "xk-built", "xk-prebuilt"} <= shared, shared
+    pools = [T.pool_branches(c) for c in T.POOL_CASES.values()]
+    for want in ("overlap", "gap", "tiled", "act-only"):
+        assert any(want in b for b in pools), want
+    assert any({"gap", "floor-rows", "floor-cols", "h!=w"} <= b for b in pools)
+    assert any({"overlap", "floor-rows", "floor-cols", "h!=w"} <= b for b in pools)
+    # the launchers' own choices, on the shapes that pin them
+    from bbb_hip import ops
+    assert ops.wgrad_batch_chunks(3, 5, 4, 3, 2, 132) == 4 and ops.wgrad_batch_chunks(1, 64, 192, 3, 3, 4) == 1
+    assert ops.shared_input_k_slices(64, 364, 56 * 56 * 4) >= 2 and ops.shared_input_k_slices(96, 64, 5 * 5 * 4) == 1
