@@ -564,6 +564,33 @@ int bbb_plane_sum(const float* x, float* out, int64_t outer, int64_t rows, int64
 int bbb_sum_leading(const float* x, float* out, int64_t outer, int64_t n, void* stream);
 int bbb_lrt_glue(const float* a, const float* x, const float* b, float* out, int64_t n, int64_t x_n, int mode, void* stream);
 
+/*
+ * bf16 training backward (the bf16 storage mode of the training step; additive entry points, ABI 13).  The gradient contractions
+ * run on bbb_conv2d_chwn_bf16_fwd (dgrad: the forward on flipped, channel-transposed weight rows; wgrad: the forward with batch and
+ * channel roles swapped); these are the steps around them.  Deterministic, no atomics, 16-byte vector stores.
+ * bbb_pool_act_bwd_chwn_bf16: bbb_pool_act_bwd_chwn on bf16 storage.  y [planes][h][w][B] bf16 (the stored activated output),
+ *   g_out [planes][hp][wp][B] bf16, or fp32 with BBB_BF16_BWD_G_F32; g_pre = act'(y) * route(g_out) in fp32 (routing to the first
+ *   maximum among the stored bf16 values, act' from the bf16 y), rounded once to bf16 (nearest-even) -- written as bf16, or with
+ *   BBB_BF16_BWD_OUT_F32 as the fp32 values of that rounding.  B % 8 == 0; out_plane_pitch: 0 = dense, else elements (% 8 == 0).
+ * bbb_plane_sum_bf16: out[r] = sum over j < cols of x[r*row_pitch + j], bf16 in, fp32 accumulation in a fixed order (bias
+ *   gradients); cols and row_pitch multiples of 8.
+ * bbb_flip_transpose_w_bf16: w [draws][cout][Kpi] bf16 rows (Kp = row length rounded up to 8) -> out [draws][cin][Kpo] with the
+ *   taps reversed and the channels transposed, pad columns zero: the weight operand of the input gradient.  Row orders: (ci, tap)
+ *   or, with BBB_BF16_FLIP_IN_TAP_MAJOR, (tap, ci); out (co, tap) or, with BBB_BF16_FLIP_OUT_TAP_MAJOR (cout % 8 == 0), (tap, co).
+ * bbb_chwn_to_bhwc_bf16: [draws][c][hw][B] -> [draws][B][hw][c_pad] bf16, channels c .. c_pad-1 zero (B, c_pad multiples of 8).
+ * bbb_batch_chunks_bf16: [outer][rows][B] -> [outer][chunks][rows][B / chunks] bf16 (B % (8 * chunks) == 0).
+ */
+#define BBB_BF16_BWD_G_F32          1u
+#define BBB_BF16_BWD_OUT_F32        2u
+#define BBB_BF16_FLIP_IN_TAP_MAJOR  1u
+#define BBB_BF16_FLIP_OUT_TAP_MAJOR 2u
+int bbb_pool_act_bwd_chwn_bf16(const void* g_out, const void* y, void* g_pre, int64_t planes, int h, int w, int batch, int k, int s,
+                               int act, int64_t out_plane_pitch, uint32_t flags, void* stream);
+int bbb_plane_sum_bf16(const void* x, float* out, int64_t rows, int64_t cols, int64_t row_pitch, void* stream);
+int bbb_flip_transpose_w_bf16(const void* w, void* out, int64_t draws, int cout, int cin, int khkw, uint32_t flags, void* stream);
+int bbb_chwn_to_bhwc_bf16(const void* x, void* out, int64_t draws, int c, int64_t hw, int batch, int c_pad, void* stream);
+int bbb_batch_chunks_bf16(const void* x, void* out, int64_t outer, int64_t rows, int batch, int chunks, void* stream);
+
 /* Library / device introspection (host-only). */
 int bbb_abi_version(void);
 const char* bbb_build_info(void);

@@ -115,6 +115,12 @@ _SIGNATURES = {
     "bbb_plane_sum": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p]),
     "bbb_sum_leading": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p]),
     "bbb_lrt_glue": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
+    "bbb_pool_act_bwd_chwn_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_u32,
+                                           c_void_p]),
+    "bbb_plane_sum_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p]),
+    "bbb_flip_transpose_w_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_u32, c_void_p]),
+    "bbb_chwn_to_bhwc_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
+    "bbb_batch_chunks_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
     "bbb_abi_version": (c_int, []),
     "bbb_build_info": (ctypes.c_char_p, []),
 }

@@ -946,7 +946,16 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     mean (group_share / GraphedMC steps > 1 with a process group combine the ranks' blocks).
     elbo = [target, beta, train_size, None] (a training step, train.train_step): on the batch-innermost autograd path the loss
     nll_loss(lse, target) * train_size + beta * kl is formed by the tail's own launches (ops.elbo_cb_autograd) and left in elbo[3];
-    elbo[3] still None on return: the caller forms it."""
+    elbo[3] still None on return: the caller forms it.
+    precision="bf16" with elbo (train.forward_loss(precision="bf16")) and autograd on: the bf16 training mode
+    (fast_train._MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing autograd."""
+    if precision == "bf16" and elbo is not None and torch.is_grad_enabled():
+        if not (fuse_act and fast_autograd) or timers is not None or units is not None or int(groups) > 1 or share is not None or b_offset:
+            raise _lib.BBBHipError("bf16 training runs on the batch-innermost autograd node only")
+        from . import fast_train
+        logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias, precision="bf16")
+        stats["path"] = "chwn-autograd-bf16"
+        return _autograd_tail(logits_cb, kl1, mean_over, elbo)
     _check_precision(precision, net, x, fuse_act)
     if share is not None:
         D, off = int(share[0]), int(share[1])
@@ -1000,21 +1009,26 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
             # training on the batch-innermost kernels: one autograd node for the whole batched forward
             logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias)
             stats["path"] = "chwn-autograd"
-            if elbo is not None and hip_loss_tail[0] and ops.elbo_cb_ok(logits_cb, kl1, elbo[0], elbo[1]):
-                elbo[3], lse = ops.elbo_cb_autograd(logits_cb, kl1, elbo[0], elbo[1], elbo[2], mean_over)
-                return lse, kl1
-            if logits_cb.shape[0] <= 512 and hip_loss_tail[0]:
-                lse = ops.mc_tail_cb_autograd(logits_cb, mean_over)       # log_softmax + logmeanexp, forward and backward one launch each
-            else:
-                lse = torch.logsumexp(F.log_softmax(logits_cb.permute(0, 2, 1), dim=2), dim=0) \
-                    - (math.log(mean_over) if mean_over > 0 else 0.0)
-            return lse, kl1
+            return _autograd_tail(logits_cb, kl1, mean_over, elbo)
     logits, kl1 = mc_logits(net, x, draws, seed, call0, fuse_act=fuse_act, timers=timers, layout="nchw")
     if torch.is_grad_enabled() and logits.requires_grad:
         # training extension: differentiable tail through torch ops
         lse = torch.logsumexp(F.log_softmax(logits, dim=2), dim=0) - (math.log(mean_over) if mean_over > 0 else 0.0)
     else:
         lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail(logits, mean_over=mean_over))
+    return lse, kl1
+
+
+def _autograd_tail(logits_cb, kl1, mean_over, elbo):
+    """The loss tail of the batch-innermost autograd node's logits [E, C, B] (fp32 in either training precision)."""
+    if elbo is not None and hip_loss_tail[0] and ops.elbo_cb_ok(logits_cb, kl1, elbo[0], elbo[1]):
+        elbo[3], lse = ops.elbo_cb_autograd(logits_cb, kl1, elbo[0], elbo[1], elbo[2], mean_over)
+        return lse, kl1
+    if logits_cb.shape[0] <= 512 and hip_loss_tail[0]:
+        lse = ops.mc_tail_cb_autograd(logits_cb, mean_over)       # log_softmax + logmeanexp, forward and backward one launch each
+    else:
+        lse = torch.logsumexp(F.log_softmax(logits_cb.permute(0, 2, 1), dim=2), dim=0) \
+            - (math.log(mean_over) if mean_over > 0 else 0.0)
     return lse, kl1
 
 

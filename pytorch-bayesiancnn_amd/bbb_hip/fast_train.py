@@ -252,6 +252,164 @@ class _MCForward(torch.autograd.Function):
         return tuple(out)
 
 
+class _MCForwardBF16(torch.autograd.Function):
+    """_MCForward in the bf16 storage mode (train.train_step(precision="bf16"); the arithmetic contract is DESIGN.md section 4.5):
+    (x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (fp32 logits [E, C, B] batch-innermost, fp32 kl of one forward).
+    Forward = the bf16 inference kernels with the pooling left unfused (the tape keeps every layer's pre-pool output): sampled
+    weights, the input and every hidden activated / pooled output stored as bf16, fp32 accumulation, fp32 logits and KL.  Tape:
+    each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the same walk as _MCForward._backward with
+      * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
+      * ops.plane_sums_bf16               bias gradients, the fp32 sum of that bf16 g_pre,
+      * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16,
+      * ops.conv2d_chwn_weight_grad_bf16  wgrad on the bf16 GEMM with the roles swapped -> fp32,
+      * the first layer (3-channel input shared by every draw): ops.conv2d_chwn_weight_grad_shared_input on the fp32 kernel over
+        the fp32 values of the bf16 operands (a bf16 x bf16 product is exact in fp32: the same contraction),
+      * ops.reparam_kl_backward           unchanged (fp32)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *params):
+        from . import ensemble
+        _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
+        net, E, seed, call0 = cfg["net"], cfg["draws"], cfg["seed"], cfg["call0"]
+        mods = ensemble.flat_children(net)
+        layers = [m for m in mods if isinstance(m, _BBBLayer)]
+        mus, rhos, ids = [], [], []
+        for l in layers:
+            m, r, i = l._param_lists()
+            mus += [t.detach() for t in m]
+            rhos += [t.detach() for t in r]
+            ids += i
+        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
+        kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E)
+        B = x.shape[0]
+        h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
+        tape = []
+        li, i = 0, 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, _BBBLayer):
+                w, b = ws[2 * li], ws[2 * li + 1]
+                is_conv = isinstance(m, BBBConv2d)
+                geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
+                x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
+                wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
+                ckk = wshape[1:]
+                act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
+                last = li == len(layers) - 1
+                if last and (act is not None or (i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d))):
+                    raise _lib.BBBHipError("bf16 training: the logits layer (fp32 output) must not be followed by an activation or a pool")
+                y = ops.conv2d_chwn_bf16_forward(x_in, w, b, ckk, *geom, act=act, out_f32=last,
+                                                 tap_major=is_conv and ops.bf16_tap_major(wshape))
+                rec = dict(layer=m, x=x_in, w=w, wshape=wshape, y=y, act=act, geom=geom, pool=None, first=(li == 0))
+                if act is not None:
+                    i += 1
+                h = y
+                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d):
+                    pool = mods[i + 1]
+                    h = ops.maxpool_chwn_bf16(y, pool.kernel_size, pool.stride)
+                    rec["pool"] = (pool.kernel_size, pool.stride)
+                    i += 1
+                rec["out_shape"] = tuple(h.shape)
+                tape.append(rec)
+                li += 1
+            elif isinstance(m, nn.MaxPool2d):
+                raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
+            elif isinstance(m, FlattenLayer):
+                h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
+            i += 1
+        logits = h.reshape(E, -1, B)
+        ctx.cfg, ctx.tape, ctx.meta = cfg, tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
+        ctx.launch_config = ops.current_config()
+        ctx.scratch_token = ops.current_scratch_token()
+        # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted)
+        ctx.x_nchw = x.detach().to(torch.bfloat16).to(torch.float32) if tape[0]["x"].shape[1] % 4 != 0 else None
+        ctx.versions = [(p, p._version) for p in params]
+        return logits, kl
+
+    @staticmethod
+    def backward(ctx, g_logits, g_kl):
+        with ops.use_config(ctx.launch_config), ops.scratch_scope(token=ctx.scratch_token):
+            return _MCForwardBF16._backward(ctx, g_logits, g_kl)
+
+    @staticmethod
+    def _backward(ctx, g_logits, g_kl):
+        cfg, tape = ctx.cfg, ctx.tape
+        _check_versions(ctx.versions)
+        cfg["spent"] = True
+        mus, rhos, ids, pm, ps, x_shape = ctx.meta
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        gws = [None] * len(mus)
+        g = g_logits.contiguous() if g_logits is not None else None
+        # (as in _MCForward: weight / bias gradients on side streams beside the input gradients, eager launches only; tensors the side
+        # streams read stay referenced in `keep` until the join; the first layer's im2col on a side stream up front)
+        side = _side_stream(g.device) if (g is not None and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
+        main = torch.cuda.current_stream(g.device) if side is not None else None
+        keep = []
+        xk_first = [None]
+        r0 = tape[0]
+        shared0 = r0["x"].shape[1] % 4 != 0
+        if g is not None and shared0:
+            xk_stream = None
+            if side is not None:
+                side.wait_stream(main)
+                xk_stream = side.current
+                with torch.cuda.stream(xk_stream):
+                    xk_first[0] = ops.im2col_pbj(ctx.x_nchw, (E,) + r0["wshape"], *r0["geom"])
+                keep.append(xk_first[0])
+        # every layer's flipped input-gradient weight rows up front (captured / launch-bound steps, as in _MCForward)
+        w_flipped = {}
+        if flips_up_front[0] and side is None and g is not None:
+            w_flipped = {li: ops.flip_transpose_w_bf16(tape[li]["w"], tape[li]["wshape"]) for li in range(1, len(tape))}
+        for li in range(len(tape) - 1, -1, -1):
+            rec = tape[li]
+            if g is None:
+                break
+            y, w, x_in, act, wshape = rec["y"], rec["w"], rec["x"], rec["act"], rec["wshape"]
+            stride, padding, dilation = rec["geom"]
+            g = g.reshape(rec["out_shape"])
+            shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
+            k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
+            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
+                g_pre = g                                                 # already the bf16 output gradient
+            else:
+                g_pre = ops.pool_act_backward_chwn_bf16(g, y if y.dtype == torch.bfloat16 else None, k, s, act, out_f32=shared,
+                                                        pad_planes=shared)
+
+            def weight_side(g_pre=g_pre, x_in=x_in, rec=rec, li=li, shared=shared, stride=stride, padding=padding, dilation=dilation):
+                wsh = (E,) + rec["wshape"]
+                if shared:
+                    gws[2 * li + 1] = ops.plane_sums(g_pre)
+                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, stride, padding, dilation, xk=xk_first[0])
+                else:
+                    gws[2 * li + 1] = ops.plane_sums_bf16(g_pre)
+                    gw = ops.conv2d_chwn_weight_grad_bf16(g_pre, x_in, wsh, stride, padding, dilation)
+                gws[2 * li] = gw.reshape(ws_shape(rec))
+
+            if side is not None and not rec["first"]:
+                keep.append(g_pre)
+                side.wait_stream(main)
+                with torch.cuda.stream(side.current):
+                    weight_side()
+            else:
+                if rec["first"] and xk_first[0] is not None:
+                    main.wait_stream(xk_stream)
+                weight_side()
+            if not rec["first"]:
+                g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
+                                                    w_flipped=w_flipped.get(li))
+            else:
+                g = None
+        if side is not None:
+            for st_ in side.streams:
+                main.wait_stream(st_)
+        del keep
+        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
+        out = [None, None]
+        for a, b in zip(gmu, grho):
+            out += [a, b]
+        return tuple(out)
+
+
 fold_lrt_combine = [True]       # an LRT layer's g1 + 2 x g2 is formed inside the pooling / activation backward of the layer below
 flips_up_front = [True]         # every layer's flipped input-gradient weights in one launch at the start of the backward
 pair_lrt_backward = [True]      # an LRT layer's (mean, variance) gradient pairs as the two draws of one launch (see _MCForwardLRT._backward)
@@ -467,16 +625,47 @@ class _MCForwardLRT(torch.autograd.Function):
         return (None, None, *grads)
 
 
-def mc_logits_autograd(net, x, draws, seed, call0, alias=None):
+def bf16_train_refusal(net, x):
+    """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
+        return "a 4-d fp32 CUDA batch"
+    from . import ensemble
+    if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
+        return "no eps replay"
+    kind = train_path_ok(net, x)
+    if kind == "lrt":
+        return "BBB (weight-space) layers; local-reparameterisation layers have no bf16 mode"
+    if kind is None:
+        return "a model and input on the batch-innermost training path (fast_train.train_path_ok)"
+    if x.shape[0] % 8 != 0:
+        return "a batch size that is a multiple of 8"
+    return None
+
+
+def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32"):
     """Differentiable batched forward: -> (logits [E, C, B] batch-innermost, kl of one forward), gradients flow to every
     layer's W_mu, W_rho, bias_mu, bias_rho.  Call only when train_path_ok(net, x).
     alias: {id(parameter): leaf tensor sharing its storage} -- the autograd graph is then rooted at those leaves instead of the
-    parameters (train.GraphedTrainStep: fresh leaves have no gradient accumulator bound to another stream)."""
+    parameters (train.GraphedTrainStep: fresh leaves have no gradient accumulator bound to another stream).
+    precision="bf16": the bf16 storage mode (_MCForwardBF16); what it does not cover raises BBBHipError (bf16_train_refusal)."""
     def A(t):
         return t if alias is None else alias.get(id(t), t)
 
     from . import ensemble
     _lib.require_device(x)
+    if precision not in ("fp32", "bf16"):
+        raise _lib.BBBHipError(f"training precision must be 'fp32' or 'bf16', got {precision!r}")
+    if precision == "bf16":
+        why = bf16_train_refusal(net, x)
+        if why is not None:
+            raise _lib.BBBHipError("bf16 training covers " + why)
+        params = []
+        for l in ensemble.bayesian_layers(net):
+            params += [A(l.W_mu), A(l.W_rho), A(l.bias_mu), A(l.bias_rho)]
+        cfg = dict(net=net, draws=int(draws), seed=seed, call0=call0)
+        logits, kl = _MCForwardBF16.apply(cfg, x, *params)
+        logits.bbb_cfg = cfg
+        return logits, kl
     kind = train_path_ok(net, x)
     if kind == "lrt":
         layers = ensemble.bayesian_layers(net)

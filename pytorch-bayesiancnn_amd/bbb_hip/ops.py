@@ -2254,6 +2254,164 @@ def conv2d_chwn_weight_grad_shared_input(g_pre, x_nchw, w_shape, stride, padding
     return gw[:, :J].reshape(E, Cout, Cin, kh, kw)
 
 
+# ---- bf16 training backward (fast_train._MCForwardBF16) ------------------------------------------------
+
+def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=False):
+    """pool_act_backward_chwn on bf16 storage (bbb_pool_act_bwd_chwn_bf16): y = the stored bf16 activated output [..., H, W, B],
+    g_out the bf16 (or, the logits layer's, fp32) gradient w.r.t. the (pooled) output -> g_pre = act'(y) * route(g_out) in fp32,
+    rounded once to bf16.  out_f32: the rounded values as fp32 (the first layer's fp32 weight gradient), pad_planes as there.
+    y = None (k = 0, no activation): the rounding of g_out alone (the logits layer, whose output is fp32)."""
+    if g_out.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BBBHipError("pool_act_backward_chwn_bf16: g_out must be bf16 or fp32")
+    require_device(g_out, dtype=g_out.dtype)
+    if y is None:
+        if int(k) != 0 or act is not None:
+            raise _lib.BBBHipError("pool_act_backward_chwn_bf16: pooling / activation backward needs the stored output y")
+    else:
+        require_device(y, dtype=torch.bfloat16)
+        y = y.contiguous()
+    g_out = g_out.contiguous()
+    shape = tuple(g_out.shape) if y is None else tuple(y.shape)
+    *lead, H, W, B = shape
+    planes = 1
+    for v in lead:
+        planes *= v
+    K = H * W * B
+    pitch = padded_plane_pitch(K) if pad_planes else K
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if pitch != K:
+        buf = torch.empty((planes, pitch), dtype=dt, device=g_out.device)
+        g_pre = buf[:, :K].view(*lead, H, W, B)
+    else:
+        buf = g_pre = torch.empty(shape, dtype=dt, device=g_out.device)
+    flags = (1 if g_out.dtype == torch.float32 else 0) | (2 if out_f32 else 0)
+    with on_device(g_out.device):
+        check(_lib.lib().bbb_pool_act_bwd_chwn_bf16(g_out.data_ptr(), ptr(y), buf.data_ptr(), planes, H, W, B, int(k), int(s),
+                                                    ACT_CODE[act], pitch if pitch != K else 0, flags, cur_stream(g_out.device)),
+              "bbb_pool_act_bwd_chwn_bf16")
+    return g_pre
+
+
+def plane_sums_bf16(g):
+    """plane_sums of a bf16 g [E, C, H, W, B]: -> fp32 [E, C] (bbb_plane_sum_bf16, fp32 accumulation in a fixed order)."""
+    require_device(g, dtype=torch.bfloat16)
+    g = g.contiguous()
+    E, C, H, W, B = g.shape
+    out = torch.empty((E, C), dtype=torch.float32, device=g.device)
+    with on_device(g.device):
+        check(_lib.lib().bbb_plane_sum_bf16(g.data_ptr(), out.data_ptr(), E * C, H * W * B, H * W * B, cur_stream(g.device)),
+              "bbb_plane_sum_bf16")
+    return out
+
+
+def flip_transpose_w_bf16(w, w_shape):
+    """The input gradient's weight operand from sampled bf16 rows: w [E, Cout, Kp] (sample_weights_bf16's layout and column order,
+    bf16_tap_major(w_shape)) of a layer with weights w_shape = (Cout, Cin, kh, kw) -> [E, Cin, Kp'] with the taps flipped and the
+    channels transposed, Kp' = Cout * kh * kw rounded up to 8, tap-major where bf16_tap_major((Cin, Cout, kh, kw))."""
+    require_device(w, dtype=torch.bfloat16)
+    w = w.contiguous()
+    Cout, Cin, kh, kw = w_shape
+    E = w.shape[0]
+    if w.shape[1] != Cout or w.shape[2] != bf16_row_pitch(Cin * kh * kw):
+        raise _lib.BBBHipError("flip_transpose_w_bf16: rows do not match the weight shape")
+    flags = (1 if bf16_tap_major((Cout, Cin, kh, kw)) else 0) | (2 if bf16_tap_major((Cin, Cout, kh, kw)) else 0)
+    out = torch.empty((E, Cin, bf16_row_pitch(Cout * kh * kw)), dtype=torch.bfloat16, device=w.device)
+    with on_device(w.device):
+        check(_lib.lib().bbb_flip_transpose_w_bf16(w.data_ptr(), out.data_ptr(), E, Cout, Cin, kh * kw, flags, cur_stream(w.device)),
+              "bbb_flip_transpose_w_bf16")
+    return out
+
+
+def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_flipped=None):
+    """conv2d_chwn_input_grad on bf16 storage: g_pre [E, Cout, Ho, Wo, B] bf16, w [E, Cout, Kp] sampled bf16 rows of a stride-1
+    layer with weights w_shape = (Cout, Cin, kh, kw) -> bf16 [E, Cin, H, W, B] (conv2d_chwn_bf16_forward on the flipped rows,
+    padding d*(k-1) - p; fp32 accumulation, one rounding).  w_flipped: flip_transpose_w_bf16(w, w_shape) computed ahead."""
+    Cout, Cin, kh, kw = w_shape
+    (ph, pw), (dh, dw) = _pair(padding), _pair(dilation)
+    qh, qw = dh * (kh - 1) - ph, dw * (kw - 1) - pw
+    if qh < 0 or qw < 0:
+        raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: padding larger than the kernel reach")
+    w_t = w_flipped if w_flipped is not None else flip_transpose_w_bf16(w, w_shape)
+    gx = conv2d_chwn_bf16_forward(g_pre, w_t, None, (Cout, kh, kw), 1, (qh, qw), (dh, dw), tap_major=bf16_tap_major((Cin, Cout, kh, kw)))
+    if gx.shape[2] != x_hw[0] or gx.shape[3] != x_hw[1]:
+        raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: geometry mismatch (stride-1 layers only)")
+    return gx
+
+
+def chwn_to_bhwc_bf16(x, c_pad=None):
+    """bf16 [E, C, H, W, B] -> [E, B, H, W, Cp] (bbb_chwn_to_bhwc_bf16), Cp = c_pad (default C rounded up to 8), pad channels zero."""
+    require_device(x, dtype=torch.bfloat16)
+    x = x.contiguous()
+    E, C, H, W, B = x.shape
+    Cp = ((C + 7) & ~7) if c_pad is None else int(c_pad)
+    out = torch.empty((E, B, H, W, Cp), dtype=torch.bfloat16, device=x.device)
+    with on_device(x.device):
+        check(_lib.lib().bbb_chwn_to_bhwc_bf16(x.data_ptr(), out.data_ptr(), E, C, H * W, B, Cp, cur_stream(x.device)), "bbb_chwn_to_bhwc_bf16")
+    return out
+
+
+def batch_chunks_bf16(g, chunks):
+    """bf16 [E, *R, B] -> [E, S, *R, B / S] (bbb_batch_chunks_bf16): S batch chunks of each row, chunk-major."""
+    require_device(g, dtype=torch.bfloat16)
+    g = g.contiguous()
+    E, B = g.shape[0], g.shape[-1]
+    S = int(chunks)
+    R = g.numel() // (E * B)
+    out = torch.empty((E, S) + tuple(g.shape[1:-1]) + (B // S,), dtype=torch.bfloat16, device=g.device)
+    with on_device(g.device):
+        check(_lib.lib().bbb_batch_chunks_bf16(g.data_ptr(), out.data_ptr(), E, R, B, S, cur_stream(g.device)), "bbb_batch_chunks_bf16")
+    return out
+
+
+def wgrad_batch_chunks_bf16(E, Cout, Cp, kh, kw, B):
+    """The number S of batch chunks conv2d_chwn_weight_grad_bf16 runs as extra draws (a K split): doubled while the role-swapped
+    launch (workgroups of one output pixel x 64 channels x 128 images) would occupy fewer than 512 workgroups and every chunk
+    keeps >= 16 images, a multiple of 8."""
+    wgs = E * kh * kw * -(-Cout // 64) * -(-Cp // 128)
+    S = 1
+    while wgs * S < 512 and B % (16 * S) == 0 and B // (2 * S) >= 16:
+        S *= 2
+    return S
+
+
+wgrad_chunks_bf16 = [True]      # False: one role-swapped launch reading the output gradient in place, whatever its size
+
+
+def conv2d_chwn_weight_grad_bf16(g_pre, x, w_shape, stride, padding, dilation):
+    """conv2d_chwn_weight_grad on bf16 storage, on the bf16 forward kernel with the roles swapped: the batch becomes the contraction
+    channels, the layer's input channels (padded with zero planes to a multiple of 8) the 16-byte "image" axis, the output pixels
+    the kernel taps.  g_pre [E, Cout, Ho, Wo, B] bf16 IS a tap-major weight operand (taps = output pixels, channels = images, row
+    length Ho*Wo*B): read in place, or -- when the launch would leave the chip short of workgroups -- as S batch chunks
+    (batch_chunks_bf16) that run as extra draws and are summed in a fixed order.  x [E|1, Cin, H, W, B] bf16 ->
+    fp32 [E, Cout, Cin, kh, kw] (fp32 accumulation, never rounded)."""
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    Ew, Cout, Cin, kh, kw = w_shape
+    E, B = g_pre.shape[0], g_pre.shape[4]
+    Ho, Wo = g_pre.shape[2], g_pre.shape[3]
+    Cp = (Cin + 7) & ~7
+    S = wgrad_batch_chunks_bf16(E, Cout, Cp, kh, kw, B) if wgrad_chunks_bf16[0] else 1
+    xr = chwn_to_bhwc_bf16(x, Cp)                                      # [E|1, B, H, W, Cp]
+    if S > 1:
+        gr = batch_chunks_bf16(g_pre, S).reshape(E * S, Cout, Ho * Wo * (B // S))
+        if xr.shape[0] == 1 and E > 1:
+            xr = xr.expand(E, *xr.shape[1:])
+        xr = xr.reshape(xr.shape[0] * S, B // S, *xr.shape[2:])
+    else:
+        gr = g_pre.contiguous().reshape(E, Cout, Ho * Wo * B)
+    Bs = B // S
+    y = conv2d_chwn_bf16_forward(xr, gr, None, (Bs, Ho, Wo), (dh, dw), (ph, pw), (sh, sw), out_f32=True,
+                                 tap_major=Ho * Wo > 1)               # [E*S, Cout, kh', kw', Cp] fp32, kh' >= kh
+    T = kh * kw
+    if y.shape[2] == kh and y.shape[3] == kw:
+        gw = torch.empty((E, Cout, Cin, kh, kw), dtype=torch.float32, device=y.device)
+        if _transpose_sum_batched(y, gw, T, Cin, (E, Cout, 1), (S * Cout * T * Cp, T * Cp, 0), (Cout * Cin * T, Cin * T, 0), Cp, T,
+                                  S, Cout * T * Cp):
+            return gw
+    if S > 1:
+        y = y.reshape(E, S, *y.shape[1:]).sum(1)
+    return y[:, :, :kh, :kw, :Cin].permute(0, 1, 4, 2, 3).contiguous()
+
+
 class _OpsModule(types.ModuleType):
     """`ops.gemm_mode`, `ops.split_k`, ... read and write the fields of the process-default LaunchConfig (compatibility with the
     round-1..4 switches; prefer `use_config` / `launch_config=`)."""

@@ -160,16 +160,31 @@ def elbo(log_outputs, target, kl, beta, train_size):
     return F.nll_loss(log_outputs, target, reduction="mean") * train_size + beta * kl
 
 
-def forward_loss(net, x, target, num_ens, beta, train_size, seed_call=None, param_alias=None):
+def _check_train_precision(precision):
+    if precision not in ("fp32", "bf16"):
+        raise _lib.BBBHipError(f"training precision must be 'fp32' or 'bf16', got {precision!r}")
+
+
+def forward_loss(net, x, target, num_ens, beta, train_size, seed_call=None, param_alias=None, precision="fp32"):
     """The forward half of a training iteration (main_bayesian.py:43-56): num_ens stochastic forwards batched over the draws,
     kl of one forward (= the reference's kl / num_ens), logmeanexp, ELBO -> (loss, log_outputs, kl).  On the batch-innermost
     autograd path the loss tail is two HIP launches forward and one backward (ops.elbo_cb_autograd); elsewhere torch ops.
-    seed_call: (seed, call0) reserved by the caller (a captured step); default: num_ens fresh call indices."""
+    seed_call: (seed, call0) reserved by the caller (a captured step); default: num_ens fresh call indices.
+    precision: "fp32" (the reference's arithmetic) or "bf16" -- sampled weights, activations and the gradients passed between
+    layers stored as bf16, parameters, their gradients, KL and the loss fp32; BBB models on the
+    batch-innermost training path with B % 8 == 0 only, anything else raises BBBHipError."""
+    _check_train_precision(precision)
+    if precision == "bf16" and torch.is_grad_enabled():
+        from . import fast_train
+        why = fast_train.bf16_train_refusal(net, x) if ensemble.fast_autograd else "the batch-innermost autograd path"
+        if why is not None:
+            raise _lib.BBBHipError("bf16 training covers " + why)
     if seed_call is None:
         rng.assign_stream_ids(net)
         seed_call = rng.next_calls(int(num_ens))
     req = [target, beta, float(train_size), None]
-    log_outputs, kl = ensemble._local_lse(net, x, int(num_ens), seed_call[0], seed_call[1], int(num_ens), param_alias=param_alias, elbo=req)
+    log_outputs, kl = ensemble._local_lse(net, x, int(num_ens), seed_call[0], seed_call[1], int(num_ens), param_alias=param_alias, elbo=req,
+                                          precision=precision)
     loss = req[3] if req[3] is not None else elbo(log_outputs, target, kl, beta, train_size)
     return loss, log_outputs, kl
 
@@ -225,7 +240,7 @@ def _python_hooks(net, optimizer):
     return any(getattr(p, "_backward_hooks", None) for p in net.parameters())
 
 
-def _auto_key(net, optimizer, x, target, num_ens, train_size):
+def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
     """What a captured step bakes in; None = this call cannot be a graph replay (-> eager)."""
     if not (auto_graph["enabled"] and isinstance(optimizer, FusedAdam) and torch.is_tensor(x) and x.is_cuda and target.is_cuda
             and torch.is_grad_enabled() and not x.requires_grad and not torch.cuda.is_current_stream_capturing()):
@@ -237,10 +252,11 @@ def _auto_key(net, optimizer, x, target, num_ens, train_size):
     from . import rng
     return (id(optimizer), getattr(optimizer, "_state_generation", 0), tuple(x.shape), x.dtype, tuple(target.shape), target.dtype,
             int(num_ens), float(train_size), net.training,
-            ensemble._epoch[0], groups, rng.next_calls(0)[0])               # the noise seed is a constant of the captured kernels
+            ensemble._epoch[0], groups, rng.next_calls(0)[0],               # the noise seed is a constant of the captured kernels
+            precision)
 
 
-def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=None, graph=None):
+def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=None, graph=None, precision="fp32"):
     """One iteration of train_model's batch loop (main_bayesian.py:40-58): zero_grad, num_ens stochastic forwards
     (batched over draws), kl / num_ens, logmeanexp, ELBO, backward, [gradient all-reduce], optimizer.step.
     dp_group: data-parallel process group whose ranks hold different shards of the batch (parameters replicated).
@@ -252,9 +268,11 @@ def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=No
     eager iteration on a capture stream, records it as a GraphedTrainStep and replays that from then on (beta and the learning
     rate stay run-time values; a non-capturable FusedAdam is switched to capturable in place).  Any change of the key drops the
     graph and returns to launch-by-launch steps.  graph=False: never capture.  Same noise calls, same results as the eager
-    sequence (tests/test_gpu_train.py)."""
+    sequence (tests/test_gpu_train.py).
+    precision: "fp32" or "bf16" (forward_loss); part of the self-capture key, so fp32 and bf16 calls never replay each other's graph."""
+    _check_train_precision(precision)
     small = graph is True or x.shape[0] * int(num_ens) < int(auto_graph.get("max_rows", 1 << 62))     # (graph=True: capture whatever the size)
-    key = _auto_key(net, optimizer, x, target, num_ens, train_size) if (graph is not False and dp_group is None and small) else None
+    key = _auto_key(net, optimizer, x, target, num_ens, train_size, precision) if (graph is not False and dp_group is None and small) else None
     st = _auto.get(net)
     if key is None or st is None or st["key"] != key:
         if key is not None:
@@ -269,14 +287,15 @@ def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=No
         st["streak"] += 1
         if st["streak"] > int(auto_graph["after"]) and not _python_hooks(net, optimizer):
             optimizer.make_capturable()
-            g = GraphedTrainStep(net, optimizer, x, target, num_ens, beta, train_size, warmup=1, weak_net=True)   # the warm-up IS this iteration
+            g = GraphedTrainStep(net, optimizer, x, target, num_ens, beta, train_size, warmup=1, weak_net=True,   # the warm-up IS this iteration
+                                 precision=precision)
             if g.graph is not None:
                 st["graphed"] = g
             else:
                 st["streak"] = -(1 << 60)            # capture refused (stale gradient accumulators): launch by launch from here on
             return g.warm_loss.clone(), g.warm_log_outputs.clone(), g.warm_kl.clone()
     optimizer.zero_grad()
-    loss, log_outputs, kl = forward_loss(net, x, target, num_ens, beta, train_size)
+    loss, log_outputs, kl = forward_loss(net, x, target, num_ens, beta, train_size, precision=precision)
     loss.backward()
     if dp_group is not None:
         allreduce_gradients([p for g in optimizer.param_groups for p in g["params"]], dp_group)
@@ -294,11 +313,15 @@ class GraphedTrainStep:
     the learning rate (ReduceLROnPlateau, main_bayesian.py:118) are DEVICE scalars the graph reads at run time:
     step(beta=...) sets the former, optimizer.param_groups[i]['lr'] is pushed before every replay.
     `warmup` real training iterations run eagerly on the capture stream first.
-    The optimizer must be FusedAdam(capturable=True) (or another capturable optimizer that keeps lr on the device)."""
+    The optimizer must be FusedAdam(capturable=True) (or another capturable optimizer that keeps lr on the device).
+    precision: "fp32" or "bf16" (forward_loss), a constant of the captured graph."""
 
-    def __init__(self, net, optimizer, x, target, num_ens, beta, train_size, warmup=3, weak_net=False, launch_config=None):
+    def __init__(self, net, optimizer, x, target, num_ens, beta, train_size, warmup=3, weak_net=False, launch_config=None,
+                 precision="fp32"):
         from . import rng
         _lib.require_device(x)
+        _check_train_precision(precision)
+        self.precision = precision
         self.launch_config = (launch_config if launch_config is not None else ops.current_config()).copy()
         # weak_net (train_step's self-capture keeps this object ON the net): no net -> state -> step -> net cycle, so dropping the
         # net frees the graph then and there instead of whenever the cyclic collector runs (possibly inside another capture)
@@ -360,7 +383,8 @@ class GraphedTrainStep:
         if ensemble.fast_autograd and fast_train.train_path_ok(self.net, self.x):
             alias = {id(p): p.detach().requires_grad_(True) for p in params}
         loss, log_outputs, kl = forward_loss(self.net, self.x, self.target, self.num_ens, self.beta, self.train_size,   # kl of one forward
-                                             seed_call=(self.seed, self.call0), param_alias=alias)           # = kl / num_ens of the sum
+                                             seed_call=(self.seed, self.call0), param_alias=alias,           # = kl / num_ens of the sum
+                                             precision=self.precision)
         leaves = params if alias is None else [alias[id(p)] for p in params]
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         for p, g in zip(params, grads):
