@@ -76,11 +76,47 @@ def layer_plan(net_type):
     return plan
 
 
-def step_grads(net_type, params, x, target, eps, activation, beta, train_size, rounding=True):
-    """One training step of the contract.  params: name -> {W_mu, W_rho, bias_mu, bias_rho} (numpy fp32) + '_prior_mu',
-    '_prior_sigma'; eps: a list over draws of name -> {'W': ..., 'bias': ...} (numpy); x [B, C, H, W], target [B] (numpy).
-    Returns (loss, log_outputs [B, C], {name: {W_mu, W_rho, bias_mu, bias_rho}} gradients), float64 numpy."""
-    plan = layer_plan(net_type)
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else tuple(int(t) for t in v)
+
+
+def general_plan(plan, activation=None):
+    """A layer plan in its general form: [dict(name, kind, stride, padding, dilation, act, pool, flat)] with per-axis (h, w)
+    stride / padding / dilation, act None / "relu" / "softplus" per layer, pool (k, s) or None, flat = the row length a
+    FlattenLayer after the layer (and its pool) keeps, or None.  A linear layer whose input is still 4-d (a first layer behind a
+    FlattenLayer) flattens it first.  plan: a net_type (layer_plan, every activation = `activation`), a list of layer_plan's
+    tuples (likewise), or a list of such dicts (stride / padding / dilation may be ints; dilation defaults to 1)."""
+    if isinstance(plan, str):
+        plan = layer_plan(plan)
+    out = []
+    for ent in plan:
+        if isinstance(ent, dict):
+            d = dict(ent)
+            d.setdefault("dilation", 1)
+            d.setdefault("act", None)
+            d.setdefault("pool", None)
+            d.setdefault("flat", None)
+        else:
+            name, kind, stride, pad, act, pool, flat = ent
+            d = dict(name=name, kind=kind, stride=stride, padding=pad, dilation=1, act=activation if act else None, pool=pool,
+                     flat=flat)
+        for key in ("stride", "padding", "dilation"):
+            d[key] = _pair(d[key])
+        d["pool"] = None if d["pool"] is None else (int(d["pool"][0]), int(d["pool"][1]))
+        out.append(d)
+    return out
+
+
+def _conv_fwd(h, w, b, L):
+    return F.conv2d(h, w, b, L["stride"], L["padding"], L["dilation"])
+
+
+def step_grads(plan, params, x, target, eps, activation, beta, train_size, rounding=True):
+    """One training step of the contract.  plan: a net_type or a layer plan (general_plan); activation: the activation of a
+    net_type's / layer_plan tuples' layers (a plan of dicts names its own).  params: name -> {W_mu, W_rho, bias_mu, bias_rho}
+    (numpy fp32) + '_prior_mu', '_prior_sigma'; eps: a list over draws of name -> {'W': ..., 'bias': ...} (numpy); x [B, C, H, W],
+    target [B] (numpy).  Returns (loss, log_outputs [B, C], {name: {W_mu, W_rho, bias_mu, bias_rho}} gradients), float64 numpy."""
+    plan = general_plan(plan, activation)
     E = len(eps)
     R = lambda t: _round(t, rounding)
     pm, ps = float(params["_prior_mu"]), float(params["_prior_sigma"])
@@ -88,13 +124,16 @@ def step_grads(net_type, params, x, target, eps, activation, beta, train_size, r
     tapes, logits = [], []
     for e in range(E):
         h, tape = xin, []
-        for li, (name, kind, stride, pad, act, pool, flat) in enumerate(plan):
+        for li, L in enumerate(plan):
+            name, kind, act, pool, flat = L["name"], L["kind"], L["act"], L["pool"], L["flat"]
             p = params[name]
             w = R(_sample(p["W_mu"], p["W_rho"], eps[e][name]["W"]))
             b = _sample(p["bias_mu"], p["bias_rho"], eps[e][name]["bias"])
             last = li == len(plan) - 1
-            v = F.conv2d(h, w, b, stride, pad) if kind == "conv" else F.linear(h, w, b)
-            y = _act(v, activation) if act else v
+            if kind == "fc" and h.dim() != 2:
+                h = h.reshape(h.shape[0], -1)
+            v = _conv_fwd(h, w, b, L) if kind == "conv" else F.linear(h, w, b)
+            y = _act(v, act) if act else v
             if not last:
                 y = R(y)
             out = F.max_pool2d(y, *pool) if pool else y
@@ -106,23 +145,25 @@ def step_grads(net_type, params, x, target, eps, activation, beta, train_size, r
     lg = torch.stack(logits).detach().requires_grad_(True)
     lo = torch.logsumexp(F.log_softmax(lg, dim=2), dim=0) - np.log(E)
     nll = F.nll_loss(lo, torch.from_numpy(np.asarray(target, np.int64)), reduction="mean") * train_size
-    kl = sum(_kl(params[n][k + "_mu"], params[n][k + "_rho"], pm, ps) for n, *_ in plan for k in ("W", "bias"))
+    kl = sum(_kl(params[L["name"]][k + "_mu"], params[L["name"]][k + "_rho"], pm, ps) for L in plan for k in ("W", "bias"))
     loss = float(nll.detach()) + beta * kl
     (g_lg,) = torch.autograd.grad(nll, lg)
-    grads = {n: dict(W_mu=0.0, W_rho=0.0, bias_mu=0.0, bias_rho=0.0) for n, *_ in plan}
+    grads = {L["name"]: dict(W_mu=0.0, W_rho=0.0, bias_mu=0.0, bias_rho=0.0) for L in plan}
     for e in range(E):
         g = R(g_lg[e])
         for li in range(len(plan) - 1, -1, -1):
-            name, kind, stride, pad, act, pool, flat = plan[li]
+            L = plan[li]
+            name, kind, act, pool = L["name"], L["kind"], L["act"], L["pool"]
+            geom = dict(stride=L["stride"], padding=L["padding"], dilation=L["dilation"])
             rec = tapes[e][li]
             g = g.reshape(rec["out_shape"])
             if pool:
                 g = _route(g, rec["y"], *pool)
             if act:
-                g = g * _act_grad(rec["y"], activation)
+                g = g * _act_grad(rec["y"], act)
             g_pre = R(g) if (pool or act) else g
             if kind == "conv":
-                gw = torch.nn.grad.conv2d_weight(rec["x"], tuple(rec["w"].shape), g_pre, stride, pad)
+                gw = torch.nn.grad.conv2d_weight(rec["x"], tuple(rec["w"].shape), g_pre, **geom)
                 gb = g_pre.sum(dim=(0, 2, 3))
             else:
                 gw = g_pre.t() @ rec["x"]
@@ -135,43 +176,46 @@ def step_grads(net_type, params, x, target, eps, activation, beta, train_size, r
                 grads[name][key + "_rho"] = grads[name][key + "_rho"] + (gg * ep * sgm).numpy()
             if li > 0:
                 if kind == "conv":
-                    gx = torch.nn.grad.conv2d_input(tuple(rec["x"].shape), rec["w"], g_pre, stride, pad)
+                    gx = torch.nn.grad.conv2d_input(tuple(rec["x"].shape), rec["w"], g_pre, **geom)
                 else:
                     gx = g_pre @ rec["w"]
                 g = R(gx)
-    for name, *_ in plan:
-        p = params[name]
+    for L in plan:
+        p = params[L["name"]]
         for key in ("W", "bias"):
             gm, gr = O.kl_grads(p[key + "_mu"], p[key + "_rho"], pm, ps)
-            grads[name][key + "_mu"] = grads[name][key + "_mu"] + beta * gm
-            grads[name][key + "_rho"] = grads[name][key + "_rho"] + beta * gr
+            grads[L["name"]][key + "_mu"] = grads[L["name"]][key + "_mu"] + beta * gm
+            grads[L["name"]][key + "_rho"] = grads[L["name"]][key + "_rho"] + beta * gr
     return loss, lo.detach().numpy(), grads
 
 
-def autograd_grads(net_type, params, x, target, eps, activation, beta, train_size):
+def autograd_grads(plan, params, x, target, eps, activation, beta, train_size):
     """The same step (no rounding) differentiated by torch autograd in float64: what step_grads(rounding=False) must equal."""
-    plan = layer_plan(net_type)
+    plan = general_plan(plan, activation)
     E = len(eps)
     pm, ps = float(params["_prior_mu"]), float(params["_prior_sigma"])
-    leaves = {n: {k: torch.from_numpy(params[n][k].astype(np.float64)).requires_grad_(True) for k in ("W_mu", "W_rho", "bias_mu", "bias_rho")}
-              for n, *_ in plan}
+    leaves = {L["name"]: {k: torch.from_numpy(params[L["name"]][k].astype(np.float64)).requires_grad_(True)
+                          for k in ("W_mu", "W_rho", "bias_mu", "bias_rho")} for L in plan}
     sp = lambda r: torch.log1p(torch.exp(r))
     xin = torch.from_numpy(np.asarray(x, np.float32)).to(F64)
     logits = []
     for e in range(E):
         h = xin
-        for name, kind, stride, pad, act, pool, flat in plan:
-            L = leaves[name]
-            w = L["W_mu"] + torch.from_numpy(eps[e][name]["W"].astype(np.float64)) * sp(L["W_rho"])
-            b = L["bias_mu"] + torch.from_numpy(eps[e][name]["bias"].astype(np.float64)) * sp(L["bias_rho"])
-            v = F.conv2d(h, w, b, stride, pad) if kind == "conv" else F.linear(h, w, b)
-            y = _act(v, activation) if act else v
+        for L in plan:
+            name, kind, act, pool, flat = L["name"], L["kind"], L["act"], L["pool"], L["flat"]
+            Lv = leaves[name]
+            w = Lv["W_mu"] + torch.from_numpy(eps[e][name]["W"].astype(np.float64)) * sp(Lv["W_rho"])
+            b = Lv["bias_mu"] + torch.from_numpy(eps[e][name]["bias"].astype(np.float64)) * sp(Lv["bias_rho"])
+            if kind == "fc" and h.dim() != 2:
+                h = h.reshape(h.shape[0], -1)
+            v = _conv_fwd(h, w, b, L) if kind == "conv" else F.linear(h, w, b)
+            y = _act(v, act) if act else v
             h = F.max_pool2d(y, *pool) if pool else y
             h = h.reshape(h.shape[0], flat) if flat else h
         logits.append(h)
     lo = torch.logsumexp(F.log_softmax(torch.stack(logits), dim=2), dim=0) - np.log(E)
     kl = 0.0
-    for n, *_ in plan:
+    for n in leaves:
         for key in ("W", "bias"):
             s = sp(leaves[n][key + "_rho"])
             t = 2.0 * torch.log(s / ps) - 1.0 + (ps / s) ** 2 + ((leaves[n][key + "_mu"] - pm) / s) ** 2

@@ -922,3 +922,46 @@ def test_train_fuzz_branch_coverage():
     from bbb_hip import ops
     assert ops.wgrad_batch_chunks(3, 5, 4, 3, 2, 132) == 4 and ops.wgrad_batch_chunks(1, 64, 192, 3, 3, 4) == 1
     assert ops.shared_input_k_slices(64, 364, 56 * 56 * 4) >= 2 and ops.shared_input_k_slices(96, 64, 5 * 5 * 4) == 1
+
+
+def test_bf16_train_fuzz_branch_coverage():
+    """The fixed case lists of test_gpu_bf16_train_fuzz.py reach every branch of the bf16 training backward's launchers: weight-
+    gradient batch chunks S == 1 / 2 / >= 4 (shared and per-draw x) and chunks off, the kh' > kh slice of a strided role-swapped
+    launch with and without chunks, Cin padded to 8, one-pixel output maps, linear layers (a shared x expanded over chunks), the four
+    row orders of the flipped dgrad operand, every GEMM form of bbb_conv2d_chwn_bf16_fwd the backward launches (gemm_form restates the
+    dispatcher), pools with overlap, gaps, tiles and floor-dropped rows / columns on H != W under all three activations and both
+    incoming dtypes, the shared-input first layer on 1..7 channels in both g_pre pitch forms, and models with every kind of first
+    layer.  The choices are ops' own helpers, the ones the launchers call."""
+    import test_gpu_bf16_train_fuzz as T
+    from bbb_hip import ops
+    conv = set().union(*(T.conv_branches(c) for c in T.CONV_CASES.values()))
+    conv_off = set().union(*(T.conv_branches(c, chunks=False) for c in T.CONV_CASES.values()))
+    assert {"wgrad-S1-shared", "wgrad-S1-perdraw", "wgrad-S2+-shared", "wgrad-S2+-perdraw", "wgrad-S2", "wgrad-S4+",
+            "wgrad-khslice-S1", "wgrad-khslice-S2+", "wgrad-cinpad", "wgrad-1pixel", "linear", "linear-shared",
+            "linear-shared-expand", "dgrad-plain", "dgrad-flipped", "dgrad-q0",
+            "flip-inCM-outCM", "flip-inCM-outTM", "flip-inTM-outCM", "flip-inTM-outTM"} <= conv, conv
+    forms = {"general", "shape12", "shape14", "shape22", "tiny", "ws", "kg1", "kg2", "items<512", "items>=512"}
+    assert {"dgrad:" + t for t in forms | {"smallk", "fewout-bf16"}} <= conv, conv
+    assert {"wgrad:" + t for t in forms - {"shape14"}} <= conv, conv
+    assert "wgrad:fewout-f32" in conv_off and "wgrad-khslice-S1" in conv_off
+    pools = [T.pool_branches(c) for c in T.POOL_CASES.values()]
+    for want in ("overlap", "gap", "tiled", "act-only"):
+        for act in ("None", "relu", "softplus"):
+            if want != "act-only" or act != "None":
+                assert any({want, "act-" + act} <= b for b in pools), (want, act)
+    for want in ({"gap", "floor-rows", "floor-cols", "h!=w"}, {"overlap", "floor-rows", "floor-cols", "h!=w"}, {"g-f32"}, {"g-bf16"}):
+        assert any(want <= b for b in pools), want
+    shared = set().union(*(T.shared_branches(c) for c in T.SHARED_CASES.values()))
+    assert {"shared-S1", "shared-S2+", "gpre-contiguous", "gpre-padded-view", "strided", "dilated"} <= shared, shared
+    assert {f"cin{c}" for c in (1, 2, 5, 6, 7)} <= shared, shared
+    models = set().union(*(T.model_branches(s) for s in T.MODELS.values()))
+    assert {"first-bf16-wgrad-cin4", "first-bf16-wgrad-cin8", "first-bf16-wgrad-strided", "first-linear", "first-shared-cin1",
+            "first-shared-cin2", "first-shared-cin5", "first-shared-cin7", "later-dilated", "later-nonsquare", "pool-gap",
+            "pool-overlap", "act-relu", "act-softplus", "E1", "E2", "E3", "B8", "B24", "B136", "logits-fewout-f32"} <= models, models
+    assert len(T.MODELS) >= 8 and any(T._no_ties(s) for s in T.MODELS.values())
+    # the launchers' own choices, on the shapes that pin them
+    assert ops.wgrad_batch_chunks_bf16(1, 12, 16, 3, 3, 32) == 2 and ops.wgrad_batch_chunks_bf16(1, 8, 8, 3, 2, 64) == 4
+    assert ops.wgrad_batch_chunks_bf16(2, 16, 16, 2, 3, 136) == 1 and ops.wgrad_batch_chunks_bf16(1, 10, 88, 1, 1, 512) == 32
+    assert ops.wgrad_batch_chunks_bf16(1, 128, 128, 5, 5, 4096) == 16 and ops.wgrad_batch_chunks_bf16(10, 384, 256, 3, 3, 512) == 1
+    assert ops.bf16_tap_major((16, 8, 3, 3)) and not ops.bf16_tap_major((16, 8, 1, 1)) and not ops.bf16_tap_major((16, 12, 3, 3))
+    assert ops.bf16_row_pitch(84) == 88 and ops.bf16_row_pitch(96) == 96 and ops.bf16_row_pitch(1) == 8
