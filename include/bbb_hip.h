@@ -552,6 +552,17 @@ int bbb_flip_transpose_w_multi(const bbb_flip_seg_t* segs, int n_segs, void* str
  * weight-gradient GEMM (see bbb_hip/ops.py: conv2d_chwn_weight_grad_shared_input). */
 int bbb_im2col_pbj(const float* x, float* out, const bbb_conv_desc_t* d, void* stream);
 
+/* Training extension, additive in ABI 13: the gather half of a FIRST layer's input gradient (d loss / d x of the caller's batch,
+ * which every draw shares).  The contraction D[(ci, r, q)][ho][wo][b] = sum_(e, co) w[e][co][ci][r][q] * g_pre[e][co][ho][wo][b] runs
+ * on bbb_conv2d_chwn_fwd as a 1x1 convolution (bbb_hip/ops.py: first_layer_input_grad); this folds D onto the input pixels:
+ *   dx[b][ci][h][w] = sum over the taps (r, q) with h = ho*sh - ph + r*dh, w = wo*sw - pw + q*dw of D[(ci, r, q)][ho][wo][b]
+ * (geometry from d: batch, cin, h, w, kh, kw, stride, padding, dilation; the other fields are ignored).  D's rows are row_pitch
+ * (>= ho*wo*batch) elements apart.  x == NULL: dx = that sum.  x != NULL (a local-reparameterisation first layer): D holds two sets,
+ * the second set_stride (>= cin*kh*kw*row_pitch) elements behind the first, and dx = sum(set 0) + 2 * x * sum(set 1) with x the NCHW
+ * input.  dx, x: NCHW [batch][cin][h][w]; pixels no tap reaches get 0.  Taps are added in ascending (r, q) order, no atomics. */
+int bbb_input_grad_col2im(const float* dcol, int64_t row_pitch, int64_t set_stride, const float* x, float* dx,
+                          const bbb_conv_desc_t* d, void* stream);
+
 /* Training extension, the small steps between the gradient GEMMs (ABI 8; deterministic, no atomics):
  * bbb_plane_sum: out[r] = sum over o < outer, j < cols of x[o*outer_stride + r*row_pitch + j] -- bias gradients (the gradient w.r.t.
  *   a layer's pre-activation summed over pixels and images per (draw, channel) plane; outer > 1 also sums over draws: LRT biases).

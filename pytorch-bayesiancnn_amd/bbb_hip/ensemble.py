@@ -847,6 +847,13 @@ def mc_logits(net, x, draws, seed, call0, fuse_act=True, timers=None, eps=None, 
     when it applies (inference, B % 4 == 0, known module kinds), "nchw" forces the reference layout."""
     _lib.require_device(x)
     _check_precision(precision, net, x, layout != "nchw" and eps is None and fuse_act)
+    if (layout != "nchw" and eps is None and precision == "fp32" and not any_requires_grad(net)
+            and _x_grad_node_ok(net, x, fuse_act, timers)):
+        # d/dx with frozen parameters (with trainable ones the reference-layout path below already differentiates in x)
+        from . import fast_train
+        logits_cb, kl = fast_train.mc_logits_autograd(net, x, draws, seed, call0)
+        stats["path"] = "chwn-autograd"
+        return logits_cb.permute(0, 2, 1).contiguous(), kl
     if layout != "nchw" and eps is None and fuse_act and _chwn_ok(net, x):
         out = _mc_logits_chwn(net, x, draws, seed, call0, timers, streams, precision)
         if out is not None:
@@ -957,6 +964,12 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
         stats["path"] = "chwn-autograd-bf16"
         return _autograd_tail(logits_cb, kl1, mean_over, elbo)
     _check_precision(precision, net, x, fuse_act)
+    if (precision == "fp32" and share is None and int(groups) == 1 and (units is None or units[0] <= 1) and not b_offset
+            and step_end is None and _x_grad_node_ok(net, x, fuse_act, timers)):
+        from . import fast_train
+        logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias)
+        stats["path"] = "chwn-autograd"
+        return _autograd_tail(logits_cb, kl1, mean_over, elbo)
     if share is not None:
         D, off = int(share[0]), int(share[1])
         n_steps = -(-(draws + off) // D)
@@ -1017,6 +1030,16 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     else:
         lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail(logits, mean_over=mean_over))
     return lse, kl1
+
+
+def _x_grad_node_ok(net, x, fuse_act, timers):
+    """An input that requires a gradient (saliency maps, adversarial steps) takes the batch-innermost autograd node whenever it
+    applies (fast_train.train_path_ok), the parameters trainable or frozen: its backward ends in the first layer's input gradient
+    (ops.first_layer_input_grad) and, with frozen parameters, skips the weight side."""
+    if not (fuse_act and fast_autograd and timers is None and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad):
+        return False
+    from . import fast_train
+    return fast_train.train_path_ok(net, x) is not None
 
 
 def _autograd_tail(logits_cb, kl1, mean_over, elbo):

@@ -11,6 +11,9 @@ activated output; backward walks the layers in reverse with
                                        im2col of the shared input, K split over the launch's draws,
   * `ops.reparam_kl_backward`          gradients of (mu, rho) from the gradients of the sampled weights + d loss / d KL (eps
                                        regenerated from the counter),
+  * `ops.first_layer_input_grad`       d loss / d x when x requires a gradient (saliency maps, adversarial steps): the first
+                                       layer's contraction over (draw, channel) on the forward kernel + the bbb_input_grad_col2im
+                                       gather; with frozen parameters the weight side above is skipped altogether,
 so no activation, pooling or convolution of the step runs through torch autograd.  What main_bayesian.py:43-58 does per batch:
 E forwards, KL, log_softmax / logmeanexp (the small tail stays in torch), ELBO, backward.
 """
@@ -177,13 +180,17 @@ class _MCForward(torch.autograd.Function):
         mus, rhos, ids, pm, ps, x_shape = ctx.meta
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
         B = x_shape[0]
+        # need_w False (frozen parameters: saliency maps, adversarial steps): no weight side at all -- no bias sums, weight gradients,
+        # im2col, parameter pass or side-stream forks; need_x: the first layer's input gradient (first_layer_input_grad) at the end
+        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
         gws = [None] * len(mus)
+        dx = None
         g = g_logits.contiguous() if g_logits is not None else None
         # a layer's weight / bias gradients and its input gradient are independent: the former run on a side stream beside the latter
         # (both are launches that leave the chip partly idle on their own); joined before the parameter pass's backward.  Tensors
         # the side stream reads stay referenced in `keep` until the join (the allocator must not hand them out again before).
         # (eager launches only: inside a captured step the forks cost more than the overlap gains -- 4.8 against 3.05 ms per step)
-        side = _side_stream(g.device) if (g is not None and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
+        side = _side_stream(g.device) if (g is not None and need_w and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
         main = torch.cuda.current_stream(g.device) if side is not None else None
         keep = []
         # the first layer's im2col depends on the batch alone: on a side stream NOW, beside the small last layers' launches, instead of
@@ -233,20 +240,24 @@ class _MCForward(torch.autograd.Function):
                 side.wait_stream(main)
                 with torch.cuda.stream(side.current):
                     weight_side()
-            else:
+            elif need_w:
                 if rec["first"] and xk_first[0] is not None:
                     main.wait_stream(xk_stream)
                 weight_side()
             if not rec["first"]:
                 g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li))
             else:
+                if need_x:
+                    dx = ops.first_layer_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), stride, padding, dilation).view(x_shape)
                 g = None
         if side is not None:
             for st_ in side.streams:
                 main.wait_stream(st_)
         del keep
+        out = [None, dx]
+        if not need_w:
+            return tuple(out + [None] * (2 * len(mus)))
         gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        out = [None, None]
         for a, b in zip(gmu, grho):
             out += [a, b]
         return tuple(out)
@@ -533,10 +544,12 @@ class _MCForwardLRT(torch.autograd.Function):
         tape = ctx.tape
         _check_versions(ctx.versions)
         ctx.cfg["spent"] = True
+        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])         # (as in _MCForward)
         grads = [None] * (4 * len(tape))
+        dx = None
         g = g_logits.contiguous()
         # (as in _MCForward: the weight-side work of a layer on a second stream beside its input gradients, eager launches only)
-        side = _side_stream(g.device) if (overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
+        side = _side_stream(g.device) if (need_w and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
         main = torch.cuda.current_stream(g.device) if side is not None else None
         keep = []
         # (as in _MCForward: the flipped input-gradient weights of every layer -- mean and variance sets -- in one launch up front)
@@ -569,7 +582,9 @@ class _MCForwardLRT(torch.autograd.Function):
             else:
                 g_mu, g_var = ops.lrt_pool_act_backward_chwn(g, y, am, av, k, s, act, pad_planes=pad, combine=comb)
             if am.shape[0] == 1 and g_mu.shape[0] > 1:      # first layer: one pair of moments feeds every draw
-                g_mu, g_var = ops.sum_over_draws(g_mu, keepdim=True), ops.sum_over_draws(g_var, keepdim=True)
+                # (the two sums one set apart in one buffer: the input gradient reads them as the two draws of one launch)
+                both = torch.empty((2, 1) + tuple(g_mu.shape[1:]), dtype=torch.float32, device=g_mu.device)
+                g_mu, g_var = ops.sum_over_draws(g_mu, keepdim=True, out=both[0]), ops.sum_over_draws(g_var, keepdim=True, out=both[1])
             def weight_side(g_mu=g_mu, g_var=g_var, x_in=x_in, w_mu=w_mu, rec=rec, li=li, stride=stride, padding=padding, dilation=dilation,
                             g_pair=g_pair):
                 wshape = (1,) + tuple(w_mu.shape)
@@ -601,8 +616,11 @@ class _MCForwardLRT(torch.autograd.Function):
                 side.wait_stream(main)
                 with torch.cuda.stream(side.current):
                     weight_side()
-            else:
+            elif need_w:
                 weight_side()
+            if rec["first"] and need_x:
+                dx = ops.first_layer_input_grad((g_mu, g_var), (w_mu, w_var), (x_in.shape[2], x_in.shape[3]), stride, padding, dilation,
+                                                x_lrt=ctx.x_nchw).view(ctx.x_nchw.shape)
             if not rec["first"]:
                 hw = (x_in.shape[2], x_in.shape[3])
                 w_t = w_flipped.get(li)
@@ -622,13 +640,15 @@ class _MCForwardLRT(torch.autograd.Function):
             for st_ in side.streams:
                 main.wait_stream(st_)
         del keep
-        return (None, None, *grads)
+        return (None, dx, *grads)
 
 
 def bf16_train_refusal(net, x):
     """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return "a 4-d fp32 CUDA batch"
+    if x.requires_grad and torch.is_grad_enabled():
+        return "inputs that do not require a gradient (there are no bf16 input gradients; precision='fp32' has them)"
     from . import ensemble
     if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
         return "no eps replay"

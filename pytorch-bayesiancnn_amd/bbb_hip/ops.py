@@ -1648,8 +1648,8 @@ def conv2d_input_grad(gy, w, x_shape, stride, padding, dilation):
     """d loss / d x of y = conv2d(x, w) on the same fp32-MFMA kernel: a stride-1 convolution of gy -- zero-upsampled by the
     layer's stride -- with the spatially flipped, channel-transposed weights, the layer's dilation and padding
     d*(k-1) - p; rows / columns of x that no output touched get zero.  gy [E,B,Cout,Ho,Wo], w [E|1,Cout,Cin,kh,kw].
-    (Stride s multiplies s*s - 1 inserted zeros: fine for the rare strided layer that is not a model's first layer -- a
-    first layer needs no input gradient at all.)"""
+    (Stride s multiplies s*s - 1 inserted zeros: fine for the rare strided layer that is not a model's first layer -- on the
+    batch-innermost path a first layer's input gradient is first_layer_input_grad, which multiplies no inserted zero.)"""
     (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
     kh, kw = w.shape[3], w.shape[4]
     H, W = x_shape[-2], x_shape[-1]
@@ -1887,18 +1887,23 @@ def plane_sums(g, over_draws=False):
     return out
 
 
-def sum_over_draws(x, keepdim=False):
-    """x [E, ...] -> the sum over the leading (draw) axis, added in draw order (bbb_sum_leading); trailing size % 4 == 0."""
+def sum_over_draws(x, keepdim=False, out=None):
+    """x [E, ...] -> the sum over the leading (draw) axis, added in draw order (bbb_sum_leading); trailing size % 4 == 0.
+    out: a contiguous fp32 tensor of one draw's element count to write into (returned in the result's shape)."""
     require_device(x)
     x = x.contiguous()
     E = x.shape[0]
-    if E == 1:
+    if E == 1 and out is None:
         return x if keepdim else x[0]
     n = x.numel() // E
-    out = torch.empty(((1,) if keepdim else ()) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    shape = ((1,) if keepdim else ()) + tuple(x.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not out.is_contiguous() or out.numel() != n or out.dtype != torch.float32:
+        raise _lib.BBBHipError("sum_over_draws: out must be a contiguous fp32 tensor of one draw's size")
     with on_device(x.device):
         check(_lib.lib().bbb_sum_leading(x.data_ptr(), out.data_ptr(), E, n, cur_stream(x.device)), "bbb_sum_leading")
-    return out
+    return out.view(shape)
 
 
 def square(x, out=None):
@@ -1951,14 +1956,14 @@ def lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, k, s, act, pad_planes=
         raise _lib.BBBHipError("lrt_pool_act_backward_chwn: act_mu / act_var must hold y's planes, or one draw's worth of them")
     K = H * W * B
     pitch = padded_plane_pitch(K) if pad_planes else K
+    # the two outputs one allocation apart in every form: a first layer's input gradient reads them as the two draws of one launch
     if pitch != K:
-        bufs = [torch.empty((planes, pitch), dtype=torch.float32, device=y.device) for _ in range(2)]
+        pair = torch.empty((2, planes, pitch), dtype=torch.float32, device=y.device)
+        bufs = [pair[0], pair[1]]
         outs = [b[:, :K].view(*lead, H, W, B) for b in bufs]
-    elif stacked:
+    else:
         both = torch.empty((2,) + tuple(y.shape), dtype=torch.float32, device=y.device)
         bufs = outs = [both[0], both[1]]
-    else:
-        bufs = outs = [torch.empty_like(y), torch.empty_like(y)]
     with on_device(y.device):
         check(_lib.lib().bbb_lrt_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), act_mu.data_ptr(), act_var.data_ptr(),
                                                    bufs[0].data_ptr(), bufs[1].data_ptr(), planes, mom_planes, H, W, B, int(k), int(s),
@@ -2252,6 +2257,70 @@ def conv2d_chwn_weight_grad_shared_input(g_pre, x_nchw, w_shape, stride, padding
                                              cur_stream(g_pre.device)), "bbb_conv2d_chwn_fwd")
     gw = y.sum(0) if S > 1 else y[0]
     return gw[:, :J].reshape(E, Cout, Cin, kh, kw)
+
+
+def _gemm_rows(gs):
+    """gs: tensors [E, C, Ho, Wo, B] of one shape -> (operand [len(gs), E*C, 1, 1, P], P): their (draw, channel) rows as the input of
+    a 1x1 launch whose draws are the tensors.  Read in place when every row sits at one pitch P >= Ho*Wo*B and the tensors one set
+    apart in one allocation -- a first layer's gradient as pool_act_backward_chwn(pad_planes=True) writes it: the pad columns are
+    contracted too, their results are never read -- else copied once into a dense buffer."""
+    g0 = gs[0]
+    E, C, Ho, Wo, B = g0.shape
+    K, M, P = Ho * Wo * B, E * C, g0.stride(1)
+    st = g0.untyped_storage()
+    ok = (g0.stride(4) == 1 and g0.stride(3) == B and g0.stride(2) == Wo * B and P >= K and P % 4 == 0 and (E == 1 or g0.stride(0) == C * P)
+          and (g0.storage_offset() + len(gs) * M * P) * 4 <= st.nbytes()
+          and all(g.shape == g0.shape and g.stride() == g0.stride() and g.untyped_storage().data_ptr() == st.data_ptr()
+                  and g.data_ptr() - g0.data_ptr() == i * M * P * 4 for i, g in enumerate(gs)))
+    if ok:
+        return g0.as_strided((len(gs), M, 1, 1, P), (M * P, P, P, P, 1)), P
+    out = torch.empty((len(gs), M, 1, 1, K), dtype=torch.float32, device=g0.device)
+    for i, g in enumerate(gs):
+        out[i].view(E, C, Ho, Wo, B).copy_(g)
+    return out, K
+
+
+def first_layer_input_grad(g_pre, w, x_hw, stride, padding, dilation, x_lrt=None):
+    """d loss / d x of a model's FIRST layer, whose input (the caller's batch) every draw shares -- the sum over draws is part of the
+    contraction:
+        dx[b, ci, h, w] = sum_e sum_co sum_(r, q) g_pre[e, co, ho, wo, b] * w[e, co, ci, r, q],  h = ho*sh - ph + r*dh, w = wo*sw - pw + q*dw
+    Two launches: D[j, ho, wo, b] = sum_(e, co) W[(e, co), j] G[(e, co), ho, wo, b], j = (ci, r, q), on the forward kernel as a 1x1
+    "convolution" (g_pre's own memory is its input with E*Cout channels -- as conv2d_chwn_weight_grad_shared_input reads it the other
+    way round --, the sampled weights transposed to [J, E*Cout] its weights; follows gemm_mode like every gradient GEMM), then
+    bbb_input_grad_col2im folds D onto the input pixels in NCHW (no stride upsampling: no product lands on an inserted zero).
+    g_pre [E, Cout, Ho, Wo, B] (the padded-pitch view of pool_act_backward_chwn(pad_planes=True) is read in place), w [E, Cout, Cin,
+    kh, kw], x_hw = (H, W) -> dx [B, Cin, H, W].  A first linear layer behind a flatten: kh = kw = 1, H = W = 1, Cin = in_features.
+    x_lrt = the layer's input x (a local-reparameterisation layer): g_pre = (g_mu, g_var), each [1, Cout, Ho, Wo, B] (summed over
+    draws), w = (W_mu, W_var) [Cout, Cin, kh, kw] -> T(g_mu, W_mu) + 2 x * T(g_var, W_var); the pair runs as the two draws of one GEMM
+    launch (in place when g_var sits one set behind g_mu in one buffer)."""
+    lrt = x_lrt is not None
+    gs = list(g_pre) if lrt else [g_pre]
+    ws = [t.contiguous() for t in (w if lrt else [w])]
+    require_device(*gs, *ws, x_lrt)
+    E, Cout, Ho, Wo, B = gs[0].shape
+    Cin, kh, kw = ws[0].shape[-3:]
+    H, W = int(x_hw[0]), int(x_hw[1])
+    J, M = Cin * kh * kw, E * Cout
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    if ((H + 2 * ph - dh * (kh - 1) - 1) // sh + 1 != Ho or (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1 != Wo
+            or any(t.numel() != M * J for t in ws) or (lrt and (len(gs) != 2 or x_lrt.numel() != B * Cin * H * W))):
+        raise _lib.BBBHipError("first_layer_input_grad: geometry mismatch")
+    xg, P = _gemm_rows(gs)
+    wt = torch.empty((len(gs), J, M, 1, 1), dtype=torch.float32, device=xg.device)
+    with on_device(xg.device):
+        for i, t in enumerate(ws):
+            check(_lib.lib().bbb_transpose2d(t.data_ptr(), wt[i].data_ptr(), M, J, cur_stream(xg.device)), "bbb_transpose2d")
+    dcol = conv2d_chwn_forward(xg, wt, None)                          # [len(gs), J, 1, 1, P]
+    d = ConvDesc()
+    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, 1, kh, kw
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
+    d.draws = 1
+    xc = x_lrt.contiguous() if lrt else None
+    dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=xg.device)
+    with on_device(dx.device):
+        check(_lib.lib().bbb_input_grad_col2im(dcol.data_ptr(), P, J * P, ptr(xc), dx.data_ptr(), ctypes.byref(d), cur_stream(dx.device)),
+              "bbb_input_grad_col2im")
+    return dx
 
 
 # ---- bf16 training backward (fast_train._MCForwardBF16; DESIGN.md section 4.5) ------------------------------------------------
