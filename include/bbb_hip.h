@@ -563,6 +563,24 @@ int bbb_im2col_pbj(const float* x, float* out, const bbb_conv_desc_t* d, void* s
 int bbb_input_grad_col2im(const float* dcol, int64_t row_pitch, int64_t set_stride, const float* x, float* dx,
                           const bbb_conv_desc_t* d, void* stream);
 
+/* Training extension, additive in ABI 13: the input gradient of a STRIDED layer y = conv(x, w) in the batch-innermost layout, as
+ * the transposed ("fractionally strided") form of bbb_conv2d_chwn_fwd's launch (csrc/pconv_dgrad.hip):
+ *   dx[e][ci][ih][iw][b] = sum over co and the taps (r', q') of g_pre[e][co][oh][ow][b] * w_flipped[e][ci][co][r'][q']
+ * where tap r' takes part iff t = ih - pad_h + r' * dil_h satisfies t >= 0, t % up_h == 0 and oh = t / up_h < h (columns alike).
+ * d is the descriptor of the launch a stride-1 layer's gradient takes on bbb_conv2d_chwn_fwd -- batch; cin, h, w = channels and
+ * map of g_pre (the layer's cout, ho, wo); cout = channels of dx (the layer's cin); kh, kw, dil = the layer's; stride 1;
+ * pad = dil * (k - 1) - the layer's padding (>= 0); draws, x_draw_stride (g_pre) and w_draw_stride (0: every draw shares one
+ * weight set) as usual; every other field 0 -- and the layer's stride travels as the upsampling factors (up_h, up_w), the map of
+ * dx as (out_h, out_w): it must be one whose forward gives g_pre's map, (out + 2 p - dil (k - 1) - 1) / up + 1 == h | w, else
+ * BBB_ESHAPE.  g_pre [draws|1][cin][h][w][B], w_flipped [draws|1][cout][cin][kh][kw] (bbb_flip_transpose_w*), dx
+ * [draws][cout][out_h][out_w][B].  No inserted zero and no padding tap is multiplied: the (pixel, tap) pairs visited are the
+ * forward launch's in-bounds pairs.  A pixel no tap reaches (up > dil (k - 1) + 1, rows the forward's floor dropped) is written
+ * as zeros.  One fmaf chain per element in a fixed order (channel-major, then taps ascending), no atomics, no scratch, never
+ * split: a draw's slab does not depend on what shares the launch.  up_h == up_w == 1 is BBB_EINVAL (that gradient is
+ * bbb_conv2d_chwn_fwd on the flipped weights: there is one way to compute it). */
+int bbb_conv2d_chwn_dgrad(const bbb_conv_desc_t* d, const float* g_pre, const float* w_flipped, float* dx, int up_h, int up_w,
+                          int out_h, int out_w, void* stream);
+
 /* Training extension, the small steps between the gradient GEMMs (ABI 8; deterministic, no atomics):
  * bbb_plane_sum: out[r] = sum over o < outer, j < cols of x[o*outer_stride + r*row_pitch + j] -- bias gradients (the gradient w.r.t.
  *   a layer's pre-activation summed over pixels and images per (draw, channel) plane; outer > 1 also sums over draws: LRT biases).

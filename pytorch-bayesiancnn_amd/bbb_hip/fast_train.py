@@ -5,7 +5,8 @@ BBB (weight-space) layers: ONE autograd node for the whole batched forward.  For
 pixel-major GEMMs that skip padding taps with the activation in the epilogue, HIP pooling) recording each layer's input and
 activated output; backward walks the layers in reverse with
   * `bbb_pool_act_bwd_chwn`            pooling + activation backward from the activated output alone,
-  * `ops.conv2d_chwn_input_grad`       dgrad = the forward kernel on flipped, channel-transposed weights,
+  * `ops.conv2d_chwn_input_grad`       dgrad = the forward kernel on flipped, channel-transposed weights (a strided layer: the
+                                       transposed form of that launch, csrc/pconv_dgrad.hip),
   * `ops.conv2d_chwn_weight_grad`      wgrad = the forward kernel with batch <-> channel roles swapped (padding taps skipped),
   * `ops.conv2d_chwn_weight_grad_shared_input`  the first layer (3-channel images): draws stacked into the GEMM rows over an
                                        im2col of the shared input, K split over the launch's draws,
@@ -33,9 +34,11 @@ def _layers():
 def train_path_ok(net, x):
     """The fast autograd path covers: a 4-d CUDA fp32 batch with B % 4 == 0; a flat model (ensemble.flat_children) of Bayesian
     conv / linear layers of ONE kind (all BBB or all BBB_LRT) sharing one prior, each optionally followed by ReLU /
-    Softplus(1, 20) and then MaxPool2d (no padding, floor), and a FlattenLayer that keeps one row per image; stride-1
-    convolutions and channel counts that are multiples of 4 everywhere except the first layer; the model ends in a Bayesian
-    linear layer; no eps replay.  Returns "bbb", "lrt" or None."""
+    Softplus(1, 20) and then MaxPool2d (no padding, floor), and a FlattenLayer that keeps one row per image; convolutions of any
+    positive stride in any layer (a strided layer behind the first takes its input gradient on the transposed launch,
+    ops.conv2d_chwn_input_grad(stride=)), padding within the kernel reach (p <= d (k - 1)) and channel counts that are multiples
+    of 4 everywhere except the first layer; the model ends in a Bayesian linear layer; no eps replay.  Returns "bbb", "lrt" or
+    None."""
     from . import ensemble
     if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4 or x.dtype != torch.float32 or x.shape[0] % 4 != 0:
         return None
@@ -75,7 +78,7 @@ def _train_path_static(net, x):
                 return None
             pri.add((m.prior_mu, m.prior_sigma))
             if isinstance(m, (BBBConv2d, LRTConv2d)):
-                if not first and ops._pair(m.stride) != (1, 1):
+                if min(ops._pair(m.stride)) < 1:
                     return None
                 (ph, pw), (dh, dw) = ops._pair(m.padding), ops._pair(m.dilation)
                 if dh * (m.kernel_size[0] - 1) < ph or dw * (m.kernel_size[1] - 1) < pw:
@@ -245,7 +248,8 @@ class _MCForward(torch.autograd.Function):
                     main.wait_stream(xk_stream)
                 weight_side()
             if not rec["first"]:
-                g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li))
+                g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li),
+                                               stride=stride)
             else:
                 if need_x:
                     dx = ops.first_layer_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), stride, padding, dilation).view(x_shape)
@@ -628,12 +632,12 @@ class _MCForwardLRT(torch.autograd.Function):
                     if w_t is None:
                         w_t = ops.flip_transpose_w_pair(w_mu.unsqueeze(0), w_var.unsqueeze(0))
                     gx = ops.conv2d_chwn_input_grad(g_pair.reshape((2,) + tuple(g_mu.shape[1:])), w_mu.unsqueeze(0), hw, padding, dilation,
-                                                    w_flipped=w_t)
+                                                    w_flipped=w_t, stride=stride)
                     g1, g2 = gx[0:1], gx[1:2]
                 else:
                     t_mu, t_var = (w_t[0:1], w_t[1:2]) if w_t is not None else (None, None)
-                    g1 = ops.conv2d_chwn_input_grad(g_mu, w_mu.unsqueeze(0), hw, padding, dilation, w_flipped=t_mu)
-                    g2 = ops.conv2d_chwn_input_grad(g_var, w_var.unsqueeze(0), hw, padding, dilation, w_flipped=t_var)
+                    g1 = ops.conv2d_chwn_input_grad(g_mu, w_mu.unsqueeze(0), hw, padding, dilation, w_flipped=t_mu, stride=stride)
+                    g2 = ops.conv2d_chwn_input_grad(g_var, w_var.unsqueeze(0), hw, padding, dilation, w_flipped=t_var, stride=stride)
                 # (g1 + 2 x g2 is formed by the layer below's pooling / activation pass)
                 g = (g1, x_in, g2) if fold_lrt_combine[0] else ops.lrt_input_grad_combine(g1, x_in, g2)
         if side is not None:
@@ -641,6 +645,12 @@ class _MCForwardLRT(torch.autograd.Function):
                 main.wait_stream(st_)
         del keep
         return (None, dx, *grads)
+
+
+def _strided_later_conv(net):
+    """A convolution behind the first Bayesian layer has a stride other than 1."""
+    from . import ensemble
+    return any(hasattr(m, "stride") and ops._pair(m.stride) != (1, 1) for m in ensemble.bayesian_layers(net)[1:])
 
 
 def bf16_train_refusal(net, x):
@@ -657,6 +667,9 @@ def bf16_train_refusal(net, x):
         return "BBB (weight-space) layers; local-reparameterisation layers have no bf16 mode"
     if kind is None:
         return "a model and input on the batch-innermost training path (fast_train.train_path_ok)"
+    if _strided_later_conv(net):
+        return ("stride-1 convolutions after the first layer (the strided input gradient has an fp32 kernel only; "
+                "precision='fp32' trains such a model)")
     if x.shape[0] % 8 != 0:
         return "a batch size that is a multiple of 8"
     return None

@@ -8,6 +8,7 @@ anywhere.  Activations, pooling and the loss tail use torch autograd (element-wi
 """
 import contextlib
 import ctypes
+import math
 import os
 import itertools
 import sys
@@ -302,12 +303,15 @@ class LaunchConfig:
                 (bf16 has fp32's exponent range: no operand windows or scales).  Opt-in: results agree with the fp32 kernel
                 to rounding, not bit for bit.  LRT layers keep the fused fp32 kernel (one staged x tile feeds both of its
                 contractions; a split form would need twelve operand planes in LDS).
+                The input gradient of a STRIDED layer (conv2d_chwn_input_grad(stride != 1)) runs on the fp32 transposed
+                launch in either mode; it is held to the same bounds.
     bf16x3_min_workgroups   smaller launches stay on the fp32 kernel (and the layer's split contraction): measured faster there
     s3_min_images   split-bf16 mode: steps of at least this many (draw x image) rows keep their activations in the split format S3
                 between layers (ensemble._mc_logits_chwn); smaller steps split while staging, per launch
     split_k     layers with few (pixel, channel-tile) groups and a long contraction (AlexNet conv4 / conv5) add their k ranges'
                 partial sums in range order (bbb_conv2d_chwn_splitk_fwd): a property of the LAYER, identical for every launch
                 size and partition.  False: the plain fmaf chain everywhere (bit-identical to the reference-layout kernel).
+                (The strided input gradient is never split: one chain per element whatever this says.)
     pool_fusion a conv layer followed by [activation ->] MaxPool2d(2, 2) may run as ONE launch (bbb_conv_desc_t::pool)
     pool_fuse_min_items / pool_fuse_imbalance   a launch with nothing else in flight: only when it still has this many (pooled pixel,
                 64-channel tile, 128-image tile, draw) items and they spread over the 256 CUs to within this factor (4x longer items)
@@ -2032,19 +2036,56 @@ def flip_transpose_w_multi(sets):
     return outs
 
 
-def conv2d_chwn_input_grad(g_pre, w, x_hw, padding, dilation, w_flipped=None):
-    """d loss / d x of a STRIDE-1 y = conv(x, w) in the batch-innermost layout, on the forward kernel itself: the convolution
-    of g_pre [E, Cout, Ho, Wo, B] with the spatially flipped, channel-transposed weights, padding d*(k-1) - p.
-    w [E, Cout, Cin, kh, kw] -> [E, Cin, H, W, B].  w_flipped: flip_transpose_w(w) computed ahead (off the gradient chain)."""
-    (ph, pw), (dh, dw) = _pair(padding), _pair(dilation)
+def dgrad_tap_plan(ih, ho, k, s, p, d):
+    """Host restatement of the transposed launch's per-axis tap enumeration (csrc/pconv_body.cuh, tr_axis): the flipped-weight taps
+    r' that take part in input row `ih` of a layer with `ho` output rows, kernel k, stride s, padding p, dilation d, and the output
+    row each reads -> [(r', oh)].  t = ih - (d (k - 1) - p) + r' d must be >= 0, divisible by s and t / s < ho; those taps are an
+    arithmetic progression with step s / gcd(s, d) whose first member is among the first `step` taps."""
+    base, step = ih - (d * (k - 1) - p), s // math.gcd(s, d)
+    first = next((r for r in range(min(step, k)) if (base + r * d) % s == 0), None)
+    if first is None:
+        return []
+    t0, sd = base + first * d, step * d
+    r0 = first + ((-t0 + sd - 1) // sd if t0 < 0 else 0) * step
+    lim = (ho - 1) * s - base
+    if lim < 0:
+        return []
+    r1 = min(lim // d, k - 1)
+    return [(r, (base + r * d) // s) for r in range(r0, r1 + 1, step)]
+
+
+def conv2d_chwn_input_grad(g_pre, w, x_hw, padding, dilation, w_flipped=None, stride=1):
+    """d loss / d x of y = conv(x, w) in the batch-innermost layout.  g_pre [E, Cout, Ho, Wo, B], w [E|1, Cout, Cin, kh, kw] ->
+    [E, Cin, H, W, B] for x_hw = (H, W).  w_flipped: flip_transpose_w(w) computed ahead (off the gradient chain).
+    stride 1 (the default): the forward kernel itself -- the convolution of g_pre with the spatially flipped, channel-transposed
+    weights, padding d*(k-1) - p.
+    Any other stride: the transposed form of that launch (bbb_conv2d_chwn_dgrad, csrc/pconv_dgrad.hip), which visits exactly the
+    forward's in-bounds (pixel, tap) pairs -- no zero-upsampled gradient, no product with an inserted zero; input pixels that no
+    tap reaches come back as zeros.  Always the fp32 kernel and never a split contraction (LaunchConfig: gemm_mode, split_k)."""
+    (ph, pw), (dh, dw), (sh, sw) = _pair(padding), _pair(dilation), _pair(stride)
     kh, kw = w.shape[3], w.shape[4]
     qh, qw = dh * (kh - 1) - ph, dw * (kw - 1) - pw
     if qh < 0 or qw < 0:
         raise _lib.BBBHipError("conv2d_chwn_input_grad: padding larger than the kernel reach")
     w_t = w_flipped if w_flipped is not None else flip_transpose_w(w)
-    gx = conv2d_chwn_forward(g_pre, w_t, None, 1, (qh, qw), (dh, dw))
-    if gx.shape[2] != x_hw[0] or gx.shape[3] != x_hw[1]:
-        raise _lib.BBBHipError("conv2d_chwn_input_grad: geometry mismatch (stride-1 layers only)")
+    if (sh, sw) == (1, 1):
+        gx = conv2d_chwn_forward(g_pre, w_t, None, 1, (qh, qw), (dh, dw))
+        if gx.shape[2] != x_hw[0] or gx.shape[3] != x_hw[1]:
+            raise _lib.BBBHipError("conv2d_chwn_input_grad: geometry mismatch (x_hw is not this stride-1 layer's input map)")
+        return gx
+    if sh < 1 or sw < 1:
+        raise _lib.BBBHipError("conv2d_chwn_input_grad: strides are positive")
+    require_device(g_pre, w_t)
+    g_pre, w_t = g_pre.contiguous(), w_t.contiguous()
+    E = max(g_pre.shape[0], w_t.shape[0])
+    if g_pre.dim() != 5 or w_t.dim() != 5 or g_pre.shape[0] not in (1, E) or w_t.shape[0] not in (1, E):
+        raise _lib.BBBHipError("leading (draw) dims of g_pre and w must be 1 or equal")
+    H, W = int(x_hw[0]), int(x_hw[1])
+    d, _, _ = _desc_chwn(g_pre, w_t, 1, (qh, qw), (dh, dw), E, g_pre.shape[0] == 1 and E > 1, w_t.shape[0] == 1 and E > 1, None)
+    gx = torch.empty((E, w_t.shape[1], H, W, g_pre.shape[4]), dtype=torch.float32, device=g_pre.device)
+    with on_device(g_pre.device):
+        check(_lib.lib().bbb_conv2d_chwn_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
+                                               cur_stream(g_pre.device)), "bbb_conv2d_chwn_dgrad")
     return gx
 
 

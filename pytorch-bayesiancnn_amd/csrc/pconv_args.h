@@ -31,4 +31,5 @@ struct PConvArgs {
     int32_t y_f32;       // pconv_bf16_fewout_kernel: y is fp32 (the logits layer) instead of bf16
     int32_t vh0, vh1, vw0, vw1;   // pconv_c8x3: input rows [vh0, vh1) x columns [vw0, vw1) may hold non-zero data (the rest is declared zero)
     int32_t y_c8;        // pconv_bf16.hip: y is written channel-interleaved, [cout / 8][ho][wo][B][8] (BBB_BF16_OUT_C8)
+    int32_t up_h, up_w, tstep_h, tstep_w;   // pconv_body.cuh, TR (the strided input gradient): the layer's stride and the step between taps that take part
 };

@@ -41,6 +41,14 @@ constexpr int TPC = KCH / BK;            // tiles per chunk
 // multiplied that the unfused launch does not multiply), and the result is bit for bit pool(act(conv + bias)) of the separate
 // launches (max is exact).  Items are four times fewer and four times longer: for launches that still fill the chip evenly.
 constexpr int kPlain = 0, kSplit = 1, kSeq = 2, kPool = 3;
+// TR: the TRANSPOSED ("fractionally strided") item -- the input gradient of a strided layer (pconv_dgrad.hip).  x is the output
+// gradient g [Cin = the layer's cout][H = ho][W = wo][B], w the flipped, channel-transposed weights, the item's pixel (oh, ow) a
+// pixel of dx [Ho x Wo = the layer's input map], p.ph / p.pw the stride-1 padding d (k - 1) - p and p.up_h / p.up_w the layer's
+// stride.  Tap r reads g row t / up_h, t = oh - ph + r * dh, iff t >= 0, t % up_h == 0 and t / up_h < H: per axis the taps that
+// take part are an arithmetic progression with step p.tstep = up / gcd(up, d) whose first member is among the first `step`
+// taps, so the in-bounds taps stay a rectangle nr x nq -- only set_pixel's ranges and fill_chunk's table entries differ (both
+// behind `if constexpr`: the other instantiations compile to what they were); a pixel that no tap reaches has Keff = 0 and
+// stores the zero accumulator.
 
 // SEQ keeps its running totals in ACCUMULATION registers through inline asm: they are touched three times per item, and left to
 // the register allocator they became 28-55 extra VGPRs (one resident workgroup less per CU: +5-8 % per launch, measured);
@@ -51,12 +59,13 @@ __device__ __forceinline__ float agpr_read(float a) {
     return v;
 }
 __device__ __forceinline__ void agpr_write(float& a, float v) { asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v)); }
-template <int BM, bool LRT, bool ILV, int MODE = kPlain>
+template <int BM, bool LRT, bool ILV, int MODE = kPlain, bool TR = false>
 __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t item, const int ks = 0) {
     constexpr bool SPLIT = MODE == kSplit;
     constexpr bool SEQ = MODE == kSeq;
     constexpr bool POOL = MODE == kPool;
     static_assert(!POOL || !LRT || BM == 64, "the pooled LRT form: 64-image tiles (one accumulator pair per wave)");
+    static_assert(!TR || (MODE == kPlain && !LRT), "the transposed item: plain BBB form only");
     constexpr int LDX = BM + 4;
     constexpr int NT = (BM >= 128) ? 2 : 1;              // 32-channel MFMA tiles per wave
     constexpr int MT = (BM == 256) ? 2 : 1;              // 32-image MFMA tiles per wave
@@ -110,10 +119,39 @@ __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t ite
     int ihb, iwb, r_lo, q_lo, nq, nrq, Keff, ntiles;
     float inv_nrq, inv_nq;
     const float inv_cin = 1.0f / (float)p.Cin;
+    // TR, one axis: taps r = lo + i * step, i < cnt, are those with t = base + r * d >= 0, t % up == 0 and t / up < n
+    auto tr_axis = [](int base, int d, int up, int step, int k, int n, int& lo, int& cnt) {
+        lo = 0; cnt = 0;
+        int first = -1;
+        for (int r = 0; r < step && r < k; ++r)
+            if ((base + r * d) % up == 0) { first = r; break; }
+        if (first < 0) return;
+        const int t0 = base + first * d, sd = step * d;                  // (sd is a multiple of up: members stay divisible)
+        const int r0 = first + (t0 < 0 ? (-t0 + sd - 1) / sd : 0) * step;
+        const int lim = (n - 1) * up - base;                              // r * d <= lim  <=>  t / up <= n - 1
+        if (lim < 0) return;
+        int r1 = lim / d;
+        r1 = r1 < k - 1 ? r1 : k - 1;
+        if (r1 < r0) return;
+        lo = r0; cnt = (r1 - r0) / step + 1;
+    };
     auto set_pixel = [&](int oh, int ow) {
         if constexpr (POOL) {            // re-set inside a loop: keep the pixel's state in scalar registers
             oh = __builtin_amdgcn_readfirstlane(oh);
             ow = __builtin_amdgcn_readfirstlane(ow);
+        }
+        if constexpr (TR) {
+            ihb = oh - p.ph;
+            iwb = ow - p.pw;
+            int nr;
+            tr_axis(ihb, p.dh, p.up_h, p.tstep_h, p.kh, p.H, r_lo, nr);
+            tr_axis(iwb, p.dw, p.up_w, p.tstep_w, p.kw, p.W, q_lo, nq);
+            nrq = nr * nq;
+            Keff = p.Cin * nrq;
+            ntiles = (Keff + BK - 1) / BK;
+            inv_nrq = nrq > 0 ? 1.0f / (float)nrq : 0.0f;
+            inv_nq = nq > 0 ? 1.0f / (float)nq : 0.0f;
+            return;
         }
         ihb = oh * p.sh - p.ph;
         iwb = ow * p.sw - p.pw;
@@ -185,9 +223,15 @@ __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t ite
             int rr = (int)((float)rq * inv_nq);
             int qq = rq - rr * nq;
             if (qq < 0) { --rr; qq += nq; } else if (qq >= nq) { ++rr; qq -= nq; }
-            const int r = r_lo + rr, q = q_lo + qq;
-            wo = (p.wtap ? (uint32_t)((r * p.kw + q) * p.Cin + ci) : (uint32_t)(ci * p.khkw + r * p.kw + q)) * 4u;   // byte offset in a row
-            xo = (uint32_t)((ci * p.H + ihb + r * p.dh) * p.W + iwb + q * p.dw) * (uint32_t)p.B * 4u;   // row byte offset
+            if constexpr (TR) {
+                const int r = r_lo + rr * p.tstep_h, q = q_lo + qq * p.tstep_w;
+                wo = (uint32_t)(ci * p.khkw + r * p.kw + q) * 4u;
+                xo = (uint32_t)((ci * p.H + (ihb + r * p.dh) / p.up_h) * p.W + (iwb + q * p.dw) / p.up_w) * (uint32_t)p.B * 4u;
+            } else {
+                const int r = r_lo + rr, q = q_lo + qq;
+                wo = (p.wtap ? (uint32_t)((r * p.kw + q) * p.Cin + ci) : (uint32_t)(ci * p.khkw + r * p.kw + q)) * 4u;   // byte offset in a row
+                xo = (uint32_t)((ci * p.H + ihb + r * p.dh) * p.W + iwb + q * p.dw) * (uint32_t)p.B * 4u;   // row byte offset
+            }
         }
         kt_w[chunk & 1][tid] = (int32_t)wo;
         kt_x[chunk & 1][tid] = (int32_t)xo;
