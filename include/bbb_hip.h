@@ -444,6 +444,51 @@ int bbb_nchw_to_chwn_bf16(const float* x, void* y, int batch, int64_t plane, voi
 int bbb_nchw_to_chwn_bf16_slices(const float* x, void* y, int batch, int64_t plane, int slices, void* stream);
 
 /*
+ * The local-reparameterisation layer on bf16 storage (additive to ABI 13; layers/BBB_LRT/BBBConv.py:71-81, BBBLinear.py:65-73):
+ *   act_mu  = sum x * bf16(W_mu) + b_mu
+ *   act_var = 1e-16 + sum bf16(x^2) * bf16(sigma^2) + sigma_b^2
+ *   y       = act(act_mu + sqrt(act_var) * eps)        (sample != 0)   |   act(act_mu)   (sample == 0)
+ * x is the STORED bf16 value; x^2 is its exact fp32 square rounded once to bf16 (nearest even), formed inside the kernel; both
+ * contractions run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation from one staged x tile; biases, the sampling step and the
+ * activation are fp32; y is rounded once when stored as bf16.  eps is the element bbb_lrt_conv2d_chwn_fwd draws: canonical index
+ * ((b + d->b_offset) * cout + c) * ho * wo + pixel of stream (seed, call0 + slab, stream_id).
+ *   x:           [draws|1][cin][h][w][B] bf16 (B % 8 == 0, 16-byte aligned); d->x_unit_div / x_unit_off as in bbb_conv2d_chwn_fwd
+ *   w_mu, w_var: [cout][Kp] bf16 rows as bbb_lrt_weights_bf16 writes them (Kp = cin*kh*kw rounded up to 8, zero pad; column order
+ *                (ci, r, q), or (r, q, ci) with BBB_BF16_W_TAP_MAJOR, cin % 8 == 0), SHARED by every slab of the launch:
+ *                d->w_draw_stride == d->b_draw_stride == 0.  b_mu / b_var: fp32 [cout], both or neither.
+ *   y:           [draws][cout][ho][wo][B] bf16, or fp32 with BBB_BF16_OUT_F32 (the logits layer).  May be NULL when sample == 0 and
+ *                the moment outputs are given (a moments-only launch).
+ *   act_mu_out / act_var_out: optional fp32 [draws][cout][ho][wo][B] copies of the two moments (both or neither).
+ * No work units, no pooled form (BBB_EINVAL).  Every sum has a fixed order that depends on the layer's geometry only, so a slab
+ * computed alone or inside a larger launch is the same bits.
+ * bbb_lrt_conv2d_chwn_bf16_plan reports what the launcher picks for a descriptor: *shape = 22 (128 channels x 128 images per
+ * workgroup), 14 (64 x 256) or 12 (64 x 128), *k_groups = 1 | 2, *wave_specialised = 0 | 1.  Host only (tests, profiling).
+ */
+int bbb_lrt_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void* x, const void* w_mu, const void* w_var, const float* b_mu,
+                                 const float* b_var, void* y, float* act_mu_out, float* act_var_out, uint64_t seed, uint32_t call0,
+                                 uint32_t stream_id, int sample, const uint32_t* call_dev, uint32_t flags, void* stream);
+int bbb_lrt_conv2d_chwn_bf16_plan(const bbb_conv_desc_t* d, uint32_t flags, int32_t* shape, int32_t* k_groups,
+                                  int32_t* wave_specialised);
+/* bbb_lrt_sample_chwn with bf16 output: y[e] = bf16(act(act_mu + sqrt(act_var) * eps[e])), [draws][channels][pixels][batch], from one
+ * pair of fp32 moments (a moments-only bbb_lrt_conv2d_chwn_bf16_fwd launch); bit for bit what `draws` sampling launches of that
+ * entry point store.  batch % 8 == 0. */
+int bbb_lrt_sample_chwn_bf16(const float* act_mu, const float* act_var, void* y, int draws, int channels, int pixels, int batch,
+                             int b_offset, int act, uint64_t seed, uint32_t call0, uint32_t stream_id, const uint32_t* call_dev,
+                             void* stream);
+/* fp32 matrices [rows][row_len] -> bf16 [rows][Kp] in the bf16 GEMMs' row layout (Kp = row_len rounded up to 8, zero pad), up to
+ * BBB_BF16_ROWS_MAX_SEGMENTS of them in ONE launch: the W_mu and sigma^2 operands of every LRT layer of a model.  taps > 0: the
+ * source row is [cin][taps] and the output row tap-major, column t * cin + ci (cin = row_len / taps, cin % 8 == 0); 0: as it is. */
+#define BBB_BF16_ROWS_MAX_SEGMENTS 32
+typedef struct bbb_bf16_rows_segment {
+    const float* src;
+    void* dst;            /* 16-byte aligned */
+    int64_t rows;
+    int32_t row_len;
+    int32_t taps;
+} bbb_bf16_rows_segment_t;
+int bbb_lrt_weights_bf16(const bbb_bf16_rows_segment_t* segs, int nseg, void* stream);
+
+/*
  * Monte-Carlo tail (main_bayesian.py:49,53 / :78,80 + utils.py:14-22): per draw log_softmax over
  * classes, then log-sum-exp over the local draws.
  *   logits [draws][B][C]  ->  lse [B][C] = log sum_e exp(log_softmax(logits[e])[b][c])

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("BBB_HIP_LIB") or os.path.join(_HERE, "libbbb_hip.so")
 
 ABI_VERSION = 13
 MAX_SEGMENTS = 16
+BF16_ROWS_MAX_SEGMENTS = 32
 SIGMA_SQUARED = 1
 KL_TEXTBOOK = 2
 GW_MEAN_ONLY = 4
@@ -35,6 +36,10 @@ class AdamSegment(ctypes.Structure):
 class FlipSeg(ctypes.Structure):
     _fields_ = [("w0", c_void_p), ("w1", c_void_p), ("out", c_void_p), ("draws", c_i64), ("cout", c_i32), ("cin", c_i32),
                 ("khkw", c_i32), ("reserved", c_i32)]
+
+
+class RowsSegment(ctypes.Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("rows", c_i64), ("row_len", c_i32), ("taps", c_i32)]
 
 
 class ConvDesc(ctypes.Structure):
@@ -84,6 +89,13 @@ _SIGNATURES = {
     "bbb_maxpool_chwn_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bbb_nchw_to_chwn_bf16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p]),
     "bbb_nchw_to_chwn_bf16_slices": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p]),
+    "bbb_lrt_conv2d_chwn_bf16_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_u64, c_u32, c_u32, c_int, c_void_p, c_u32, c_void_p]),
+    "bbb_lrt_conv2d_chwn_bf16_plan": (c_int, [ctypes.POINTER(ConvDesc), c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                              ctypes.POINTER(c_i32)]),
+    "bbb_lrt_sample_chwn_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_u64, c_u32, c_u32,
+                                         c_void_p, c_void_p]),
+    "bbb_lrt_weights_bf16": (c_int, [ctypes.POINTER(RowsSegment), c_int, c_void_p]),
     "bbb_mc_tail": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bbb_mc_tail_cb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bbb_mc_tail_cb_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

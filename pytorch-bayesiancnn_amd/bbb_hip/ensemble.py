@@ -346,11 +346,25 @@ def _chwn_mods_ok(mods):
     return True
 
 
-def _check_precision(precision, net, x, fast_path_allowed):
+_BF16_LRT_HINT = ("LRT models run in bf16 only under LaunchConfig.bf16_lrt (ops.use_config(bf16_lrt=True) or launch_config= on the "
+                  "graphed classes): all-LRT models on mc_logits / mc_forward / GraphedMC / GraphedPipeline")
+
+
+def _has_lrt(net):
+    return any(isinstance(l, _LRTLayer) for l in bayesian_layers(net))
+
+
+def _refuse_bf16_lrt_sharded(net, precision, sharded):
+    """bf16 on LRT models (LaunchConfig.bf16_lrt) has no sharded form: a process group raises instead of computing something else."""
+    if precision == "bf16" and sharded and _has_lrt(net):
+        raise _lib.BBBHipError("bf16 on LRT models runs on one device: no group= sharding, work units or shares of a group of steps")
+
+
+def _check_precision(precision, net, x, fast_path_allowed, dropin=False):
     """precision: "fp32" (the reference's arithmetic, default); "bf16x3" (fp32 tensors and fp32 accuracy, the BBB GEMM launches of
     the batch-innermost path on the 16-bit matrix pipe -- range-free split bf16, ops.gemm_mode -- everything else as fp32); or
     "bf16" (bf16 storage of sampled weights and activations, fp32 accumulate; inference on the batch-innermost path only --
-    anything else fails loudly)."""
+    anything else fails loudly).  dropin: the check of the drop-in `net(x)` loop, which covers BBB models only."""
     if precision in ("fp32", "bf16x3"):
         return
     if precision != "bf16":
@@ -358,6 +372,8 @@ def _check_precision(precision, net, x, fast_path_allowed):
     if not fast_path_allowed or not _chwn_ok(net, x, any_batch=False):
         raise _lib.BBBHipError("bf16 runs on the batch-innermost inference path only (no autograd, no external eps, "
                                "4-d input with B % 8 == 0, BBB layers + ReLU/Softplus/MaxPool2d/FlattenLayer)")
+    if dropin and _has_lrt(net):
+        raise _lib.BBBHipError("the drop-in loop in bf16 covers BBB (non-LRT) models; " + _BF16_LRT_HINT)
 
 
 def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precision="fp32", units=None, b_offset=0, groups=1,
@@ -421,8 +437,14 @@ def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precisio
         streams = 1
     else:
         S, n_draws = 1, E
-    if bf16 and (lrt or B % 8 != 0):
-        raise _lib.BBBHipError("the bf16 path covers BBB (non-LRT) layers and batch sizes that are multiples of 8")
+    bf16_lrt = bf16 and bool(lrt)
+    if bf16 and (B % 8 != 0 or (lrt and not ops.current_config().bf16_lrt)):
+        raise _lib.BBBHipError("the bf16 path covers BBB (non-LRT) layers and batch sizes that are multiples of 8; " + _BF16_LRT_HINT)
+    if bf16_lrt:
+        if bbb:
+            raise _lib.BBBHipError("bf16: a model mixes BBB and LRT layers (all one kind or the other)")
+        if ukw or share is not None or b_offset:
+            raise _lib.BBBHipError("bf16 on LRT models: no work units, shares of a group of steps or batch offsets")
     # split-bf16 mode: BBB layers with Cin % 32 == 0 (never the first one: its input is the caller's fp32 batch) run on the
     # MFMA-ready-operand kernel (ops.conv2d_c8x3_forward) -- their input travels channel-interleaved and already split ("c8 S3"),
     # their weights come tap-major from the parameter pass.  Which kernel a layer takes is a property of the LAYER (not of the
@@ -467,6 +489,13 @@ def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precisio
     if lrt:
         variances, k2 = _variances_all(lrt, timers)
         kl = k2 if kl is None else kl + k2
+    lrt_b16 = {}                                                  # LRT layer -> bf16 (W_mu, sigma^2) rows: one conversion launch per step
+    if bf16_lrt:
+        srcs = []
+        for l in lrt:
+            srcs += [l.W_mu, variances[l][0]]
+        rows = _run(timers, "layout", None, lambda: ops.lrt_weights_bf16(srcs))
+        lrt_b16 = {l: (rows[2 * k], rows[2 * k + 1]) for k, l in enumerate(lrt)}
     to_cb = ops.to_batch_innermost_bf16 if bf16 else ops.to_batch_innermost
     nblk = (S if S > 1 else nb) if (S > 1 or G > 1 or share is not None) else 1
     xs2d = w_s2d = None
@@ -671,6 +700,36 @@ def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precisio
                     s3 = o_s3
                     if fuse_pool:
                         i += 1                                   # the pooling module is done too
+                elif bf16:
+                    # an LRT layer on bf16 storage (LaunchConfig.bf16_lrt): both contractions in one launch of the dual-accumulator
+                    # bf16 GEMM, weights shared by every slab, the fp32 path's noise elements
+                    wm_b, wv_b = lrt_b16[mod]
+                    b_var = variances[mod][1]
+                    ckk = (mod.in_channels, *mod.kernel_size) if is_conv else (mod.in_features, 1, 1)
+                    tapm = is_conv and ops.bf16_tap_major(tuple(mod.W_mu.shape))
+                    of32 = i == last_bayes and tail_is_last
+                    dst = logits_buf[e0:e1] if (logits_buf is not None and i == last_bayes and not is_conv) else None
+                    shared_in = h5.shape[0] == 1 and Es > 1 and G == 1 and not of32
+                    fl = conv_flops(B, h5.shape[1], h5.shape[2], h5.shape[3], wm_b.shape[0], ckk[1], ckk[2],
+                                    *geom, 1 if shared_in else Es, 2) if timers is not None else None
+                    if shared_in:
+                        # same input AND same weights for every draw: the two contractions run once (moments only), the E draws
+                        # differ only in the noise -- bitwise the same result as E full launches
+                        _, am, av = _run(timers, "lrt_gemm", fl,
+                                         lambda h5=h5, wm_b=wm_b, wv_b=wv_b, b_var=b_var, mod=mod, geom=geom, ckk=ckk, tapm=tapm:
+                                         ops.lrt_conv2d_chwn_bf16_forward(h5, wm_b, wv_b, mod.bias_mu if mod.use_bias else None, b_var, ckk,
+                                                                          seed, call0 + e0, mod._stream_base + 2, *geom, sample=False,
+                                                                          moments_only=True, tap_major=tapm))
+                        y = _run(timers, "lrt_sample", None,
+                                 lambda am=am, av=av, mod=mod, act=act:
+                                 ops.lrt_sample_chwn_bf16(am, av, Es, seed, call0 + e0, mod._stream_base + 2, act=act))
+                    else:
+                        y = _run(timers, "lrt_gemm", fl,
+                                 lambda h5=h5, wm_b=wm_b, wv_b=wv_b, b_var=b_var, mod=mod, geom=geom, ckk=ckk, tapm=tapm, act=act, ukw2=ukw2,
+                                 of32=of32, dst=dst:
+                                 ops.lrt_conv2d_chwn_bf16_forward(h5, wm_b, wv_b, mod.bias_mu if mod.use_bias else None, b_var, ckk, seed,
+                                                                  call0 + e0, mod._stream_base + 2, *geom, sample=True, act=act,
+                                                                  out_f32=of32, out=dst, tap_major=tapm, n_slabs=Es, **ukw2)[0])
                 else:
                     w_var, b_var = variances[mod]
                     w_mu = mod.W_mu
@@ -784,7 +843,7 @@ def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precisio
         out = logits_buf if (logits_buf is not None and all(pt.data_ptr() == logits_buf[b0:b1].data_ptr()
                                                             for pt, (b0, b1) in zip(parts, bounds))) \
             else torch.cat(parts, dim=0)
-    stats["path"] = "chwn"
+    stats["path"] = "chwn-bf16-lrt" if bf16_lrt else "chwn"
     if rows_real is not None:
         out = out[:, :, :rows_real]                              # (a view: the consumers' .contiguous() compacts it)
     return out, kl                                               # logits stay batch-innermost: [E, C, B]
@@ -1097,6 +1156,7 @@ def mc_forward(net, x, num_ens, group=None, fuse_act=True, timers=None, kl_mode=
     rank = 0 if group is None else torch.distributed.get_rank(group)
     rng.assign_stream_ids(net)                       # stream ids by module order: identical on every rank
     seed, call0 = rng.next_calls(num_ens)            # all ranks advance identically
+    _refuse_bf16_lrt_sharded(net, precision, world > 1)
     S, lo, hi = shard_plan(net, x, num_ens, rank, world, fuse_act, precision)
     if hi > lo:
         if S > 1:
@@ -1150,6 +1210,7 @@ def mc_forward_batch_parallel(net, x_local, num_ens, group=None, gather=False, f
     world = 1 if group is None else torch.distributed.get_world_size(group)
     rank = 0 if group is None else torch.distributed.get_rank(group)
     rng.assign_stream_ids(net)
+    _refuse_bf16_lrt_sharded(net, precision, world > 1)
     if b_offset is None:
         b_offset = rank * x_local.shape[0]
     if not any(isinstance(l, _LRTLayer) for l in bayesian_layers(net)):
@@ -1444,6 +1505,7 @@ class GraphedMC:
         import os as _os
         self._force_combine = group is not None and _os.environ.get("BBB_FORCE_COMBINE") == "1"   # test hook: N > 1 code path at world 1
         self.multi = self.world > 1 or self._force_combine
+        _refuse_bf16_lrt_sharded(net, precision, self.multi)
         if self.steps > 1 and self.multi:
             # a group of steps over several ranks: contiguous ranges of the group's steps * num_ens draws (group_share)
             self.S = 1

@@ -326,11 +326,17 @@ class LaunchConfig:
                 path of ensemble.mc_forward(precision="bf16") (sampled weights and activations in bf16, fp32 accumulation, fp32 logits)
                 behind the unmodified `for j in range(num_ens): net(x)` loop -- inference only, BBB models the batch-innermost path
                 covers; anything else (autograd enabled, LRT layers, hooks, a layer called on its own) raises instead of silently
-                computing in fp32"""
+                computing in fp32
+    bf16_lrt    False | True: precision="bf16" admits models whose Bayesian layers are ALL local-reparameterisation layers, on
+                lrt_conv2d_chwn_bf16_forward (csrc/pconv_bf16_lrt.hip: both contractions of a layer on the 16-bit matrix pipe from one
+                staged bf16 x tile; W_mu and sigma^2 rounded once per step by lrt_weights_bf16, x^2 rounded once to bf16 in the kernel;
+                fp32 accumulation, biases, sampling step, KL and tail; the fp32 path's noise elements).  Inference on
+                ensemble.mc_logits / mc_forward / GraphedMC / GraphedPipeline, B % 8 == 0.  Opt-in: under the default, bf16 on an LRT
+                model raises, as it always did"""
     FIELDS = ("gemm_mode", "bf16x3_min_workgroups", "s3_min_images", "split_k", "pool_fusion", "pool_fuse_min_items",
               "pool_fuse_imbalance", "launches_overlap", "pool_fuse_min_items_overlapped", "pool_fuse_weight_budget",
               "bf16_pool_fuse_min_rows", "bf16_pool_fuse_min_rows_overlapped", "bf16_c8", "bf16_c8_min_items", "c8x3", "c8x3_s2d",
-              "dropin_precision")
+              "dropin_precision", "bf16_lrt")
     __slots__ = FIELDS
 
     def __init__(self, **kw):
@@ -351,6 +357,7 @@ class LaunchConfig:
         self.bf16_c8_min_items = 0                     # layer that has the strip form over them, for launches of at least this many strip
                                                        # workgroups (0: always -- measured faster from one step per launch on); False: never
         self.dropin_precision = "fp32"
+        self.bf16_lrt = False                          # precision="bf16" on all-LRT models (lrt_conv2d_chwn_bf16_forward); opt-in
         self.c8x3 = True                               # split-bf16 mode: layers (behind the first) with Cin % 32 == 0 run on the
                                                        # MFMA-ready-operand kernel (conv2d_c8x3_forward: channel-interleaved split
                                                        # activations + tap-major weights from the parameter pass); False: round 4's
@@ -1198,6 +1205,126 @@ def conv2d_chwn_bf16_forward(x, w, bias, cin_khkw, stride=1, padding=0, dilation
                                                   (1 if out_f32 else 0) | (2 if tap_major else 0) | (4 if x_c8 else 0) |
                                                   (8 if out_c8 else 0), cur_stream(x.device)),
               "bbb_conv2d_chwn_bf16_fwd")
+    return y
+
+
+def lrt_weights_bf16(weights):
+    """The W_mu / sigma^2 operands of lrt_conv2d_chwn_bf16_forward: fp32 [Cout, Cin, kh, kw] or [Cout, K] tensors -> bf16
+    [Cout, Kp] rows (Kp = bf16_row_pitch(K), zero pad; tap-major column order where bf16_tap_major says so -- the layout
+    sample_weights_bf16 writes for BBB layers), one rounding each.  Every tensor of the list in one launch per
+    _lib.BF16_ROWS_MAX_SEGMENTS of them (both operands of every layer of a model: one launch per step)."""
+    require_device(*weights)
+    weights = [w.detach().contiguous() for w in weights]
+    if not weights:
+        return []
+    dev = weights[0].device
+    outs = []
+    for w in weights:
+        if w.dim() not in (2, 4):
+            raise _lib.BBBHipError("lrt_weights_bf16: [Cout, Cin, kh, kw] or [Cout, K] tensors")
+        outs.append(torch.empty((w.shape[0], bf16_row_pitch(w.numel() // w.shape[0])), dtype=torch.bfloat16, device=dev))
+    n = _lib.BF16_ROWS_MAX_SEGMENTS
+    with on_device(dev):
+        for s0 in range(0, len(weights), n):
+            ws, os_ = weights[s0:s0 + n], outs[s0:s0 + n]
+            segs = (_lib.RowsSegment * len(ws))()
+            for sg, w, o in zip(segs, ws, os_):
+                sg.src, sg.dst, sg.rows, sg.row_len = w.data_ptr(), o.data_ptr(), w.shape[0], w.numel() // w.shape[0]
+                sg.taps = w.shape[2] * w.shape[3] if bf16_tap_major(tuple(w.shape)) else 0
+            check(_lib.lib().bbb_lrt_weights_bf16(segs, len(ws), cur_stream(dev)), "bbb_lrt_weights_bf16")
+    return outs
+
+
+def _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, x_shared, act):
+    Ex, Cin, H, W, B = x_shape
+    cin, kh, kw = cin_khkw
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    d = ConvDesc()
+    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, cout, kh, kw
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
+    d.draws = E
+    d.x_draw_stride = 0 if x_shared else Cin * H * W * B
+    d.act = {None: 0, "relu": 1, "softplus": 2}[act]
+    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    return d, ho, wo
+
+
+def lrt_bf16_plan(x_shape, cout, cin_khkw, stride=1, padding=0, dilation=1, draws=None):
+    """(tile shape 22 | 14 | 12, k-groups, wave-specialised) the library picks for lrt_conv2d_chwn_bf16_forward on this geometry
+    (bbb_lrt_conv2d_chwn_bf16_plan; host only: needs no device)."""
+    E = int(draws) if draws is not None else x_shape[0]
+    d, _, _ = _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, False, None)
+    sh, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.lib().bbb_lrt_conv2d_chwn_bf16_plan(ctypes.byref(d), 0, ctypes.byref(sh), ctypes.byref(kg), ctypes.byref(ws)),
+          "bbb_lrt_conv2d_chwn_bf16_plan")
+    return sh.value, kg.value, bool(ws.value)
+
+
+def lrt_conv2d_chwn_bf16_forward(x, w_mu, w_var, b_mu, b_var, cin_khkw, seed, call0, stream_id, stride=1, padding=0, dilation=1,
+                                 sample=True, want_moments=False, moments_only=False, act=None, out_f32=False, out=None,
+                                 tap_major=False, b_offset=0, x_div=1, x_off=0, n_slabs=None):
+    """LRT layer on bf16 storage, batch-innermost.  x: [E|1, Cin, H, W, B] bf16 (B % 8 == 0); w_mu / w_var: bf16 [Cout, Kp] rows
+    from lrt_weights_bf16 (tap_major = their column order), shared by every slab; b_mu / b_var fp32 [Cout] or None ->
+    (y, act_mu | None, act_var | None): y [E, Cout, Ho, Wo, B] bf16 (fp32 when out_f32) = act(act_mu + sqrt(act_var) * eps) with
+    act_mu = sum x bf16(W_mu) + b_mu, act_var = 1e-16 + sum bf16(x^2) bf16(sigma^2) + b_var and eps the fp32 LRT kernel's element
+    (call0 + slab, stream_id, canonical index keyed by b_offset + image); the moments fp32.  moments_only: no y (sample=False).
+    x_div / x_off / n_slabs: several steps per launch, as in lrt_conv2d_chwn_forward."""
+    require_device(x, w_mu, w_var, dtype=torch.bfloat16)
+    require_device(b_mu, b_var)
+    x, w_mu, w_var = x.contiguous(), w_mu.contiguous(), w_var.contiguous()
+    b_mu = None if b_mu is None else b_mu.contiguous()
+    b_var = None if b_var is None else b_var.contiguous()
+    cin, kh, kw = cin_khkw
+    grouped = int(x_div) > 1
+    E = int(n_slabs) if n_slabs is not None else x.shape[0] * int(x_div)
+    if grouped and (not 0 <= int(x_off) < int(x_div) or x.shape[0] != -(-(E + int(x_off)) // int(x_div))):
+        raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E output slabs")
+    if not grouped and x.shape[0] not in (1, E):
+        raise _lib.BBBHipError("the leading (draw) dim of x must be 1 or the number of slabs")
+    if x.shape[1] != cin or w_mu.shape != w_var.shape or w_mu.dim() != 2 or w_mu.shape[1] != bf16_row_pitch(cin * kh * kw):
+        raise _lib.BBBHipError("weight pitch / channel count do not match the geometry")
+    if moments_only and sample:
+        raise _lib.BBBHipError("moments_only: sample=False")
+    cout, B = w_mu.shape[0], x.shape[4]
+    d, ho, wo = _lrt_bf16_desc(x.shape, cout, cin_khkw, stride, padding, dilation, E, x.shape[0] == 1 and E > 1 and not grouped, act)
+    if grouped:
+        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
+    d.b_offset = int(b_offset)
+    shape = (E, cout, ho, wo, B)
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if moments_only:
+        y = None
+    elif out is None:
+        y = torch.empty(shape, dtype=dt, device=x.device)
+    else:
+        if out.numel() != E * cout * ho * wo * B or not out.is_contiguous() or out.dtype != dt:
+            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
+        y = out.view(shape)
+    moments = want_moments or moments_only
+    am = torch.empty(shape, dtype=torch.float32, device=x.device) if moments else None
+    av = torch.empty(shape, dtype=torch.float32, device=x.device) if moments else None
+    with on_device(x.device):
+        check(_lib.lib().bbb_lrt_conv2d_chwn_bf16_fwd(ctypes.byref(d), x.data_ptr(), w_mu.data_ptr(), w_var.data_ptr(), ptr(b_mu),
+                                                      ptr(b_var), ptr(y), ptr(am), ptr(av), seed, call0 & 0xFFFFFFFF, stream_id,
+                                                      1 if sample else 0, rng.call_dev_ptr(x.device),
+                                                      (1 if out_f32 else 0) | (2 if tap_major else 0), cur_stream(x.device)),
+              "bbb_lrt_conv2d_chwn_bf16_fwd")
+    return y, am, av
+
+
+def lrt_sample_chwn_bf16(act_mu, act_var, draws, seed, call0, stream_id, act=None, b_offset=0):
+    """lrt_sample_chwn with bf16 output: E draws from one pair of fp32 moments [1|-, C, Ho, Wo, B] (B % 8 == 0) -> bf16
+    [E, C, Ho, Wo, B]; bit for bit what E sampling launches of lrt_conv2d_chwn_bf16_forward store."""
+    require_device(act_mu, act_var)
+    act_mu, act_var = act_mu.contiguous(), act_var.contiguous()
+    C, Ho, Wo, B = act_mu.shape[-4:]
+    y = torch.empty((draws, C, Ho, Wo, B), dtype=torch.bfloat16, device=act_mu.device)
+    with on_device(act_mu.device):
+        check(_lib.lib().bbb_lrt_sample_chwn_bf16(act_mu.data_ptr(), act_var.data_ptr(), y.data_ptr(), draws, C, Ho * Wo, B,
+                                                  int(b_offset), {None: 0, "relu": 1, "softplus": 2}[act], seed, call0 & 0xFFFFFFFF,
+                                                  stream_id, rng.call_dev_ptr(act_mu.device), cur_stream(act_mu.device)),
+              "bbb_lrt_sample_chwn_bf16")
     return y
 
 

@@ -29,6 +29,7 @@
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
 #include "pconv_args.h"
+#include "smem_attr.h"
 
 namespace {
 
@@ -1363,23 +1364,7 @@ __global__ __launch_bounds__(256) void pconv_bf16_fewout_kernel(const PConvArgs 
     }
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: `state` (one array per kernel instantiation)
-// remembers the bytes granted on each device, so that a process driving several GPUs -- or several threads (relaxed atomics: a
-// duplicated call is harmless) -- sets it wherever a launch needs it.
-constexpr int kMaxDevices = 64;
-struct SmemAttrState { std::atomic<int> bytes[kMaxDevices]; };
-inline int ensure_dynamic_smem(const void* fn, int bytes, SmemAttrState& state) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) {
-        return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);       // (unknown device: every time)
-    }
-    if (state.bytes[dev].load(std::memory_order_relaxed) >= bytes) return 0;
-    const hipError_t er = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (er != hipSuccess) return (int)er;
-    state.bytes[dev].store(bytes, std::memory_order_relaxed);
-    return 0;
-}
-
+// (per-device dynamic-LDS attribute of a kernel: ensure_dynamic_smem, smem_attr.h)
 template <int NP>
 int launch_fewout(const PConvArgs& a, int64_t blocks, hipStream_t st) {
     constexpr int kSmem = 64 * NP * 32 * 4;

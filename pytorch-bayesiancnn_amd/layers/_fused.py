@@ -294,7 +294,7 @@ def fast_forward(wrapper, x):
     if prec != "fp32":
         if grad:
             return None                               # (ModuleWrapper.forward raises: bf16 is inference only)
-        ensemble._check_precision(prec, wrapper, x, True)     # raises unless the bf16 inference path covers this model and input
+        ensemble._check_precision(prec, wrapper, x, True, dropin=True)     # raises unless the bf16 inference path covers this model and input
     if grad:
         # training / the reference's validate loop (which does not disable autograd): the same kernels behind ONE autograd node
         from bbb_hip import fast_train
