@@ -665,6 +665,23 @@ int bbb_flip_transpose_w_bf16(const void* w, void* out, int64_t draws, int cout,
 int bbb_chwn_to_bhwc_bf16(const void* x, void* out, int64_t draws, int c, int64_t hw, int batch, int c_pad, void* stream);
 int bbb_batch_chunks_bf16(const void* x, void* out, int64_t outer, int64_t rows, int batch, int chunks, void* stream);
 
+/* bf16 training backward, additive in ABI 13: the input gradient of a STRIDED layer on bf16 storage -- bbb_conv2d_chwn_dgrad's
+ * transposed launch on the general bf16 GEMM (csrc/pconv_bf16.hip, pconv_bf16_kernel TR).  The argument contract is
+ * bbb_conv2d_chwn_dgrad's: d describes the stride-1 launch on the flipped rows (batch; cin, h, w = channels and map of g_pre;
+ * cout = channels of dx; kh, kw, dil = the layer's; stride 1; pad = dil * (k - 1) - the layer's padding; draws, x_draw_stride,
+ * w_draw_stride; every other field 0), (up_h, up_w) = the layer's stride ((1, 1) is BBB_EINVAL: that gradient is
+ * bbb_conv2d_chwn_bf16_fwd on the flipped rows), (out_h, out_w) = the map of dx, which must be one whose forward gives g_pre's map
+ * (else BBB_ESHAPE).  Operands as bbb_conv2d_chwn_bf16_fwd's: g_pre [draws|1][cin][h][w][B] bf16, B % 8 == 0; w_flipped
+ * [draws|1][cout][Kp] bf16 rows as bbb_flip_transpose_w_bf16 writes them, Kp = cin*kh*kw rounded up to 8, in (ci, r, q) order or,
+ * with flags = BBB_BF16_W_TAP_MAJOR (cin % 8 == 0), (r, q, ci) order (no other flag is accepted); dx [draws][cout][out_h][out_w][B]
+ * bf16; all three 16-byte aligned, draw strides multiples of 8 elements (else BBB_EALIGN); the forward's 32-bit offset limits and
+ * cin*kh*kw < 2^24 (else BBB_ESHAPE).  fp32 accumulation in a fixed order, one rounding to nearest-even, no bias / activation /
+ * pooling, no atomics, no scratch.  Tap-major rows: only the taps that take part are contracted (no inserted zero, no padding
+ * tap).  Reference-order rows: the full row is contracted with the other taps' image rows read as zero (about up_h * up_w times
+ * the useful matrix work).  A pixel no tap reaches is written as +0.  Every check happens before any launch. */
+int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* g_pre, const void* w_flipped, void* dx, int up_h, int up_w,
+                               int out_h, int out_w, uint32_t flags, void* stream);
+
 /* Library / device introspection (host-only). */
 int bbb_abi_version(void);
 const char* bbb_build_info(void);

@@ -133,6 +133,8 @@ _SIGNATURES = {
                                            c_void_p]),
     "bbb_plane_sum_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_void_p]),
     "bbb_flip_transpose_w_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_u32, c_void_p]),
+    "bbb_conv2d_chwn_bf16_dgrad": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_u32,
+                                           c_void_p]),
     "bbb_chwn_to_bhwc_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
     "bbb_batch_chunks_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
     "bbb_abi_version": (c_int, []),

@@ -275,7 +275,8 @@ class _MCForwardBF16(torch.autograd.Function):
     each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the same walk as _MCForward._backward with
       * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
       * ops.plane_sums_bf16               bias gradients, the fp32 sum of that bf16 g_pre,
-      * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16,
+      * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16 (a strided layer, admitted
+        under LaunchConfig.bf16_strided_train: the transposed launch on the same rows),
       * ops.conv2d_chwn_weight_grad_bf16  wgrad on the bf16 GEMM with the roles swapped -> fp32,
       * the first layer (3-channel input shared by every draw): ops.conv2d_chwn_weight_grad_shared_input on the fp32 kernel over
         the fp32 values of the bf16 operands (a bf16 x bf16 product is exact in fp32: the same contraction),
@@ -411,7 +412,7 @@ class _MCForwardBF16(torch.autograd.Function):
                 weight_side()
             if not rec["first"]:
                 g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
-                                                    w_flipped=w_flipped.get(li))
+                                                    w_flipped=w_flipped.get(li), stride=stride)
             else:
                 g = None
         if side is not None:
@@ -654,7 +655,9 @@ def _strided_later_conv(net):
 
 
 def bf16_train_refusal(net, x):
-    """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0."""
+    """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0 --
+    with stride-1 convolutions behind the first layer, or any stride there under LaunchConfig.bf16_strided_train (read from the
+    configuration that is current: the caller's use_config, or what GraphedTrainStep snapshotted)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return "a 4-d fp32 CUDA batch"
     if x.requires_grad and torch.is_grad_enabled():
@@ -667,9 +670,10 @@ def bf16_train_refusal(net, x):
         return "BBB (weight-space) layers; local-reparameterisation layers have no bf16 mode"
     if kind is None:
         return "a model and input on the batch-innermost training path (fast_train.train_path_ok)"
-    if _strided_later_conv(net):
+    if _strided_later_conv(net) and not ops.current_config().bf16_strided_train:
         return ("stride-1 convolutions after the first layer (the strided input gradient has an fp32 kernel only; "
-                "precision='fp32' trains such a model)")
+                "precision='fp32' trains such a model) unless LaunchConfig.bf16_strided_train is set "
+                "(ops.use_config(bf16_strided_train=True) or launch_config= on GraphedTrainStep: the transposed bf16 launch, opt-in)")
     if x.shape[0] % 8 != 0:
         return "a batch size that is a multiple of 8"
     return None

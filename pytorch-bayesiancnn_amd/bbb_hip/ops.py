@@ -332,11 +332,15 @@ class LaunchConfig:
                 staged bf16 x tile; W_mu and sigma^2 rounded once per step by lrt_weights_bf16, x^2 rounded once to bf16 in the kernel;
                 fp32 accumulation, biases, sampling step, KL and tail; the fp32 path's noise elements).  Inference on
                 ensemble.mc_logits / mc_forward / GraphedMC / GraphedPipeline, B % 8 == 0.  Opt-in: under the default, bf16 on an LRT
-                model raises, as it always did"""
+                model raises, as it always did
+    bf16_strided_train   False | True: train_step / forward_loss / GraphedTrainStep(precision="bf16") admit BBB models with STRIDED
+                convolutions behind the first layer: their input gradient runs on the transposed form of the general bf16 GEMM
+                (conv2d_chwn_input_grad_bf16(stride=...), bbb_conv2d_chwn_bf16_dgrad; bf16 in, fp32 accumulation, one rounding).
+                Opt-in: under the default such a model is refused, as it always was (precision="fp32" trains it)"""
     FIELDS = ("gemm_mode", "bf16x3_min_workgroups", "s3_min_images", "split_k", "pool_fusion", "pool_fuse_min_items",
               "pool_fuse_imbalance", "launches_overlap", "pool_fuse_min_items_overlapped", "pool_fuse_weight_budget",
               "bf16_pool_fuse_min_rows", "bf16_pool_fuse_min_rows_overlapped", "bf16_c8", "bf16_c8_min_items", "c8x3", "c8x3_s2d",
-              "dropin_precision", "bf16_lrt")
+              "dropin_precision", "bf16_lrt", "bf16_strided_train")
     __slots__ = FIELDS
 
     def __init__(self, **kw):
@@ -358,6 +362,7 @@ class LaunchConfig:
                                                        # workgroups (0: always -- measured faster from one step per launch on); False: never
         self.dropin_precision = "fp32"
         self.bf16_lrt = False                          # precision="bf16" on all-LRT models (lrt_conv2d_chwn_bf16_forward); opt-in
+        self.bf16_strided_train = False                # bf16 training of models with strided later layers (bbb_conv2d_chwn_bf16_dgrad); opt-in
         self.c8x3 = True                               # split-bf16 mode: layers (behind the first) with Cin % 32 == 0 run on the
                                                        # MFMA-ready-operand kernel (conv2d_c8x3_forward: channel-interleaved split
                                                        # activations + tap-major weights from the parameter pass); False: round 4's
@@ -2164,7 +2169,7 @@ def flip_transpose_w_multi(sets):
 
 
 def dgrad_tap_plan(ih, ho, k, s, p, d):
-    """Host restatement of the transposed launch's per-axis tap enumeration (csrc/pconv_body.cuh, tr_axis): the flipped-weight taps
+    """Host restatement of the transposed launch's per-axis tap enumeration (csrc/pconv_args.h, tr_axis): the flipped-weight taps
     r' that take part in input row `ih` of a layer with `ho` output rows, kernel k, stride s, padding p, dilation d, and the output
     row each reads -> [(r', oh)].  t = ih - (d (k - 1) - p) + r' d must be >= 0, divisible by s and t / s < ho; those taps are an
     arithmetic progression with step s / gcd(s, d) whose first member is among the first `step` taps."""
@@ -2559,19 +2564,74 @@ def flip_transpose_w_bf16(w, w_shape):
     return out
 
 
-def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_flipped=None):
-    """conv2d_chwn_input_grad on bf16 storage: g_pre [E, Cout, Ho, Wo, B] bf16, w [E, Cout, Kp] sampled bf16 rows of a stride-1
-    layer with weights w_shape = (Cout, Cin, kh, kw) -> bf16 [E, Cin, H, W, B] (conv2d_chwn_bf16_forward on the flipped rows,
-    padding d*(k-1) - p; fp32 accumulation, one rounding).  w_flipped: flip_transpose_w_bf16(w, w_shape) computed ahead."""
+def bf16_dgrad_form(B, cin, cout, kh, kw, x_hw, stride, dilation, draws):
+    """(tile shape 22 | 14 | 12, k-groups 1 | 2, wave-specialised, tap-major rows) bbb_conv2d_chwn_bf16_dgrad picks for the input
+    gradient of a strided layer with weights (cout, cin, kh, kw), input map x_hw = (H, W), `draws` draws of B images -- the host
+    restatement of its selection (csrc/pconv_bf16.hip): the general path's rules of bbb_conv2d_chwn_bf16_fwd on dx's cin channels
+    and H x W pixels, with the k-tile count of the LONGEST contraction a pixel can have (tap-major rows: cout * ceil(kh / tstep_h) *
+    ceil(kw / tstep_w), tstep = s / gcd(s, d); reference-order rows: the full row), and without the forward's four-k-group form
+    for tiny launches (its transposed instantiation would spill registers)."""
+    (sh, sw), (dh, dw) = _pair(stride), _pair(dilation)
+    H, W = int(x_hw[0]), int(x_hw[1])
+    tap_major = bf16_tap_major((cin, cout, kh, kw))
+    waste = lambda n, t: -(-n // t) * t / n
+    c22 = 256.0 * waste(cin, 128) * waste(B, 128)
+    c14 = 288.0 * waste(cin, 64) * waste(B, 256)
+    c12 = 320.0 * waste(cin, 64) * waste(B, 128)
+    shape = 22 if (c22 <= c14 and c22 <= c12) else (14 if c14 <= c12 else 12)
+    th, tw = sh // math.gcd(sh, dh), sw // math.gcd(sw, dw)
+    kmax = cout * -(-kh // th) * -(-kw // tw) if tap_major else cout * kh * kw
+    t64 = -(-kmax // 64)
+    bn, bm = (128 if shape == 22 else 64), (256 if shape == 14 else 128)
+    items = draws * H * W * -(-cin // bn) * -(-B // bm)
+    kgs = 2 if (items < 512 and t64 >= 8) else 1
+    ws = shape == 22 and items <= 1024
+    if ws:
+        kgs = 1
+    return shape, kgs, ws, tap_major
+
+
+def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_flipped=None, stride=1):
+    """conv2d_chwn_input_grad on bf16 storage: g_pre [E, Cout, Ho, Wo, B] bf16, w [E, Cout, Kp] sampled bf16 rows of a layer with
+    weights w_shape = (Cout, Cin, kh, kw) -> bf16 [E, Cin, H, W, B] for x_hw = (H, W); fp32 accumulation, one rounding.
+    w_flipped: flip_transpose_w_bf16(w, w_shape) computed ahead.
+    stride 1 (the default): conv2d_chwn_bf16_forward on the flipped rows, padding d*(k-1) - p.
+    Any other stride: the transposed form of the general bf16 GEMM (bbb_conv2d_chwn_bf16_dgrad, csrc/pconv_bf16.hip) on the same
+    flipped rows -- with tap-major rows (Cout % 8 == 0) exactly the forward's in-bounds (pixel, tap) pairs, with reference-order rows
+    the full row against image rows read as zero; input pixels no tap reaches come back as +0 (bf16_dgrad_form: the launch form)."""
     Cout, Cin, kh, kw = w_shape
-    (ph, pw), (dh, dw) = _pair(padding), _pair(dilation)
+    (ph, pw), (dh, dw), (sh, sw) = _pair(padding), _pair(dilation), _pair(stride)
     qh, qw = dh * (kh - 1) - ph, dw * (kw - 1) - pw
     if qh < 0 or qw < 0:
         raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: padding larger than the kernel reach")
     w_t = w_flipped if w_flipped is not None else flip_transpose_w_bf16(w, w_shape)
-    gx = conv2d_chwn_bf16_forward(g_pre, w_t, None, (Cout, kh, kw), 1, (qh, qw), (dh, dw), tap_major=bf16_tap_major((Cin, Cout, kh, kw)))
-    if gx.shape[2] != x_hw[0] or gx.shape[3] != x_hw[1]:
-        raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: geometry mismatch (stride-1 layers only)")
+    tap_major = bf16_tap_major((Cin, Cout, kh, kw))
+    if (sh, sw) == (1, 1):
+        gx = conv2d_chwn_bf16_forward(g_pre, w_t, None, (Cout, kh, kw), 1, (qh, qw), (dh, dw), tap_major=tap_major)
+        if gx.shape[2] != x_hw[0] or gx.shape[3] != x_hw[1]:
+            raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: geometry mismatch (x_hw is not this stride-1 layer's input map)")
+        return gx
+    if sh < 1 or sw < 1:
+        raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: strides are positive")
+    require_device(g_pre, w_t, dtype=torch.bfloat16)
+    g_pre, w_t = g_pre.contiguous(), w_t.contiguous()
+    E = max(g_pre.shape[0], w_t.shape[0])
+    if g_pre.dim() != 5 or w_t.dim() != 3 or g_pre.shape[0] not in (1, E) or w_t.shape[0] not in (1, E):
+        raise _lib.BBBHipError("leading (draw) dims of g_pre and w must be 1 or equal")
+    if g_pre.shape[1] != Cout or w_t.shape[1] != Cin or w_t.shape[2] != bf16_row_pitch(Cout * kh * kw):
+        raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: rows do not match the weight shape")
+    H, W, B = int(x_hw[0]), int(x_hw[1]), g_pre.shape[4]
+    d = ConvDesc()
+    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cout, g_pre.shape[2], g_pre.shape[3], Cin, kh, kw
+    d.stride_h = d.stride_w = 1
+    d.pad_h, d.pad_w, d.dil_h, d.dil_w = qh, qw, dh, dw
+    d.draws = E
+    d.x_draw_stride = 0 if (g_pre.shape[0] == 1 and E > 1) else Cout * g_pre.shape[2] * g_pre.shape[3] * B
+    d.w_draw_stride = 0 if (w_t.shape[0] == 1 and E > 1) else w_t.shape[1] * w_t.shape[2]
+    gx = torch.empty((E, Cin, H, W, B), dtype=torch.bfloat16, device=g_pre.device)
+    with on_device(g_pre.device):
+        check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
+                                                    2 if tap_major else 0, cur_stream(g_pre.device)), "bbb_conv2d_chwn_bf16_dgrad")
     return gx
 
 

@@ -1,4 +1,5 @@
-// Kernel-argument block shared by the pixel-major GEMM variants (pconv_gemm.hip, pconv_bf16.hip).
+// Kernel-argument block shared by the pixel-major GEMM variants (pconv_gemm.hip, pconv_bf16.hip), and the tap enumeration of their
+// transposed forms (tr_axis).
 #pragma once
 #include <stdint.h>
 
@@ -33,3 +34,22 @@ struct PConvArgs {
     int32_t y_c8;        // pconv_bf16.hip: y is written channel-interleaved, [cout / 8][ho][wo][B][8] (BBB_BF16_OUT_C8)
     int32_t up_h, up_w, tstep_h, tstep_w;   // pconv_body.cuh, TR (the strided input gradient): the layer's stride and the step between taps that take part
 };
+
+// TR, one axis of the transposed ("fractionally strided") item (pconv_body.cuh, pconv_bf16.hip): the taps r = lo + i * step, i < cnt,
+// are those with t = base + r * d >= 0, t % up == 0 and t / up < n -- an arithmetic progression with step = up / gcd(up, d) whose
+// first member is among the first `step` taps (bbb_hip/ops.py: dgrad_tap_plan restates it on the host)
+__device__ __forceinline__ void tr_axis(int base, int d, int up, int step, int k, int n, int& lo, int& cnt) {
+    lo = 0; cnt = 0;
+    int first = -1;
+    for (int r = 0; r < step && r < k; ++r)
+        if ((base + r * d) % up == 0) { first = r; break; }
+    if (first < 0) return;
+    const int t0 = base + first * d, sd = step * d;                  // (sd is a multiple of up: members stay divisible)
+    const int r0 = first + (t0 < 0 ? (-t0 + sd - 1) / sd : 0) * step;
+    const int lim = (n - 1) * up - base;                              // r * d <= lim  <=>  t / up <= n - 1
+    if (lim < 0) return;
+    int r1 = lim / d;
+    r1 = r1 < k - 1 ? r1 : k - 1;
+    if (r1 < r0) return;
+    lo = r0; cnt = (r1 - r0) / step + 1;
+}

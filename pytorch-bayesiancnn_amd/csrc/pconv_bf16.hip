@@ -57,9 +57,23 @@ __device__ __forceinline__ uint16_t f2bf(float v) {              // round to nea
 // table lookups, buffer loads and ds_writes, one tile ahead into the other of TWO LDS stages with the tile after that in
 // flight in their registers; one barrier per tile.  (s_memtime of the unspecialised kernel: 800 cycles issuing loads +
 // 520 in ds_writes + 290 in barriers per iteration against 512 of MFMA, all serial inside the workgroup.)
-template <bool OUT_F32, int WN, int WM, int KG, bool WS>
+//
+// TR: the TRANSPOSED ("fractionally strided") workgroup -- the input gradient of a strided layer on bf16 storage
+// (bbb_conv2d_chwn_bf16_dgrad; the semantics are the comment at the top of pconv_dgrad.hip).  x is the
+// output gradient g [Cin = the layer's cout][H = ho][W = wo][B], w the flipped, channel-transposed rows of
+// bbb_flip_transpose_w_bf16, the workgroup's pixel (oh, ow) a pixel of dx [Ho x Wo = the layer's input map], p.ph / p.pw the
+// stride-1 padding d (k - 1) - p, p.up_h / p.up_w the layer's stride.  Tap r reads g row t / up_h, t = oh - ph + r * dh, iff
+// t >= 0, t % up_h == 0 and t / up_h < H (columns alike): per axis an arithmetic progression with step p.tstep = up / gcd(up, d),
+// so with TAP-MAJOR rows the taps that take part are still a rectangle nr x nq and K = Cin * nr * nq (no product with an inserted
+// zero, no padding tap); with reference-order rows k runs over the full row and a tap that does not take part gets the
+// out-of-range image offset (about up_h * up_w times the useful matrix work).  Only the tap ranges and fill_chunk's table differ
+// (both behind `if constexpr`: the forward's instantiations compile to what they were).  A pixel no tap reaches has K = 0 and
+// niter = 0: every wave still passes the same barriers (the prologue's two, none in the k loop, the reduction's and the
+// epilogue's), the prologue's loads all carry out-of-range offsets, and the zero accumulator is stored as +0.
+template <bool OUT_F32, int WN, int WM, int KG, bool WS, bool TR = false>
 __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16_kernel(const PConvArgs p) {
     static_assert(!WS || KG == 1, "wave specialisation replaces the k-groups");
+    static_assert(!TR || !OUT_F32, "the transposed form writes bf16");
     constexpr int GT = 64 * WN * WM;                              // MFMA threads per k-group
     constexpr int LT = WS ? 256 : GT;                             // threads that stage one tile
     constexpr int NSTG = WS ? 2 : 1;                              // LDS stages per k-group
@@ -97,7 +111,12 @@ __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16
     const int Kp = p.Kp;
     // in-bounds tap rectangle of this pixel (tap-major rows only; otherwise every tap is enumerated)
     int r_lo = 0, q_lo = 0, nr = p.kh, nq = p.kw;
-    if (p.wtap) {
+    if constexpr (TR) {
+        if (p.wtap) {                                             // the stepped rectangle of the taps that take part (pconv_args.h)
+            tr_axis(ihb, p.dh, p.up_h, p.tstep_h, p.kh, p.H, r_lo, nr);
+            tr_axis(iwb, p.dw, p.up_w, p.tstep_w, p.kw, p.W, q_lo, nq);
+        }
+    } else if (p.wtap) {
         r_lo = ihb < 0 ? (-ihb + p.dh - 1) / p.dh : 0;
         q_lo = iwb < 0 ? (-iwb + p.dw - 1) / p.dw : 0;
         int r_hi = (p.H - 1 - ihb) >= 0 ? (p.H - 1 - ihb) / p.dh + 1 : 0;
@@ -147,9 +166,15 @@ __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16
                     int rr = (int)((float)t * inv_nq);
                     int qq = t - rr * nq;
                     if (qq < 0) { --rr; qq += nq; } else if (qq >= nq) { ++rr; qq -= nq; }
-                    const int r = r_lo + rr, q = q_lo + qq;
-                    wo = (uint32_t)((r * p.kw + q) * p.Cin + ci) * 2u;
-                    xo = (uint32_t)((ci * p.H + ihb + r * p.dh) * p.W + iwb + q * p.dw) * (uint32_t)p.B * 2u;
+                    if constexpr (TR) {
+                        const int r = r_lo + rr * p.tstep_h, q = q_lo + qq * p.tstep_w;
+                        wo = (uint32_t)((r * p.kw + q) * p.Cin + ci) * 2u;
+                        xo = (uint32_t)((ci * p.H + (ihb + r * p.dh) / p.up_h) * p.W + (iwb + q * p.dw) / p.up_w) * (uint32_t)p.B * 2u;
+                    } else {
+                        const int r = r_lo + rr, q = q_lo + qq;
+                        wo = (uint32_t)((r * p.kw + q) * p.Cin + ci) * 2u;
+                        xo = (uint32_t)((ci * p.H + ihb + r * p.dh) * p.W + iwb + q * p.dw) * (uint32_t)p.B * 2u;
+                    }
                 }
             } else {
                 if (k < Kp) wo = (uint32_t)k * 2u;                 // the zero pad columns K..Kp-1 are part of the row
@@ -161,8 +186,14 @@ __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16
                     int q = rq - r * p.kw;
                     if (q < 0) { --r; q += p.kw; } else if (q >= p.kw) { ++r; q -= p.kw; }
                     const int ih = ihb + r * p.dh, iw = iwb + q * p.dw;
-                    if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W)
-                        xo = (uint32_t)((ci * p.H + ih) * p.W + iw) * (uint32_t)p.B * 2u;
+                    if constexpr (TR) {
+                        // (ih, iw) are positions on the zero-upsampled g map: only multiples of the stride hold a g pixel
+                        if (ih >= 0 && iw >= 0 && ih % p.up_h == 0 && iw % p.up_w == 0 && ih / p.up_h < p.H && iw / p.up_w < p.W)
+                            xo = (uint32_t)((ci * p.H + ih / p.up_h) * p.W + iw / p.up_w) * (uint32_t)p.B * 2u;
+                    } else {
+                        if (ih >= 0 && ih < p.H && iw >= 0 && iw < p.W)
+                            xo = (uint32_t)((ci * p.H + ih) * p.W + iw) * (uint32_t)p.B * 2u;
+                    }
                 }
             }
             kt_all[(chunk & 1) * KCHG + i] = (int32_t)xo;
@@ -1444,6 +1475,37 @@ int launch_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks
     return kgs == 2 ? launch_cfg<OUT_F32, 1, 2, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 1, 2, 1, false>(a, blocks, st);
 }
 
+// the transposed form: every (shape, k-groups, wave-specialised) combination its selection can produce.  The forward's "tiny" rule
+// (64 x 128 with FOUR k-groups) is left out: that instantiation of the transposed body needs more than the 256 registers a wave
+// of a 512-thread workgroup may hold (5 spilled, 24 bytes of scratch), and a launch must not use scratch -- such launches take
+// the rules below (two k-groups).
+template <int WN, int WM, int KG, bool WS>
+int launch_dgrad_cfg(const PConvArgs& a, int64_t blocks, hipStream_t st) {
+    constexpr int kStageB = (BK * (64 * WM + 32) + 64 * WN * LDWB) * 2;
+    constexpr int kSmem = KG * (WS ? 2 : 1) * kStageB + 4 * KCH * KG * 4;
+    constexpr int kRed = (KG - 1) * 64 * (64 * WN * WM) * 4;
+    static_assert(kRed <= KG * kStageB, "reduction buffer must fit in the stage memory");
+    static_assert(kSmem <= 160 * 1024, "LDS");
+    static_assert(WN * WM * 64 * 72 * 2 <= kStageB, "epilogue staging must fit in one stage");
+    static SmemAttrState attr_state;
+    if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(&pconv_bf16_kernel<false, WN, WM, KG, WS, true>), kSmem, attr_state)) return rc;
+    hipLaunchKernelGGL((pconv_bf16_kernel<false, WN, WM, KG, WS, true>), dim3((unsigned)blocks),
+                       dim3(64 * WN * WM * KG + (WS ? 256 : 0)), kSmem, st, a);
+    return (int)hipGetLastError();
+}
+
+int launch_dgrad_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks, hipStream_t st) {
+    // (128 x 128: a launch small enough for a second k-group is wave-specialised instead, so <2, 2, 2> is never selected)
+    if (shape == 22) return ws ? launch_dgrad_cfg<2, 2, 1, true>(a, blocks, st) : launch_dgrad_cfg<2, 2, 1, false>(a, blocks, st);
+    if (shape == 14) return kgs == 2 ? launch_dgrad_cfg<1, 4, 2, false>(a, blocks, st) : launch_dgrad_cfg<1, 4, 1, false>(a, blocks, st);
+    return kgs == 2 ? launch_dgrad_cfg<1, 2, 2, false>(a, blocks, st) : launch_dgrad_cfg<1, 2, 1, false>(a, blocks, st);
+}
+
+int gcd_i(int a, int b) {
+    while (b != 0) { const int t = a % b; a = b; b = t; }
+    return a;
+}
+
 // maxpool over [planes][H][W][B] bf16, 8 images per thread (bf16 order = fp32 order of the widened values: exact)
 __global__ __launch_bounds__(256) void maxpool_chwn_bf16_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t total8,
                                                                 int H, int W, int Ho, int Wo, int B8, int k, int s) {
@@ -1715,6 +1777,85 @@ extern "C" int bbb_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void* x,
     if (ws) kgs = 1;
     hipStream_t st = (hipStream_t)stream;
     return out_f32 ? launch_shape<true>(a, shape, kgs, ws, blocks, st) : launch_shape<false>(a, shape, kgs, ws, blocks, st);
+}
+
+// The input gradient of a strided layer on bf16 storage: the transposed form of the general kernel (pconv_bf16_kernel, TR).  The
+// argument contract of bbb_conv2d_chwn_dgrad plus the bf16 forward's operand checks; everything is validated before any launch.
+extern "C" int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* g_pre, const void* w_flipped, void* dx, int up_h,
+                                          int up_w, int out_h, int out_w, uint32_t flags, void* stream) {
+    if (d == nullptr) return BBB_EINVAL;
+    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->pad_h < 0 ||
+        d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 || d->draws <= 0 || up_h <= 0 || up_w <= 0 || out_h <= 0 || out_w <= 0)
+        return BBB_EINVAL;
+    // d describes the stride-1 launch on the flipped rows; the layer's stride travels as the upsampling factors
+    if (d->stride_h != 1 || d->stride_w != 1) return BBB_EINVAL;
+    if (up_h == 1 && up_w == 1) return BBB_EINVAL;          // a stride-1 layer's gradient is bbb_conv2d_chwn_bf16_fwd: one way to compute it
+    if (d->act != 0 || d->pool != 0 || d->w_tap_major != 0 || d->w_row_pitch != 0 || d->unit_div != 0 || d->unit_off != 0 ||
+        d->x_unit_mod != 0 || d->x_unit_div != 0 || d->x_unit_off != 0 || d->b_offset != 0)
+        return BBB_EINVAL;
+    if (d->x_draw_stride < 0 || d->w_draw_stride < 0) return BBB_EINVAL;
+    if ((flags & ~BBB_BF16_W_TAP_MAJOR) != 0) return BBB_EINVAL;
+    const bool tap_major = (flags & BBB_BF16_W_TAP_MAJOR) != 0;
+    if (d->batch % 8 != 0) return BBB_ESHAPE;               // rows of 16-byte vectors of 8 bf16 images
+    if (tap_major && d->cin % 8 != 0) return BBB_ESHAPE;    // a 16-byte weight vector must not straddle two taps
+    // (out_h, out_w) must be a map whose forward (padding p = d (k - 1) - q >= 0, stride up) gives exactly the g map of d
+    const int fph = d->dil_h * (d->kh - 1) - d->pad_h, fpw = d->dil_w * (d->kw - 1) - d->pad_w;
+    if (fph < 0 || fpw < 0) return BBB_ESHAPE;
+    const int64_t nh = (int64_t)out_h + 2 * fph - (int64_t)d->dil_h * (d->kh - 1) - 1;
+    const int64_t nw = (int64_t)out_w + 2 * fpw - (int64_t)d->dil_w * (d->kw - 1) - 1;
+    if (nh < 0 || nw < 0 || nh / up_h + 1 != d->h || nw / up_w + 1 != d->w) return BBB_ESHAPE;
+    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
+    const int64_t Kp = (K + 7) & ~(int64_t)7;
+    if (K >= (1 << 24)) return BBB_ESHAPE;                  // float-reciprocal k decode is exact below 2^24
+    // per-draw slabs are addressed through 32-bit buffer offsets (as in the forward's checks)
+    const int64_t g_bytes = (int64_t)d->cin * d->h * d->w * d->batch * 2, dx_bytes = (int64_t)d->cout * out_h * out_w * d->batch * 2;
+    if (g_bytes > 0xFFFE0000LL || dx_bytes > 0xFFFE0000LL || ((int64_t)d->cout + 64) * Kp * 2 > 0x7FFFFFFFLL ||
+        (int64_t)d->batch * 2 > 0x0FFFFFFFLL)
+        return BBB_ESHAPE;
+    const uint32_t x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 2u) & ~15u;
+    if (g_bytes > (int64_t)x_inv) return BBB_ESHAPE;
+    if (g_pre == nullptr || w_flipped == nullptr || dx == nullptr) return BBB_EINVAL;
+    if ((((uintptr_t)g_pre | (uintptr_t)w_flipped | (uintptr_t)dx) & 15u) != 0) return BBB_EALIGN;
+    if ((d->x_draw_stride & 7) != 0 || (d->w_draw_stride & 7) != 0) return BBB_EALIGN;
+    PConvArgs a = {};
+    a.x = reinterpret_cast<const float*>(g_pre); a.w = reinterpret_cast<const float*>(w_flipped); a.y = reinterpret_cast<float*>(dx);
+    a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
+    a.sh = 1; a.sw = 1; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
+    a.Ho = out_h; a.Wo = out_w; a.K = (int32_t)K; a.Kp = (int32_t)Kp; a.khkw = d->kh * d->kw;
+    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride;
+    a.y_ds = (int64_t)d->cout * out_h * out_w * d->batch;
+    a.x_inv = x_inv;
+    a.wtap = tap_major ? 1 : 0;
+    a.up_h = up_h; a.up_w = up_w;
+    a.tstep_h = up_h / gcd_i(up_h, d->dil_h); a.tstep_w = up_w / gcd_i(up_w, d->dil_w);
+    // tile shape, k-groups and wave specialisation as bbb_conv2d_chwn_bf16_fwd's general path picks them -- with the k-tile count
+    // of the LONGEST contraction a pixel can have: tap-major rows visit at most ceil(k / tstep) taps per axis (counting the full
+    // row would hand k-groups nothing), reference-order rows run over the full row.  Never the small-k, few-output, strip or
+    // pooled kernels, and without the four-k-group form (launch_dgrad_shape).
+    auto waste = [](int n, int t) { return (double)(((n + t - 1) / t) * t) / (double)n; };
+    const double c22 = 256.0 * waste(a.Cout, 128) * waste(a.B, 128);
+    const double c14 = 288.0 * waste(a.Cout, 64) * waste(a.B, 256);
+    const double c12 = 320.0 * waste(a.Cout, 64) * waste(a.B, 128);
+    const int shape = (c22 <= c14 && c22 <= c12) ? 22 : (c14 <= c12 ? 14 : 12);
+    const int64_t kmax = tap_major ? (int64_t)a.Cin * ((a.kh + a.tstep_h - 1) / a.tstep_h) * ((a.kw + a.tstep_w - 1) / a.tstep_w) : K;
+    const int t64 = (int)((kmax + BK - 1) / BK);
+    const int64_t pixels = (int64_t)out_h * out_w;
+    const int bn = shape == 22 ? 128 : 64, bm = shape == 14 ? 256 : 128;
+    a.Ntiles = (a.Cout + bn - 1) / bn;
+    a.G = a.Ntiles * d->draws;
+    a.nbt = (a.B + bm - 1) / bm;
+    const int64_t mt = pixels * a.nbt;
+    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
+    a.Mtiles = (int)mt;
+    const int64_t items = (int64_t)a.G * mt;
+    const int64_t per = (items + 7) / 8;
+    const int64_t blocks = 8 * per;
+    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
+    a.per_xcd = (int32_t)per;
+    int kgs = (items < 512 && t64 >= 8) ? 2 : 1;
+    const bool ws = shape == 22 && items <= 1024;
+    if (ws) kgs = 1;
+    return launch_dgrad_shape(a, shape, kgs, ws, blocks, (hipStream_t)stream);
 }
 
 extern "C" int bbb_maxpool_chwn_bf16(const void* x, void* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream) {

@@ -119,22 +119,6 @@ __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t ite
     int ihb, iwb, r_lo, q_lo, nq, nrq, Keff, ntiles;
     float inv_nrq, inv_nq;
     const float inv_cin = 1.0f / (float)p.Cin;
-    // TR, one axis: taps r = lo + i * step, i < cnt, are those with t = base + r * d >= 0, t % up == 0 and t / up < n
-    auto tr_axis = [](int base, int d, int up, int step, int k, int n, int& lo, int& cnt) {
-        lo = 0; cnt = 0;
-        int first = -1;
-        for (int r = 0; r < step && r < k; ++r)
-            if ((base + r * d) % up == 0) { first = r; break; }
-        if (first < 0) return;
-        const int t0 = base + first * d, sd = step * d;                  // (sd is a multiple of up: members stay divisible)
-        const int r0 = first + (t0 < 0 ? (-t0 + sd - 1) / sd : 0) * step;
-        const int lim = (n - 1) * up - base;                              // r * d <= lim  <=>  t / up <= n - 1
-        if (lim < 0) return;
-        int r1 = lim / d;
-        r1 = r1 < k - 1 ? r1 : k - 1;
-        if (r1 < r0) return;
-        lo = r0; cnt = (r1 - r0) / step + 1;
-    };
     auto set_pixel = [&](int oh, int ow) {
         if constexpr (POOL) {            // re-set inside a loop: keep the pixel's state in scalar registers
             oh = __builtin_amdgcn_readfirstlane(oh);
