@@ -435,6 +435,18 @@ int bbb_lrt_sample_nchw(const float* act_mu, const float* act_var, float* y, int
 #define BBB_BF16_OUT_C8       8u   /* y is written channel-interleaved: [draws][cout / 8][ho][wo][B][8] (ABI 10) */
 int bbb_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void* x, const void* w, const float* bias, void* y,
                              uint32_t flags, void* stream);
+/* What bbb_conv2d_chwn_bf16_fwd picks for (d, flags) (additive to ABI 13; host only, needs no device: tests, profiling).  *form: the
+ * kernel; for BBB_BF16_FORM_GENERAL *shape = 22 (128 channels x 128 images per workgroup), 14 (64 x 256) or 12 (64 x 128),
+ * *k_groups = 1 | 2 | 4, *wave_specialised = 0 | 1 (all three 0 for the other forms).  Out-pointers may be NULL.  Returns what the
+ * launch entry returns for every check that does not involve an operand pointer; the two call the same plan (csrc/pconv_bf16_plan.h). */
+#define BBB_BF16_FORM_GENERAL 0        /* pconv_bf16_kernel */
+#define BBB_BF16_FORM_SMALLK 1         /* short contraction (row pitch <= 128), weights in registers */
+#define BBB_BF16_FORM_SMALLK_POOL 2    /* ... with the pooling in the launch, strip form */
+#define BBB_BF16_FORM_SMALLK_POOLWIN 3 /* ... window-resident form (small launches) */
+#define BBB_BF16_FORM_STRIP8 4         /* BBB_BF16_X_C8 */
+#define BBB_BF16_FORM_FEWOUT 5         /* classifiers: <= 16 outputs, a row of >= 512 */
+int bbb_conv2d_chwn_bf16_plan(const bbb_conv_desc_t* d, uint32_t flags, int32_t* form, int32_t* shape, int32_t* k_groups,
+                              int32_t* wave_specialised);
 /* nn.MaxPool2d(k, s) on [planes][h][w][B] bf16 (B % 8 == 0); exact (max commutes with the rounding). */
 int bbb_maxpool_chwn_bf16(const void* x, void* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream);
 /* fp32 [batch][plane] (an NCHW tensor, plane = C*H*W) -> bf16 [plane][batch] (batch-innermost), nearest-even. */
@@ -681,6 +693,11 @@ int bbb_batch_chunks_bf16(const void* x, void* out, int64_t outer, int64_t rows,
  * the useful matrix work).  A pixel no tap reaches is written as +0.  Every check happens before any launch. */
 int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* g_pre, const void* w_flipped, void* dx, int up_h, int up_w,
                                int out_h, int out_w, uint32_t flags, void* stream);
+/* What that launch picks (additive to ABI 13; host only): *shape = 22 | 14 | 12, *k_groups = 1 | 2, *wave_specialised = 0 | 1, as
+ * for bbb_conv2d_chwn_bf16_plan -- always the general kernel.  Out-pointers may be NULL; the launch entry's codes for every check
+ * that does not involve an operand pointer. */
+int bbb_conv2d_chwn_bf16_dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, int out_w, uint32_t flags,
+                                    int32_t* shape, int32_t* k_groups, int32_t* wave_specialised);
 
 /* Library / device introspection (host-only). */
 int bbb_abi_version(void);

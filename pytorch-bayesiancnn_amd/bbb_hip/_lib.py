@@ -86,6 +86,8 @@ _SIGNATURES = {
     "bbb_lrt_pool_act_bwd_chwn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "bbb_conv2d_chwn_bf16_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_u32, c_void_p]),
+    "bbb_conv2d_chwn_bf16_plan": (c_int, [ctypes.POINTER(ConvDesc), c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                          ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "bbb_maxpool_chwn_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bbb_nchw_to_chwn_bf16": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p]),
     "bbb_nchw_to_chwn_bf16_slices": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p]),
@@ -135,6 +137,8 @@ _SIGNATURES = {
     "bbb_flip_transpose_w_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_u32, c_void_p]),
     "bbb_conv2d_chwn_bf16_dgrad": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_u32,
                                            c_void_p]),
+    "bbb_conv2d_chwn_bf16_dgrad_plan": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, c_int, c_int, c_u32, ctypes.POINTER(c_i32),
+                                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "bbb_chwn_to_bhwc_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
     "bbb_batch_chunks_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
     "bbb_abi_version": (c_int, []),

@@ -1266,6 +1266,27 @@ def lrt_bf16_plan(x_shape, cout, cin_khkw, stride=1, padding=0, dilation=1, draw
     return sh.value, kg.value, bool(ws.value)
 
 
+BF16_FORMS = ("general", "smallk", "smallk-pool", "smallk-poolwin", "strip8", "fewout")      # BBB_BF16_FORM_* (include/bbb_hip.h)
+
+
+def bf16_fwd_plan(x_shape, cout, cin_khkw, stride=1, padding=0, dilation=1, draws=None, out_f32=False, tap_major=False, x_c8=False,
+                  out_c8=False, pool=None):
+    """(form, tile shape, k-groups, wave-specialised) the library picks for conv2d_chwn_bf16_forward on x_shape = [E, Cin, H, W, B]:
+    form one of BF16_FORMS; for "general" the tile shape 22 | 14 | 12, 1 | 2 | 4 k-groups and whether the launch is
+    wave-specialised, (0, 0, False) otherwise (bbb_conv2d_chwn_bf16_plan, the launch entry's own plan; host only: needs no device).
+    A geometry the launch refuses raises the launch's error."""
+    E = int(draws) if draws is not None else x_shape[0]
+    d, _, _ = _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, False, None)
+    d.w_draw_stride = cout * bf16_row_pitch(cin_khkw[0] * cin_khkw[1] * cin_khkw[2])
+    if pool is not None:
+        d.pool = 1 if tuple(pool) == (2, 2) else ((int(pool[0]) << 8) | int(pool[1]))
+    flags = (1 if out_f32 else 0) | (2 if tap_major else 0) | (4 if x_c8 else 0) | (8 if out_c8 else 0)
+    fm, sh, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.lib().bbb_conv2d_chwn_bf16_plan(ctypes.byref(d), flags, ctypes.byref(fm), ctypes.byref(sh), ctypes.byref(kg),
+                                               ctypes.byref(ws)), "bbb_conv2d_chwn_bf16_plan")
+    return BF16_FORMS[fm.value], sh.value, kg.value, bool(ws.value)
+
+
 def lrt_conv2d_chwn_bf16_forward(x, w_mu, w_var, b_mu, b_var, cin_khkw, seed, call0, stream_id, stride=1, padding=0, dilation=1,
                                  sample=True, want_moments=False, moments_only=False, act=None, out_f32=False, out=None,
                                  tap_major=False, b_offset=0, x_div=1, x_off=0, n_slabs=None):
@@ -2564,31 +2585,35 @@ def flip_transpose_w_bf16(w, w_shape):
     return out
 
 
+def _bf16_dgrad_desc(B, cin, cout, kh, kw, g_hw, pad, dilation, E, g_shared=False, w_shared=False):
+    """The descriptor of bbb_conv2d_chwn_bf16_dgrad: the stride-1 launch on the flipped rows of a layer with weights (cout, cin, kh,
+    kw) over g's map g_hw, pad = dilation * (k - 1) - the layer's padding."""
+    (dh, dw), (qh, qw) = _pair(dilation), _pair(pad)
+    d = ConvDesc()
+    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, cout, g_hw[0], g_hw[1], cin, kh, kw
+    d.stride_h = d.stride_w = 1
+    d.pad_h, d.pad_w, d.dil_h, d.dil_w = qh, qw, dh, dw
+    d.draws = E
+    d.x_draw_stride = 0 if g_shared else cout * g_hw[0] * g_hw[1] * B
+    d.w_draw_stride = 0 if w_shared else cin * bf16_row_pitch(cout * kh * kw)
+    return d
+
+
 def bf16_dgrad_form(B, cin, cout, kh, kw, x_hw, stride, dilation, draws):
     """(tile shape 22 | 14 | 12, k-groups 1 | 2, wave-specialised, tap-major rows) bbb_conv2d_chwn_bf16_dgrad picks for the input
-    gradient of a strided layer with weights (cout, cin, kh, kw), input map x_hw = (H, W), `draws` draws of B images -- the host
-    restatement of its selection (csrc/pconv_bf16.hip): the general path's rules of bbb_conv2d_chwn_bf16_fwd on dx's cin channels
-    and H x W pixels, with the k-tile count of the LONGEST contraction a pixel can have (tap-major rows: cout * ceil(kh / tstep_h) *
-    ceil(kw / tstep_w), tstep = s / gcd(s, d); reference-order rows: the full row), and without the forward's four-k-group form
-    for tiny launches (its transposed instantiation would spill registers)."""
+    gradient of a strided layer with weights (cout, cin, kh, kw), input map x_hw = (H, W), `draws` draws of B images: the launch
+    entry's own plan (bbb_conv2d_chwn_bf16_dgrad_plan, csrc/pconv_bf16_plan.h: dgrad_tile_rule; host only).  The selection does
+    not depend on the layer's padding; the descriptor asked about is the layer with padding dilation * (k - 1), whose output map
+    exists for every input map."""
     (sh, sw), (dh, dw) = _pair(stride), _pair(dilation)
     H, W = int(x_hw[0]), int(x_hw[1])
     tap_major = bf16_tap_major((cin, cout, kh, kw))
-    waste = lambda n, t: -(-n // t) * t / n
-    c22 = 256.0 * waste(cin, 128) * waste(B, 128)
-    c14 = 288.0 * waste(cin, 64) * waste(B, 256)
-    c12 = 320.0 * waste(cin, 64) * waste(B, 128)
-    shape = 22 if (c22 <= c14 and c22 <= c12) else (14 if c14 <= c12 else 12)
-    th, tw = sh // math.gcd(sh, dh), sw // math.gcd(sw, dw)
-    kmax = cout * -(-kh // th) * -(-kw // tw) if tap_major else cout * kh * kw
-    t64 = -(-kmax // 64)
-    bn, bm = (128 if shape == 22 else 64), (256 if shape == 14 else 128)
-    items = draws * H * W * -(-cin // bn) * -(-B // bm)
-    kgs = 2 if (items < 512 and t64 >= 8) else 1
-    ws = shape == 22 and items <= 1024
-    if ws:
-        kgs = 1
-    return shape, kgs, ws, tap_major
+    g_hw = ((H + dh * (kh - 1) - 1) // sh + 1, (W + dw * (kw - 1) - 1) // sw + 1)
+    d = _bf16_dgrad_desc(B, cin, cout, kh, kw, g_hw, 0, (dh, dw), int(draws))
+    shape, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad_plan(ctypes.byref(d), sh, sw, H, W, 2 if tap_major else 0, ctypes.byref(shape),
+                                                     ctypes.byref(kg), ctypes.byref(ws)), "bbb_conv2d_chwn_bf16_dgrad_plan")
+    return shape.value, kg.value, bool(ws.value), tap_major
 
 
 def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_flipped=None, stride=1):
@@ -2621,13 +2646,8 @@ def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_fl
     if g_pre.shape[1] != Cout or w_t.shape[1] != Cin or w_t.shape[2] != bf16_row_pitch(Cout * kh * kw):
         raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: rows do not match the weight shape")
     H, W, B = int(x_hw[0]), int(x_hw[1]), g_pre.shape[4]
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cout, g_pre.shape[2], g_pre.shape[3], Cin, kh, kw
-    d.stride_h = d.stride_w = 1
-    d.pad_h, d.pad_w, d.dil_h, d.dil_w = qh, qw, dh, dw
-    d.draws = E
-    d.x_draw_stride = 0 if (g_pre.shape[0] == 1 and E > 1) else Cout * g_pre.shape[2] * g_pre.shape[3] * B
-    d.w_draw_stride = 0 if (w_t.shape[0] == 1 and E > 1) else w_t.shape[1] * w_t.shape[2]
+    d = _bf16_dgrad_desc(B, Cin, Cout, kh, kw, (g_pre.shape[2], g_pre.shape[3]), (qh, qw), (dh, dw), E,
+                         g_pre.shape[0] == 1 and E > 1, w_t.shape[0] == 1 and E > 1)
     gx = torch.empty((E, Cin, H, W, B), dtype=torch.bfloat16, device=g_pre.device)
     with on_device(g_pre.device):
         check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,

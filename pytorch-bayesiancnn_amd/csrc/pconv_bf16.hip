@@ -29,6 +29,7 @@
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
 #include "pconv_args.h"
+#include "pconv_bf16_plan.h"
 #include "smem_attr.h"
 
 namespace {
@@ -41,9 +42,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BK = 64;
-constexpr int LDWB = BK + 8;             // weight row pitch (elements): 144 B
-constexpr int KCH = 256;                 // k entries per decode chunk and k-group
+using bf16_plan::BK;                     // (k per tile, weight row pitch, k per decode chunk and k-group: pconv_bf16_plan.h)
+using bf16_plan::LDWB;
+using bf16_plan::KCH;
 constexpr int TPC = KCH / BK;
 
 __device__ __forceinline__ uint16_t f2bf(float v) {              // round to nearest even (v_cvt_pk_bf16_f32)
@@ -849,7 +850,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT == 1 ? 2
 // reads of the next pixel in flight under the current pixel's MFMAs.  Out-of-image taps are rows the loader filled with zeros (the
 // buffer unit returns 0 for their out-of-range offsets); k >= K reads a zero row.  Same MFMA sequence per output element as the
 // other forms: bit-identical.
-constexpr int kWinPasses = 13;             // 16-row passes of the window loader: windows of up to 13 * 16 - 1 = 207 image rows (+ the zero row)
+using bf16_plan::kWinPasses;               // 16-row passes of the window loader (pconv_bf16_plan.h)
 
 template <int KS, bool C8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pconv_bf16_smallk_poolwin_kernel(const PConvArgs p) {
@@ -1445,34 +1446,25 @@ int launch_smallk(const PConvArgs& a, int64_t blocks, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
+// (one weight tile per stage: launch_cfg, smem_attr.h)
 template <bool OUT_F32, int WN, int WM, int KG, bool WS>
-int launch_cfg(const PConvArgs& a, int64_t blocks, hipStream_t st) {
-    constexpr int kStageB = (BK * (64 * WM + 32) + 64 * WN * LDWB) * 2;
-    constexpr int kSmem = KG * (WS ? 2 : 1) * kStageB + 4 * KCH * KG * 4;
-    constexpr int kRed = (KG - 1) * 64 * (64 * WN * WM) * 4;
-    static_assert(kRed <= KG * kStageB, "reduction buffer must fit in the stage memory");
-    static_assert(kSmem <= 160 * 1024, "LDS");
-    static_assert(WN * WM * 64 * 72 * 2 <= kStageB, "epilogue staging must fit in one stage");
-    static SmemAttrState attr_state;
-    if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(&pconv_bf16_kernel<OUT_F32, WN, WM, KG, WS>), kSmem, attr_state)) return rc;
-    hipLaunchKernelGGL((pconv_bf16_kernel<OUT_F32, WN, WM, KG, WS>), dim3((unsigned)blocks),
-                       dim3(64 * WN * WM * KG + (WS ? 256 : 0)), kSmem, st, a);
-    return (int)hipGetLastError();
+int launch_fwd(const PConvArgs& a, int64_t blocks, hipStream_t st) {
+    return launch_cfg<&pconv_bf16_kernel<OUT_F32, WN, WM, KG, WS>, WN, WM, KG, WS, 1>(a, blocks, st);
 }
 
 template <bool OUT_F32>
 int launch_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks, hipStream_t st) {
     if (shape == 22) {
-        if (ws) return launch_cfg<OUT_F32, 2, 2, 1, true>(a, blocks, st);
-        return kgs == 2 ? launch_cfg<OUT_F32, 2, 2, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 2, 2, 1, false>(a, blocks, st);
+        if (ws) return launch_fwd<OUT_F32, 2, 2, 1, true>(a, blocks, st);
+        return kgs == 2 ? launch_fwd<OUT_F32, 2, 2, 2, false>(a, blocks, st) : launch_fwd<OUT_F32, 2, 2, 1, false>(a, blocks, st);
     }
     if (shape == 14) {
-        if (ws) return launch_cfg<OUT_F32, 1, 4, 1, true>(a, blocks, st);
-        return kgs == 2 ? launch_cfg<OUT_F32, 1, 4, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 1, 4, 1, false>(a, blocks, st);
+        if (ws) return launch_fwd<OUT_F32, 1, 4, 1, true>(a, blocks, st);
+        return kgs == 2 ? launch_fwd<OUT_F32, 1, 4, 2, false>(a, blocks, st) : launch_fwd<OUT_F32, 1, 4, 1, false>(a, blocks, st);
     }
-    if (ws) return launch_cfg<OUT_F32, 1, 2, 1, true>(a, blocks, st);
-    if (kgs == 4) return launch_cfg<OUT_F32, 1, 2, 4, false>(a, blocks, st);
-    return kgs == 2 ? launch_cfg<OUT_F32, 1, 2, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 1, 2, 1, false>(a, blocks, st);
+    if (ws) return launch_fwd<OUT_F32, 1, 2, 1, true>(a, blocks, st);
+    if (kgs == 4) return launch_fwd<OUT_F32, 1, 2, 4, false>(a, blocks, st);
+    return kgs == 2 ? launch_fwd<OUT_F32, 1, 2, 2, false>(a, blocks, st) : launch_fwd<OUT_F32, 1, 2, 1, false>(a, blocks, st);
 }
 
 // the transposed form: every (shape, k-groups, wave-specialised) combination its selection can produce.  The forward's "tiny" rule
@@ -1480,30 +1472,15 @@ int launch_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks
 // of a 512-thread workgroup may hold (5 spilled, 24 bytes of scratch), and a launch must not use scratch -- such launches take
 // the rules below (two k-groups).
 template <int WN, int WM, int KG, bool WS>
-int launch_dgrad_cfg(const PConvArgs& a, int64_t blocks, hipStream_t st) {
-    constexpr int kStageB = (BK * (64 * WM + 32) + 64 * WN * LDWB) * 2;
-    constexpr int kSmem = KG * (WS ? 2 : 1) * kStageB + 4 * KCH * KG * 4;
-    constexpr int kRed = (KG - 1) * 64 * (64 * WN * WM) * 4;
-    static_assert(kRed <= KG * kStageB, "reduction buffer must fit in the stage memory");
-    static_assert(kSmem <= 160 * 1024, "LDS");
-    static_assert(WN * WM * 64 * 72 * 2 <= kStageB, "epilogue staging must fit in one stage");
-    static SmemAttrState attr_state;
-    if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(&pconv_bf16_kernel<false, WN, WM, KG, WS, true>), kSmem, attr_state)) return rc;
-    hipLaunchKernelGGL((pconv_bf16_kernel<false, WN, WM, KG, WS, true>), dim3((unsigned)blocks),
-                       dim3(64 * WN * WM * KG + (WS ? 256 : 0)), kSmem, st, a);
-    return (int)hipGetLastError();
+int launch_tr(const PConvArgs& a, int64_t blocks, hipStream_t st) {
+    return launch_cfg<&pconv_bf16_kernel<false, WN, WM, KG, WS, true>, WN, WM, KG, WS, 1>(a, blocks, st);
 }
 
 int launch_dgrad_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks, hipStream_t st) {
     // (128 x 128: a launch small enough for a second k-group is wave-specialised instead, so <2, 2, 2> is never selected)
-    if (shape == 22) return ws ? launch_dgrad_cfg<2, 2, 1, true>(a, blocks, st) : launch_dgrad_cfg<2, 2, 1, false>(a, blocks, st);
-    if (shape == 14) return kgs == 2 ? launch_dgrad_cfg<1, 4, 2, false>(a, blocks, st) : launch_dgrad_cfg<1, 4, 1, false>(a, blocks, st);
-    return kgs == 2 ? launch_dgrad_cfg<1, 2, 2, false>(a, blocks, st) : launch_dgrad_cfg<1, 2, 1, false>(a, blocks, st);
-}
-
-int gcd_i(int a, int b) {
-    while (b != 0) { const int t = a % b; a = b; b = t; }
-    return a;
+    if (shape == 22) return ws ? launch_tr<2, 2, 1, true>(a, blocks, st) : launch_tr<2, 2, 1, false>(a, blocks, st);
+    if (shape == 14) return kgs == 2 ? launch_tr<1, 4, 2, false>(a, blocks, st) : launch_tr<1, 4, 1, false>(a, blocks, st);
+    return kgs == 2 ? launch_tr<1, 2, 2, false>(a, blocks, st) : launch_tr<1, 2, 1, false>(a, blocks, st);
 }
 
 // maxpool over [planes][H][W][B] bf16, 8 images per thread (bf16 order = fp32 order of the widened values: exact)
@@ -1563,299 +1540,83 @@ __global__ __launch_bounds__(256) void nchw_to_chwn_bf16_kernel(const float* __r
 
 }  // namespace
 
+extern "C" int bbb_conv2d_chwn_bf16_plan(const bbb_conv_desc_t* d, uint32_t flags, int32_t* form, int32_t* shape, int32_t* k_groups,
+                                         int32_t* wave_specialised) {
+    bf16_plan::FwdPlan p;
+    if (const int rc = bf16_plan::fwd_plan(d, flags, 0, &p)) return rc;
+    if (form) *form = p.form;
+    if (shape) *shape = p.tile.shape;
+    if (k_groups) *k_groups = p.tile.kgs;
+    if (wave_specialised) *wave_specialised = p.tile.ws ? 1 : 0;
+    return 0;
+}
+
 extern "C" int bbb_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void* x, const void* w, const float* bias, void* y,
                                         uint32_t flags, void* stream) {
-    const int out_f32 = (flags & BBB_BF16_OUT_F32) ? 1 : 0;
-    const bool tap_major = (flags & BBB_BF16_W_TAP_MAJOR) != 0;
+    const bool out_f32 = (flags & BBB_BF16_OUT_F32) != 0;
     if (d == nullptr || x == nullptr || w == nullptr || y == nullptr) return BBB_EINVAL;
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 ||
-        d->draws <= 0 || d->act < 0 || d->act > 2)
-        return BBB_EINVAL;
-    if (d->batch % 8 != 0) return BBB_ESHAPE;        // rows of 16-byte vectors of 8 bf16 images
-    if (tap_major && d->cin % 8 != 0) return BBB_ESHAPE;   // a 16-byte weight vector must not straddle two taps
-    if ((flags & ~(BBB_BF16_OUT_F32 | BBB_BF16_W_TAP_MAJOR | BBB_BF16_X_C8 | BBB_BF16_OUT_C8)) != 0) return BBB_EINVAL;
-    const bool x_c8 = (flags & BBB_BF16_X_C8) != 0, out_c8 = (flags & BBB_BF16_OUT_C8) != 0;
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
-    const int64_t Kp = (K + 7) & ~(int64_t)7;
-    if (K >= (1 << 24)) return BBB_ESHAPE;           // float-reciprocal k decode is exact below 2^24
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 2 > 0xFFFE0000LL || (int64_t)d->cout * ho * wo * d->batch * 4 > 0xFFFE0000LL ||
-        ((int64_t)d->cout + 64) * Kp * 2 > 0x7FFFFFFFLL || (int64_t)d->batch * 2 > 0x0FFFFFFFLL)
-        return BBB_ESHAPE;
-    const uint32_t x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 2u) & ~15u;   // a ragged last tile reaches < 512 columns past the row
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 2 > (int64_t)x_inv) return BBB_ESHAPE;
-    if ((((uintptr_t)x | (uintptr_t)w) & 15u) != 0 || ((uintptr_t)y & (out_f32 ? 3u : 1u)) != 0 || ((uintptr_t)bias & 3u) != 0)
-        return BBB_EALIGN;
-    if ((d->x_draw_stride & 7) != 0 || (d->w_draw_stride & 7) != 0) return BBB_EALIGN;
+    const bool misaligned = (((uintptr_t)x | (uintptr_t)w) & 15u) != 0 || ((uintptr_t)y & (out_f32 ? 3u : 1u)) != 0 || ((uintptr_t)bias & 3u) != 0;
+    bf16_plan::FwdPlan p;
+    if (const int rc = bf16_plan::fwd_plan(d, flags, misaligned ? BBB_EALIGN : 0, &p)) return rc;
     PConvArgs a = {};
-    a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
-    a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = ho; a.Wo = wo; a.K = (int32_t)K; a.Kp = (int32_t)Kp; a.khkw = d->kh * d->kw; a.act = d->act;
-    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride;
-    a.y_ds = (int64_t)d->cout * ho * wo * d->batch;
+    bf16_plan::fill_geometry(a, d, p.g, (flags & BBB_BF16_W_TAP_MAJOR) != 0);
+    a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride;
+    a.y_ds = p.y_ds;
     a.x = reinterpret_cast<const float*>(x); a.w = reinterpret_cast<const float*>(w); a.bias = bias;
     a.y = reinterpret_cast<float*>(y);
-    a.x_inv = x_inv;
-    a.wtap = tap_major ? 1 : 0;
-    if (d->unit_div < 0 || d->unit_off < 0 || d->x_unit_mod < 0 || (d->unit_div > 1 && d->unit_off >= d->unit_div) ||
-        (d->x_unit_mod > 0 && d->x_unit_mod != d->unit_div) || d->w_row_pitch != 0 || d->w_tap_major != 0)
-        return BBB_EINVAL;
-    // pooling in the launch (bbb_conv_desc_t::pool): first layers with a short contraction only (pconv_bf16_smallk_pool_kernel);
-    // 1 = MaxPool2d(2, 2), (k << 8) | s otherwise; admitted: 2 / 2 and 3 / 2 (at most one window closes per conv column)
-    int pool_k = 0, pool_s = 0;
-    if (d->pool != 0) {
-        pool_k = d->pool == 1 ? 2 : (d->pool >> 8);
-        pool_s = d->pool == 1 ? 2 : (d->pool & 255);
-        if (!((pool_k == 2 && pool_s == 2) || (pool_k == 3 && pool_s == 2)) || ho < pool_k || wo < pool_k) return BBB_EINVAL;
-        if (tap_major || out_f32 || Kp > 128) return BBB_EINVAL;
-        if (x_c8 || (out_c8 && d->cout % 8 != 0)) return BBB_EINVAL;
-        a.y_c8 = out_c8 ? 1 : 0;
-    }
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && (d->unit_div > 1 || d->x_unit_off >= d->x_unit_div)) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
     a.x_div = d->x_unit_div; a.x_off = d->x_unit_off;
     a.unit_div = d->unit_div; a.unit_off = d->unit_div > 1 ? d->unit_off : 0; a.x_mod = d->x_unit_mod;
-    if (pool_k != 0) {
-        const int nt = a.Cout <= 32 ? 1 : 2;
-        const int ks = Kp <= 32 ? 2 : (Kp <= 80 ? 5 : 8);
-        a.Ntiles = (a.Cout + 32 * nt - 1) / (32 * nt);
-        a.G = a.Ntiles * d->draws;
-        a.nbt = (a.B + 255) / 256;
-        a.pool = (pool_k << 8) | pool_s;
-        const int hp = (ho - pool_k) / pool_s + 1, wp = (wo - pool_k) / pool_s + 1;
-        a.y_ds = (int64_t)d->cout * hp * wp * d->batch;
-        // the window-resident form (pconv_bf16_smallk_poolwin_kernel): <= 32 channels, 128-image tiles, the widest strip whose input
-        // window (+ one zero row) and epilogue staging fit 72 KB of LDS (two workgroups per CU).  Its workgroups are short (one
-        // memory round trip for the window, 15 pixels, two pooled outputs: ~8 us each), so it wins where the strip form is a
-        // latency chain -- small launches -- and loses once the strip form fills the chip (3Conv3FC conv1 + pool1, bs 256, us per
-        // launch, window / strip / conv + pool launches: 1 step 15.8 / 38.8 / 18.4, 4 steps 34.8 / 52.8 / 46.5, 5-6 steps 45.8 / 44.2 /
-        // 82, 16 steps 128 / 101 / 167; profiles/r05_notes.md section 3): below 70 pooled rows x image tiles
-        if (nt == 1 && (int64_t)a.G * a.nbt * hp < 70) {
-            const int WRw = (pool_k - 1) * a.sh + (a.kh - 1) * a.dh + 1;
-            int best_n = 0;
-            for (int n = 1; n <= wp; ++n) {
-                const int cols = (n - 1) * pool_s + pool_k;
-                const int WCw = (cols - 1) * a.sw + (a.kw - 1) * a.dw + 1;
-                const int64_t bytes = ((int64_t)a.Cin * WRw * WCw + 1) * (128 + 32) * 2 + 4 * 32 * 40 * 2;
-                if (bytes <= 72 * 1024 && a.Cin * WRw * WCw + 1 <= kWinPasses * 16) best_n = n;
-            }
-            if (best_n >= 1) {
-                const int nstr = (wp + best_n - 1) / best_n;
-                const int wpc = (wp + nstr - 1) / nstr;               // what the kernel derives from nstr
-                const int cols = (wpc - 1) * pool_s + pool_k;
-                const int WCw = (cols - 1) * a.sw + (a.kw - 1) * a.dw + 1;
-                const int rows = a.Cin * WRw * WCw + 1;
-                a.Mtiles = rows;
-                a.px_run = nstr;
-                a.nbt = (a.B + 127) / 128;
-                const int64_t itemsw = (int64_t)a.G * a.nbt * hp * nstr;
-                const int64_t perw = (itemsw + 7) / 8;
-                if (8 * perw > 0x7fffffffLL) return BBB_ESHAPE;
-                a.per_xcd = (int32_t)perw;
-                const int smem_bytes = rows * (128 + 32) * 2 + 4 * 32 * 40 * 2;
-                hipStream_t stw = (hipStream_t)stream;
-                return ks == 2 ? launch_smallk_poolwin<2>(a, 8 * perw, smem_bytes, stw)
-                     : ks == 5 ? launch_smallk_poolwin<5>(a, 8 * perw, smem_bytes, stw) : launch_smallk_poolwin<8>(a, 8 * perw, smem_bytes, stw);
-            }
-        }
-        // workgroups per pooled row.  A strip of n pooled pixels walks n * ps + pk - ps conv columns, so narrow strips compute
-        // shared columns twice, wide strips leave the chip short of workgroups: take the split whose launch costs least in
-        // (rounds of resident workgroups: 2 per CU at this kernel's register footprint) x (columns of its widest strip).
-        // 3Conv3FC conv1, 16 steps per launch (240 pooled rows): 2 strips of 8 / 7 pooled pixels = 480 workgroups, one round, 17
-        // columns (3 strips = 720 workgroups = two rounds of 11: measured 128 us against 1xx, profiles/r05_notes.md section 3)
-        const int64_t rows = (int64_t)a.G * a.nbt * hp;
-        const int64_t slots = 512;
-        int csplit = 1;
-        int64_t best = -1;
-        const int max_split = wp >= 2 ? wp / 2 : 1;
-        for (int c = 1; c <= max_split; ++c) {
-            const int wpc = (wp + c - 1) / c;
-            const int used = (wp + wpc - 1) / wpc;                // strips that actually hold pixels
-            const int64_t rounds = (rows * used + slots - 1) / slots;
-            const int64_t cost = rounds * (wpc * pool_s + pool_k - pool_s);
-            if (best < 0 || cost < best) { best = cost; csplit = c; }
-        }
-        a.px_run = csplit;
-        const int64_t items = rows * csplit;
-        const int64_t per = (items + 7) / 8;
-        if (8 * per > 0x7fffffffLL) return BBB_ESHAPE;
-        a.per_xcd = (int32_t)per;
-        hipStream_t st = (hipStream_t)stream;
-        if (nt == 1) return ks == 2 ? launch_smallk_pool<1, 2>(a, 8 * per, st) : ks == 5 ? launch_smallk_pool<1, 5>(a, 8 * per, st) : launch_smallk_pool<1, 8>(a, 8 * per, st);
-        return ks == 2 ? launch_smallk_pool<2, 2>(a, 8 * per, st) : ks == 5 ? launch_smallk_pool<2, 5>(a, 8 * per, st) : launch_smallk_pool<2, 8>(a, 8 * per, st);
-    }
-    if (x_c8) {
-        // channel-interleaved input: the strip form that reads its MFMA operands straight from memory (pconv_bf16_strip8_kernel).
-        // Tap-major rows of 32 input channels, 5 x 5 taps, stride 1, no dilation (3Conv3FC conv2); bf16 output in either layout.
-        if (!(tap_major && !out_f32 && (!out_c8 || a.Cout % 8 == 0) && a.Cin == 32 && a.kh == 5 && a.kw == 5 && a.sh == 1 && a.sw == 1 &&
-              a.dh == 1 && a.dw == 1 && a.pw < a.kw && a.ph < a.kh))
-            return BBB_EINVAL;
-        constexpr int P8 = 3;
-        a.y_c8 = out_c8 ? 1 : 0;
-        a.Ntiles = (a.Cout + 63) / 64;
-        a.G = a.Ntiles * d->draws;
-        a.nbt = (a.B + 127) / 128;
-        a.px_run = (wo + P8 - 1) / P8;
-        const int64_t sitems = (int64_t)a.G * ho * a.px_run * a.nbt;
-        const int64_t sper = (sitems + 7) / 8;
-        if (8 * sper > 0x7fffffffLL) return BBB_ESHAPE;
-        a.per_xcd = (int32_t)sper;
-        return launch_strip8<P8, 5, 4>(a, 8 * sper, (hipStream_t)stream);
-    }
-    if (out_c8) return BBB_EINVAL;                    // only the pooled first-layer forms and the strip form write that layout
-    if (!tap_major && !out_f32 && Kp <= 128 && (int64_t)ho * wo >= 16) {
-        // a first layer with a short contraction: weights in registers, a run of pixels per workgroup (pconv_bf16_smallk_kernel)
-        const int nt = a.Cout <= 32 ? 1 : 2;
-        const int ks = Kp <= 32 ? 2 : (Kp <= 80 ? 5 : 8);
-        a.Ntiles = (a.Cout + 32 * nt - 1) / (32 * nt);
-        a.G = a.Ntiles * d->draws;
-        a.nbt = (a.B + 255) / 256;
-        const int64_t npix = (int64_t)a.G * a.nbt * ho * wo;      // (pixel, channel tile, image tile) units of the launch
-        int run = (int)(npix / 512);                              // >= 512 workgroups (2 per CU) before runs get longer
-        run = run < 1 ? 1 : (run > 16 ? 16 : run);
-        a.px_run = run;
-        const int64_t items = (int64_t)a.G * a.nbt * (((int64_t)ho * wo + run - 1) / run);
-        const int64_t per = (items + 7) / 8;
-        if (8 * per > 0x7fffffffLL) return BBB_ESHAPE;
-        a.per_xcd = (int32_t)per;
-        hipStream_t st = (hipStream_t)stream;
-        if (nt == 1) return ks == 2 ? launch_smallk<1, 2>(a, 8 * per, st) : ks == 5 ? launch_smallk<1, 5>(a, 8 * per, st) : launch_smallk<1, 8>(a, 8 * per, st);
-        return ks == 2 ? launch_smallk<2, 2>(a, 8 * per, st) : ks == 5 ? launch_smallk<2, 5>(a, 8 * per, st) : launch_smallk<2, 8>(a, 8 * per, st);
-    }
-    if (a.Cout <= 16 && K >= 512 && a.kh == 1 && a.kw == 1 && a.H == 1 && a.W == 1 && a.ph == 0 && a.pw == 0) {
-        // a classifier with a handful of outputs and a long row: plain FMAs, k slices summed in a fixed order (pconv_bf16_fewout_kernel)
-        const int kps = (int)(((Kp + 63) / 64 + 7) / 8) * 8;
-        a.px_run = kps;
-        a.G = (int)((Kp + kps - 1) / kps);                // slices that hold any k (<= 64)
-        a.nbt = (a.B + 31) / 32;
-        a.y_f32 = out_f32 ? 1 : 0;
-        const int64_t fitems = (int64_t)d->draws * a.nbt;
-        if (fitems > 0x7fffffffLL) return BBB_ESHAPE;
-        hipStream_t fst = (hipStream_t)stream;
-        return a.Cout <= 10 ? launch_fewout<10>(a, fitems, fst) : launch_fewout<16>(a, fitems, fst);
-    }
-    // tile shape: LDS-pipe cycles per unit of useful work (see the kernel comment), including the waste of ragged
-    // channel / image tiles: 128x128 -> 256, 64x256 -> 288, 64x128 (two waves) -> 320
-    auto waste = [](int n, int t) { return (double)(((n + t - 1) / t) * t) / (double)n; };
-    const double c22 = 256.0 * waste(a.Cout, 128) * waste(a.B, 128);
-    const double c14 = 288.0 * waste(a.Cout, 64) * waste(a.B, 256);
-    const double c12 = 320.0 * waste(a.Cout, 64) * waste(a.B, 128);
-    int shape = (c22 <= c14 && c22 <= c12) ? 22 : (c14 <= c12 ? 14 : 12);
-    // Few workgroups with long rows (a 1000 -> 10 classifier: ONE 64 x 256 tile per draw, 16 tiles of k; AlexNet's conv3-5 at one
-    // draw) are nothing but their serial k loops: take the two-wave 64 x 128 shape, whose small stage leaves room for FOUR
-    // k-groups per workgroup, each with its own stage and loads in flight (measured, profiles/r03_notes.md section 10: fc3 of
-    // 3Conv3FC 20.7 -> 16.5 us, fc2 15.7 -> 14.6, AlexNet one draw conv2 19.0 -> 15.6, conv4 20.3 -> 18.4, conv5 15.4 -> 14.2).
-    const int t64_all = (int)((K + BK - 1) / BK);
-    const int64_t items12 = (int64_t)d->draws * ho * wo * ((a.Cout + 63) / 64) * ((a.B + 127) / 128);
-    const bool tiny = t64_all >= 16 && items12 < 256;
-    if (tiny) shape = 12;
-    const int bn = shape == 22 ? 128 : 64, bm = shape == 14 ? 256 : 128;
-    a.Ntiles = (a.Cout + bn - 1) / bn;
-    a.G = a.Ntiles * d->draws;
-    a.nbt = (a.B + bm - 1) / bm;
-    const int64_t mt = (int64_t)ho * wo * a.nbt;
-    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mt;
-    const int64_t items = (int64_t)a.G * mt;
-    const int64_t per = (items + 7) / 8;
-    const int64_t blocks = 8 * per;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
-    // a second k-group (its own stage, its own loads in flight, deterministic LDS reduction) when the launch cannot
-    // fill the chip with workgroups and the k loop is long: then per-tile latency, not LDS throughput, sets the pace
-    const int t64 = (int)((K + BK - 1) / BK);
-    int kgs = (items < 512 && t64 >= 8) ? 2 : 1;
-    if (tiny) kgs = 4;
-    // wave specialisation pays when few workgroups are resident per CU (nothing else hides the staging phases); measured
-    // on AlexNet bs=512 E=10: conv3 31.7 -> 23.2 us, conv4 46.5 -> 33.3, conv5 18.2 -> 16.8, but conv1 / conv2 (1280+
-    // workgroups, or the 64x256 shape whose two stages leave one workgroup per CU) 20-30 % slower
-    bool ws = shape == 22 && items <= 1024;
-    if (ws) kgs = 1;
+    a.Ntiles = p.f.Ntiles; a.G = p.f.G; a.nbt = p.f.nbt; a.Mtiles = p.f.Mtiles; a.per_xcd = p.f.per_xcd;
+    a.px_run = p.f.px_run; a.pool = p.f.pool; a.y_c8 = p.f.y_c8; a.y_f32 = p.f.y_f32;
     hipStream_t st = (hipStream_t)stream;
-    return out_f32 ? launch_shape<true>(a, shape, kgs, ws, blocks, st) : launch_shape<false>(a, shape, kgs, ws, blocks, st);
+    const int64_t blocks = p.blocks;
+    const int nt = p.nt, ks = p.ks;                   // small-k forms: (32-channel tiles, 16-k steps) of the instantiation
+    switch (p.form) {
+    case BBB_BF16_FORM_SMALLK_POOLWIN:
+        return ks == 2 ? launch_smallk_poolwin<2>(a, blocks, p.smem_bytes, st)
+             : ks == 5 ? launch_smallk_poolwin<5>(a, blocks, p.smem_bytes, st) : launch_smallk_poolwin<8>(a, blocks, p.smem_bytes, st);
+    case BBB_BF16_FORM_SMALLK_POOL:
+        if (nt == 1) return ks == 2 ? launch_smallk_pool<1, 2>(a, blocks, st) : ks == 5 ? launch_smallk_pool<1, 5>(a, blocks, st) : launch_smallk_pool<1, 8>(a, blocks, st);
+        return ks == 2 ? launch_smallk_pool<2, 2>(a, blocks, st) : ks == 5 ? launch_smallk_pool<2, 5>(a, blocks, st) : launch_smallk_pool<2, 8>(a, blocks, st);
+    case BBB_BF16_FORM_STRIP8:
+        return launch_strip8<3, 5, 4>(a, blocks, st);
+    case BBB_BF16_FORM_SMALLK:
+        if (nt == 1) return ks == 2 ? launch_smallk<1, 2>(a, blocks, st) : ks == 5 ? launch_smallk<1, 5>(a, blocks, st) : launch_smallk<1, 8>(a, blocks, st);
+        return ks == 2 ? launch_smallk<2, 2>(a, blocks, st) : ks == 5 ? launch_smallk<2, 5>(a, blocks, st) : launch_smallk<2, 8>(a, blocks, st);
+    case BBB_BF16_FORM_FEWOUT:
+        return a.Cout <= 10 ? launch_fewout<10>(a, blocks, st) : launch_fewout<16>(a, blocks, st);
+    default:
+        return out_f32 ? launch_shape<true>(a, p.tile.shape, p.tile.kgs, p.tile.ws, blocks, st)
+                       : launch_shape<false>(a, p.tile.shape, p.tile.kgs, p.tile.ws, blocks, st);
+    }
+}
+
+extern "C" int bbb_conv2d_chwn_bf16_dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, int out_w, uint32_t flags,
+                                               int32_t* shape, int32_t* k_groups, int32_t* wave_specialised) {
+    bf16_plan::DgradPlan p;
+    if (const int rc = bf16_plan::dgrad_plan(d, up_h, up_w, out_h, out_w, flags, 0, &p)) return rc;
+    if (shape) *shape = p.tile.shape;
+    if (k_groups) *k_groups = p.tile.kgs;
+    if (wave_specialised) *wave_specialised = p.tile.ws ? 1 : 0;
+    return 0;
 }
 
 // The input gradient of a strided layer on bf16 storage: the transposed form of the general kernel (pconv_bf16_kernel, TR).  The
 // argument contract of bbb_conv2d_chwn_dgrad plus the bf16 forward's operand checks; everything is validated before any launch.
 extern "C" int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* g_pre, const void* w_flipped, void* dx, int up_h,
                                           int up_w, int out_h, int out_w, uint32_t flags, void* stream) {
-    if (d == nullptr) return BBB_EINVAL;
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->pad_h < 0 ||
-        d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 || d->draws <= 0 || up_h <= 0 || up_w <= 0 || out_h <= 0 || out_w <= 0)
-        return BBB_EINVAL;
-    // d describes the stride-1 launch on the flipped rows; the layer's stride travels as the upsampling factors
-    if (d->stride_h != 1 || d->stride_w != 1) return BBB_EINVAL;
-    if (up_h == 1 && up_w == 1) return BBB_EINVAL;          // a stride-1 layer's gradient is bbb_conv2d_chwn_bf16_fwd: one way to compute it
-    if (d->act != 0 || d->pool != 0 || d->w_tap_major != 0 || d->w_row_pitch != 0 || d->unit_div != 0 || d->unit_off != 0 ||
-        d->x_unit_mod != 0 || d->x_unit_div != 0 || d->x_unit_off != 0 || d->b_offset != 0)
-        return BBB_EINVAL;
-    if (d->x_draw_stride < 0 || d->w_draw_stride < 0) return BBB_EINVAL;
-    if ((flags & ~BBB_BF16_W_TAP_MAJOR) != 0) return BBB_EINVAL;
-    const bool tap_major = (flags & BBB_BF16_W_TAP_MAJOR) != 0;
-    if (d->batch % 8 != 0) return BBB_ESHAPE;               // rows of 16-byte vectors of 8 bf16 images
-    if (tap_major && d->cin % 8 != 0) return BBB_ESHAPE;    // a 16-byte weight vector must not straddle two taps
-    // (out_h, out_w) must be a map whose forward (padding p = d (k - 1) - q >= 0, stride up) gives exactly the g map of d
-    const int fph = d->dil_h * (d->kh - 1) - d->pad_h, fpw = d->dil_w * (d->kw - 1) - d->pad_w;
-    if (fph < 0 || fpw < 0) return BBB_ESHAPE;
-    const int64_t nh = (int64_t)out_h + 2 * fph - (int64_t)d->dil_h * (d->kh - 1) - 1;
-    const int64_t nw = (int64_t)out_w + 2 * fpw - (int64_t)d->dil_w * (d->kw - 1) - 1;
-    if (nh < 0 || nw < 0 || nh / up_h + 1 != d->h || nw / up_w + 1 != d->w) return BBB_ESHAPE;
-    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
-    const int64_t Kp = (K + 7) & ~(int64_t)7;
-    if (K >= (1 << 24)) return BBB_ESHAPE;                  // float-reciprocal k decode is exact below 2^24
-    // per-draw slabs are addressed through 32-bit buffer offsets (as in the forward's checks)
-    const int64_t g_bytes = (int64_t)d->cin * d->h * d->w * d->batch * 2, dx_bytes = (int64_t)d->cout * out_h * out_w * d->batch * 2;
-    if (g_bytes > 0xFFFE0000LL || dx_bytes > 0xFFFE0000LL || ((int64_t)d->cout + 64) * Kp * 2 > 0x7FFFFFFFLL ||
-        (int64_t)d->batch * 2 > 0x0FFFFFFFLL)
-        return BBB_ESHAPE;
-    const uint32_t x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 2u) & ~15u;
-    if (g_bytes > (int64_t)x_inv) return BBB_ESHAPE;
-    if (g_pre == nullptr || w_flipped == nullptr || dx == nullptr) return BBB_EINVAL;
-    if ((((uintptr_t)g_pre | (uintptr_t)w_flipped | (uintptr_t)dx) & 15u) != 0) return BBB_EALIGN;
-    if ((d->x_draw_stride & 7) != 0 || (d->w_draw_stride & 7) != 0) return BBB_EALIGN;
+    const int ptr_rc = (g_pre == nullptr || w_flipped == nullptr || dx == nullptr) ? BBB_EINVAL
+                     : ((((uintptr_t)g_pre | (uintptr_t)w_flipped | (uintptr_t)dx) & 15u) != 0 ? BBB_EALIGN : 0);
+    bf16_plan::DgradPlan p;
+    if (const int rc = bf16_plan::dgrad_plan(d, up_h, up_w, out_h, out_w, flags, ptr_rc, &p)) return rc;
     PConvArgs a = {};
+    bf16_plan::fill_geometry(a, d, p.g, (flags & BBB_BF16_W_TAP_MAJOR) != 0);
     a.x = reinterpret_cast<const float*>(g_pre); a.w = reinterpret_cast<const float*>(w_flipped); a.y = reinterpret_cast<float*>(dx);
-    a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
-    a.sh = 1; a.sw = 1; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = out_h; a.Wo = out_w; a.K = (int32_t)K; a.Kp = (int32_t)Kp; a.khkw = d->kh * d->kw;
-    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride;
-    a.y_ds = (int64_t)d->cout * out_h * out_w * d->batch;
-    a.x_inv = x_inv;
-    a.wtap = tap_major ? 1 : 0;
+    a.w_ds = d->w_draw_stride;
     a.up_h = up_h; a.up_w = up_w;
-    a.tstep_h = up_h / gcd_i(up_h, d->dil_h); a.tstep_w = up_w / gcd_i(up_w, d->dil_w);
-    // tile shape, k-groups and wave specialisation as bbb_conv2d_chwn_bf16_fwd's general path picks them -- with the k-tile count
-    // of the LONGEST contraction a pixel can have: tap-major rows visit at most ceil(k / tstep) taps per axis (counting the full
-    // row would hand k-groups nothing), reference-order rows run over the full row.  Never the small-k, few-output, strip or
-    // pooled kernels, and without the four-k-group form (launch_dgrad_shape).
-    auto waste = [](int n, int t) { return (double)(((n + t - 1) / t) * t) / (double)n; };
-    const double c22 = 256.0 * waste(a.Cout, 128) * waste(a.B, 128);
-    const double c14 = 288.0 * waste(a.Cout, 64) * waste(a.B, 256);
-    const double c12 = 320.0 * waste(a.Cout, 64) * waste(a.B, 128);
-    const int shape = (c22 <= c14 && c22 <= c12) ? 22 : (c14 <= c12 ? 14 : 12);
-    const int64_t kmax = tap_major ? (int64_t)a.Cin * ((a.kh + a.tstep_h - 1) / a.tstep_h) * ((a.kw + a.tstep_w - 1) / a.tstep_w) : K;
-    const int t64 = (int)((kmax + BK - 1) / BK);
-    const int64_t pixels = (int64_t)out_h * out_w;
-    const int bn = shape == 22 ? 128 : 64, bm = shape == 14 ? 256 : 128;
-    a.Ntiles = (a.Cout + bn - 1) / bn;
-    a.G = a.Ntiles * d->draws;
-    a.nbt = (a.B + bm - 1) / bm;
-    const int64_t mt = pixels * a.nbt;
-    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mt;
-    const int64_t items = (int64_t)a.G * mt;
-    const int64_t per = (items + 7) / 8;
-    const int64_t blocks = 8 * per;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
-    int kgs = (items < 512 && t64 >= 8) ? 2 : 1;
-    const bool ws = shape == 22 && items <= 1024;
-    if (ws) kgs = 1;
-    return launch_dgrad_shape(a, shape, kgs, ws, blocks, (hipStream_t)stream);
+    a.tstep_h = p.tstep_h; a.tstep_w = p.tstep_w;
+    a.Ntiles = p.grid.Ntiles; a.G = p.grid.G; a.nbt = p.grid.nbt; a.Mtiles = p.grid.Mtiles; a.per_xcd = p.grid.per_xcd;
+    return launch_dgrad_shape(a, p.tile.shape, p.tile.kgs, p.tile.ws, p.grid.blocks, (hipStream_t)stream);
 }
 
 extern "C" int bbb_maxpool_chwn_bf16(const void* x, void* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream) {

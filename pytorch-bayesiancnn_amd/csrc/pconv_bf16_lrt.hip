@@ -28,6 +28,7 @@
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
 #include "pconv_args.h"
+#include "pconv_bf16_plan.h"
 #include "smem_attr.h"
 
 namespace {
@@ -38,9 +39,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int BK = 64;
-constexpr int LDWB = BK + 8;             // weight row pitch (elements): 144 B
-constexpr int KCH = 256;                 // k entries per decode chunk and k-group
+using bf16_plan::BK;                     // (k per tile, weight row pitch, k per decode chunk and k-group: pconv_bf16_plan.h)
+using bf16_plan::LDWB;
+using bf16_plan::KCH;
 constexpr int TPC = KCH / BK;
 
 __device__ __forceinline__ uint16_t f2bf(float v) {              // round to nearest even (v_cvt_pk_bf16_f32)
@@ -400,30 +401,20 @@ __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16
     }
 }
 
+// (two weight tiles per stage, W_mu and sigma^2: launch_cfg, smem_attr.h)
 template <bool OUT_F32, int WN, int WM, int KG, bool WS>
-int launch_cfg(const PConvArgs& a, int64_t blocks, hipStream_t st) {
-    constexpr int kStageB = (BK * (64 * WM + 32) + 2 * 64 * WN * LDWB) * 2;
-    constexpr int kSmem = KG * (WS ? 2 : 1) * kStageB + 4 * KCH * KG * 4;
-    constexpr int kRed = (KG - 1) * 64 * (64 * WN * WM) * 4;      // one moment at a time
-    static_assert(kRed <= KG * kStageB, "reduction buffer must fit in the stage memory");
-    static_assert(kSmem <= 160 * 1024, "LDS");
-    static_assert(WN * WM * 64 * 72 * 2 <= kStageB, "epilogue staging must fit in one stage");
-    static_assert(64 * WN * WM * KG + (WS ? 256 : 0) <= 512, "256 registers per wave");
-    static SmemAttrState attr_state;
-    if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(&pconv_bf16_lrt_kernel<OUT_F32, WN, WM, KG, WS>), kSmem, attr_state)) return rc;
-    hipLaunchKernelGGL((pconv_bf16_lrt_kernel<OUT_F32, WN, WM, KG, WS>), dim3((unsigned)blocks),
-                       dim3(64 * WN * WM * KG + (WS ? 256 : 0)), kSmem, st, a);
-    return (int)hipGetLastError();
+int launch_lrt(const PConvArgs& a, int64_t blocks, hipStream_t st) {
+    return launch_cfg<&pconv_bf16_lrt_kernel<OUT_F32, WN, WM, KG, WS>, WN, WM, KG, WS, 2>(a, blocks, st);
 }
 
 template <bool OUT_F32>
 int launch_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t blocks, hipStream_t st) {
     if (shape == 22) {
-        if (ws) return launch_cfg<OUT_F32, 2, 2, 1, true>(a, blocks, st);
-        return kgs == 2 ? launch_cfg<OUT_F32, 2, 2, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 2, 2, 1, false>(a, blocks, st);
+        if (ws) return launch_lrt<OUT_F32, 2, 2, 1, true>(a, blocks, st);
+        return kgs == 2 ? launch_lrt<OUT_F32, 2, 2, 2, false>(a, blocks, st) : launch_lrt<OUT_F32, 2, 2, 1, false>(a, blocks, st);
     }
-    if (shape == 14) return kgs == 2 ? launch_cfg<OUT_F32, 1, 4, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 1, 4, 1, false>(a, blocks, st);
-    return kgs == 2 ? launch_cfg<OUT_F32, 1, 2, 2, false>(a, blocks, st) : launch_cfg<OUT_F32, 1, 2, 1, false>(a, blocks, st);
+    if (shape == 14) return kgs == 2 ? launch_lrt<OUT_F32, 1, 4, 2, false>(a, blocks, st) : launch_lrt<OUT_F32, 1, 4, 1, false>(a, blocks, st);
+    return kgs == 2 ? launch_lrt<OUT_F32, 1, 2, 2, false>(a, blocks, st) : launch_lrt<OUT_F32, 1, 2, 1, false>(a, blocks, st);
 }
 
 // y[e] = bf16(act(act_mu + sqrt(act_var) * eps[e])) for E draws of ONE pair of fp32 moments: the bf16-output form of
@@ -542,35 +533,12 @@ extern "C" int bbb_lrt_sample_chwn_bf16(const float* act_mu, const float* act_va
 
 extern "C" int bbb_lrt_conv2d_chwn_bf16_plan(const bbb_conv_desc_t* d, uint32_t flags, int32_t* shape, int32_t* k_groups,
                                              int32_t* wave_specialised) {
-    if (d == nullptr || d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 || d->draws <= 0)
-        return BBB_EINVAL;
     (void)flags;
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
-    // tile shape: LDS-pipe cycles per unit of useful work including the waste of ragged channel / image tiles, as in
-    // bbb_conv2d_chwn_bf16_fwd: 128x128 -> 256, 64x256 -> 288, 64x128 (two waves) -> 320
-    auto waste = [](int n, int t) { return (double)(((n + t - 1) / t) * t) / (double)n; };
-    const double c22 = 256.0 * waste(d->cout, 128) * waste(d->batch, 128);
-    const double c14 = 288.0 * waste(d->cout, 64) * waste(d->batch, 256);
-    const double c12 = 320.0 * waste(d->cout, 64) * waste(d->batch, 128);
-    int sh = (c22 <= c14 && c22 <= c12) ? 22 : (c14 <= c12 ? 14 : 12);
-    // Two k-groups (each with its own stage and loads in flight, summed in group order) for layers that are few workgroups with
-    // long rows whatever the launch: at most 16 (pixel, 64-channel tile) groups and at least 16 tiles of 64 k.  A property of the
-    // LAYER's geometry, because the number of groups is the one launch choice that changes the summation order.
-    const int t64 = (int)((K + BK - 1) / BK);
-    const int kgs = (t64 >= 16 && (int64_t)ho * wo * ((d->cout + 63) / 64) <= 16) ? 2 : 1;
-    const int64_t items12 = (int64_t)d->draws * ho * wo * ((d->cout + 63) / 64) * ((d->batch + 127) / 128);
-    if (kgs == 2 && items12 < 256) sh = 12;                       // nothing but serial k loops: the small tile gives more of them
-    const int bn = sh == 22 ? 128 : 64, bm = sh == 14 ? 256 : 128;
-    const int64_t items = (int64_t)d->draws * ((d->cout + bn - 1) / bn) * ho * wo * ((d->batch + bm - 1) / bm);
-    // wave specialisation pays when few workgroups are resident per CU (measured on the parent kernel); same bits as one group
-    const bool ws = sh == 22 && kgs == 1 && items <= 1024;
-    if (shape) *shape = sh;
-    if (k_groups) *k_groups = kgs;
-    if (wave_specialised) *wave_specialised = ws ? 1 : 0;
+    bf16_plan::LrtPlan p;
+    if (const int rc = bf16_plan::lrt_plan(d, &p)) return rc;
+    if (shape) *shape = p.tile.shape;
+    if (k_groups) *k_groups = p.tile.kgs;
+    if (wave_specialised) *wave_specialised = p.tile.ws ? 1 : 0;
     return 0;
 }
 
@@ -579,8 +547,8 @@ extern "C" int bbb_lrt_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void
                                             uint64_t seed, uint32_t call0, uint32_t stream_id, int sample, const uint32_t* call_dev,
                                             uint32_t flags, void* stream) {
     const bool out_f32 = (flags & BBB_BF16_OUT_F32) != 0, tap_major = (flags & BBB_BF16_W_TAP_MAJOR) != 0;
-    int32_t shape = 0, kgs = 0, wsi = 0;
-    if (const int rc = bbb_lrt_conv2d_chwn_bf16_plan(d, flags, &shape, &kgs, &wsi)) return rc;
+    bf16_plan::LrtPlan p;
+    if (const int rc = bf16_plan::lrt_plan(d, &p)) return rc;
     if (x == nullptr || w_mu == nullptr || w_var == nullptr) return BBB_EINVAL;
     if ((flags & ~(BBB_BF16_OUT_F32 | BBB_BF16_W_TAP_MAJOR)) != 0 || d->act < 0 || d->act > 2) return BBB_EINVAL;
     if ((b_mu == nullptr) != (b_var == nullptr) || (act_mu_out == nullptr) != (act_var_out == nullptr)) return BBB_EINVAL;
@@ -592,50 +560,28 @@ extern "C" int bbb_lrt_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void
     if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && d->x_unit_off >= d->x_unit_div) ||
         (d->x_unit_div <= 1 && d->x_unit_off != 0))
         return BBB_EINVAL;
-    if (d->batch % 8 != 0) return BBB_ESHAPE;        // rows of 16-byte vectors of 8 bf16 images
-    if (tap_major && d->cin % 8 != 0) return BBB_ESHAPE;   // a 16-byte weight vector must not straddle two taps
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
-    const int64_t Kp = (K + 7) & ~(int64_t)7;
-    if (K >= (1 << 24)) return BBB_ESHAPE;           // float-reciprocal k decode is exact below 2^24
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 2 > 0xFFFE0000LL || (int64_t)d->cout * ho * wo * d->batch * 4 > 0x7FFE0000LL ||
-        ((int64_t)d->cout + 128) * Kp * 2 > 0x7FFFFFFFLL || (int64_t)d->batch * 2 > 0x0FFFFFFFLL)
-        return BBB_ESHAPE;
-    const uint32_t x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 2u) & ~15u;   // a ragged last tile reaches < 512 columns past the row
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 2 > (int64_t)x_inv) return BBB_ESHAPE;
+    if (const int rc = bf16_plan::vector_rows(d, tap_major)) return rc;
+    bf16_plan::Geom g;
+    if (const int rc = bf16_plan::slab_limits(d, p.ho, p.wo, bf16_plan::kLrtLimits, &g)) return rc;
     if ((((uintptr_t)x | (uintptr_t)w_mu | (uintptr_t)w_var) & 15u) != 0 || ((uintptr_t)y & (out_f32 ? 3u : 15u)) != 0 ||
         (((uintptr_t)b_mu | (uintptr_t)b_var | (uintptr_t)act_mu_out | (uintptr_t)act_var_out) & 3u) != 0)
         return BBB_EALIGN;
     if ((d->x_draw_stride & 7) != 0) return BBB_EALIGN;
+    bf16_plan::TileGrid t = {};
+    if (const int rc = bf16_plan::tile_grid(p.tile.shape, p.work, &t)) return rc;
     PConvArgs a = {};
-    a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
-    a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = ho; a.Wo = wo; a.K = (int32_t)K; a.Kp = (int32_t)Kp; a.khkw = d->kh * d->kw; a.act = d->act;
-    a.x_ds = d->x_draw_stride;
-    a.y_ds = (int64_t)d->cout * ho * wo * d->batch;
+    bf16_plan::fill_geometry(a, d, g, tap_major);
     a.x = reinterpret_cast<const float*>(x);
     a.w = reinterpret_cast<const float*>(w_mu); a.w2 = reinterpret_cast<const float*>(w_var);
     a.bias = b_mu; a.bias2 = b_var;
     a.y = reinterpret_cast<float*>(y); a.y_mu = act_mu_out; a.y_var = act_var_out;
-    a.x_inv = x_inv;
-    a.wtap = tap_major ? 1 : 0;
     a.x_div = d->x_unit_div; a.x_off = d->x_unit_off;
     a.b_off = d->b_offset;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.call0 = call0; a.stream_id = stream_id;
     a.sample = sample ? 1 : 0;
     a.call_dev = call_dev;
-    const int bn = shape == 22 ? 128 : 64, bm = shape == 14 ? 256 : 128;
-    a.Ntiles = (a.Cout + bn - 1) / bn;
-    a.G = a.Ntiles * d->draws;
-    a.nbt = (a.B + bm - 1) / bm;
-    const int64_t mt = (int64_t)ho * wo * a.nbt;
-    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mt;
-    const int64_t per = ((int64_t)a.G * mt + 7) / 8;
-    const int64_t blocks = 8 * per;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
+    a.Ntiles = t.Ntiles; a.G = t.G; a.nbt = t.nbt; a.Mtiles = t.Mtiles; a.per_xcd = t.per_xcd;
     hipStream_t st = (hipStream_t)stream;
-    return out_f32 ? launch_shape<true>(a, shape, kgs, wsi != 0, blocks, st) : launch_shape<false>(a, shape, kgs, wsi != 0, blocks, st);
+    return out_f32 ? launch_shape<true>(a, p.tile.shape, p.tile.kgs, p.tile.ws, t.blocks, st)
+                   : launch_shape<false>(a, p.tile.shape, p.tile.kgs, p.tile.ws, t.blocks, st);
 }

@@ -129,26 +129,27 @@ def _check_bf16(name, tier, got, want, mag=None, K=1):
 # (test_host_cpu.py::test_bf16_train_fuzz_branch_coverage)
 # ---------------------------------------------------------------------------------------------------------------------------
 def gemm_form(B, cin, H, W, cout, kh, kw, s, p, d, draws, out_f32, tap_major):
-    """The dispatcher's choice for one launch (no pool, no c8 layouts: what the backward launches), restated from
-    bbb_conv2d_chwn_bf16_fwd in csrc/pconv_bf16.hip.  Returns a set of tags."""
+    """The dispatcher's choice for one launch (no pool, no c8 layouts: what the backward launches), restated independently of
+    the library's plan (fwd_plan in csrc/pconv_bf16_plan.h; tests/test_bf16_plan_cpu.py holds ops.bf16_fwd_plan against it).
+    Returns a set of tags."""
     ho, wo = _out_hw(H, W, kh, kw, s, p, d)
     K = cin * kh * kw
     Kp = (K + 7) & ~7
-    # pconv_bf16.hip:1663  if (!tap_major && !out_f32 && Kp <= 128 && (int64_t)ho * wo >= 16)  -> pconv_bf16_smallk_kernel
+    # fwd_plan, BBB_BF16_FORM_SMALLK  if (!tap_major && !out_f32 && Kp <= 128 && (int64_t)ho * wo >= 16)  -> pconv_bf16_smallk_kernel
     if not tap_major and not out_f32 and Kp <= 128 and ho * wo >= 16:
         return {"smallk"}
-    # pconv_bf16.hip:1682  if (a.Cout <= 16 && K >= 512 && a.kh == 1 && a.kw == 1 && a.H == 1 && a.W == 1 && a.ph == 0 && a.pw == 0)
+    # fwd_plan, BBB_BF16_FORM_FEWOUT  cout <= 16, K >= 512, a 1 x 1 layer on a one-pixel map without padding
     if cout <= 16 and K >= 512 and kh == 1 and kw == 1 and H == 1 and W == 1 and p == (0, 0):
         return {"fewout-f32" if out_f32 else "fewout-bf16"}
 
     def waste(n, t):
         return -(-n // t) * t / n
-    # pconv_bf16.hip:1697-1700  the tile shape by LDS cycles per useful unit
+    # tile_shape: the tile shape by LDS cycles per useful unit
     c22 = 256.0 * waste(cout, 128) * waste(B, 128)
     c14 = 288.0 * waste(cout, 64) * waste(B, 256)
     c12 = 320.0 * waste(cout, 64) * waste(B, 128)
     shape = 22 if (c22 <= c14 and c22 <= c12) else (14 if c14 <= c12 else 12)
-    # pconv_bf16.hip:1705-1708  tiny: >= 16 k tiles of 64 and < 256 (64 x 128) items -> shape 12 with four k-groups
+    # fwd_tile_rule  tiny: >= 16 k tiles of 64 and < 256 (64 x 128) items -> shape 12 with four k-groups
     t64 = -(-K // 64)
     items12 = draws * ho * wo * -(-cout // 64) * -(-B // 128)
     tiny = t64 >= 16 and items12 < 256
@@ -156,7 +157,7 @@ def gemm_form(B, cin, H, W, cout, kh, kw, s, p, d, draws, out_f32, tap_major):
         shape = 12
     bn, bm = (128 if shape == 22 else 64), (256 if shape == 14 else 128)
     items = draws * ho * wo * -(-cout // bn) * -(-B // bm)
-    # pconv_bf16.hip:1724-1730  a second k-group for small launches with long k loops; wave specialisation for 128 x 128 tiles
+    # small_launch_rule  a second k-group for small launches with long k loops; wave specialisation for 128 x 128 tiles
     kgs = 2 if (items < 512 and t64 >= 8) else 1
     if tiny:
         kgs = 4
