@@ -41,18 +41,26 @@ def _pack_w(w, tap_major=False):
 
 
 CONV_CASES = [
-    # B, Cin, H, W, Cout, k, stride, pad, dil, E, x_shared
-    (16, 3, 32, 32, 64, 11, 4, 5, 1, 2, True),      # AlexNet conv1: K = 363 (padded rows), one channel tile
-    (24, 3, 16, 16, 32, 5, 1, 2, 1, 1, True),       # 3Conv3FC conv1: K = 75, B not a multiple of 128
-    (136, 6, 9, 7, 70, 3, 1, 1, 1, 2, False),       # two batch tiles + ragged tile, Cout not a multiple of 64
-    (8, 16, 6, 6, 130, 3, 2, 1, 2, 3, False),       # stride + dilation, three channel tiles
-    (8, 1, 12, 12, 6, 5, 1, 0, 1, 1, True),         # LeNet conv1: K = 25
-    (40, 520, 1, 1, 10, 1, 1, 0, 1, 2, False),      # linear layer, K = 520 (more than two 256-entry decode chunks)
-    (8, 64, 4, 4, 64, 5, 1, 2, 1, 1, True),         # K = 1600: seven decode chunks
-    (16, 24, 5, 7, 40, 3, 1, 1, 1, 2, False),       # cin = 24: 64-k tiles straddle taps in the tap-major order
-    (264, 384, 2, 2, 256, 3, 1, 1, 1, 1, False),    # AlexNet conv4 shape: 4 of 9 taps in bounds
+    # B, Cin, H, W, Cout, k, stride, pad, dil, E, x_shared -- and the form ops.bf16_fwd_plan reports (CONV_FORMS below holds it)
+    (16, 3, 32, 32, 64, 11, 4, 5, 1, 2, True),      # AlexNet conv1: K = 363 (padded rows), one channel tile: general (12,1)
+    (24, 3, 16, 16, 32, 5, 1, 2, 1, 1, True),       # 3Conv3FC conv1: K = 75, B not a multiple of 128: general (12,1); bf16 out: small-k
+    (136, 6, 9, 7, 70, 3, 1, 1, 1, 2, False),       # two batch tiles + ragged tile, Cout not a multiple of 64: general (22,1,ws); bf16 out: small-k
+    (8, 16, 6, 6, 130, 3, 2, 1, 2, 3, False),       # stride + dilation, three channel tiles: general (12,1)
+    (8, 1, 12, 12, 6, 5, 1, 0, 1, 1, True),         # LeNet conv1: K = 25: general (12,1); bf16 out: small-k
+    (40, 520, 1, 1, 10, 1, 1, 0, 1, 2, False),      # linear layer, K = 520 (more than two 256-entry decode chunks): few-output
+    (8, 64, 4, 4, 64, 5, 1, 2, 1, 1, True),         # K = 1600: seven decode chunks: general (12,4)
+    (16, 24, 5, 7, 40, 3, 1, 1, 1, 2, False),       # cin = 24: 64-k tiles straddle taps in the tap-major order: general (12,1)
+    (264, 384, 2, 2, 256, 3, 1, 1, 1, 1, False),    # AlexNet conv4 shape: 4 of 9 taps in bounds: general (12,4)
     (136, 1040, 1, 1, 10, 1, 1, 0, 1, 2, False),    # a classifier with a long row: ops.bf16_fwd_plan reports ("fewout", 0, 0, False)
 ]
+# ops.bf16_fwd_plan's answer per case: (fp32 out; bf16 out, reference-order rows; bf16 out, tap-major rows).  Asserted at the top of
+# the test, so that a change of the plan cannot move a case off the kernel its line names without this file noticing.
+_G12_1, _G12_4, _FEW = ("general", 12, 1, False), ("general", 12, 4, False), ("fewout", 0, 0, False)
+_SMALLK = ("smallk", 0, 0, False)
+CONV_FORMS = dict(zip(CONV_CASES, [
+    (_G12_1, _G12_1, None), (_G12_1, _SMALLK, None), (("general", 22, 1, True), _SMALLK, None), (_G12_1, _G12_1, _G12_1),
+    (_G12_1, _SMALLK, None), (_FEW, _FEW, _FEW), (_G12_4, _G12_4, _G12_4), (_G12_1, _G12_1, _G12_1), (_G12_4, _G12_4, _G12_4),
+    (_FEW, _FEW, _FEW)]))
 
 
 @pytest.mark.parametrize("B,Cin,H,W,Cout,k,s,p,d,E,xs", CONV_CASES)
@@ -60,6 +68,8 @@ CONV_CASES = [
 def test_conv_bf16_vs_oracle(env, B, Cin, H, W, Cout, k, s, p, d, E, xs, out_f32, tap_major):
     if tap_major and Cin % 8 != 0:
         pytest.skip("tap-major rows need cin % 8 == 0")
+    assert env["ops"].bf16_fwd_plan((E, Cin, H, W, B), Cout, (Cin, k, k), s, p, d, out_f32=out_f32, tap_major=tap_major) == \
+        CONV_FORMS[(B, Cin, H, W, Cout, k, s, p, d, E, xs)][0 if out_f32 else (2 if tap_major else 1)]
     torch.manual_seed(B * 7 + Cout)
     x = torch.randn(1 if xs else E, B, Cin, H, W, device="cuda")
     w = torch.randn(E, Cout, Cin, k, k, device="cuda") * 0.2
