@@ -95,6 +95,19 @@ int bbb_reparam_kl_fwd(const bbb_segment_t* segs, int nseg, int draws,
 /* Number of doubles of scratch bbb_reparam_kl_fwd needs for these segments, host-only helper. */
 int64_t bbb_reparam_partials(const bbb_segment_t* segs, int nseg);
 
+/* What bbb_reparam_kl_fwd launches for these segments (additive to ABI 13; host only, needs no device: tests, profiling): the entry's
+ * own plan, without the launch.  slots: 256-thread blocks resident at once (8 per compute unit); <= 0 = ask the current device as
+ * the launcher does.  *kernel: 0 = the fast kernel (every segment dense fp32 with on-chip noise), 1 = the generic one (external eps
+ * or bf16 rows).  *gpt: 16-byte groups per thread, 4 when the segments total more than 1024 * 16384 elements, else 1.  *nt: the
+ * fast kernel stores w non-temporally (gpt 4 or draws <= 16).  *chunks: (1024 * gpt)-element chunks = KL partials.  *n_small,
+ * *small_chunk0: when slots < chunks <= 3 * slots, draws > 1, gpt 1 and no tap-major segment, the last chunks % slots chunks (from
+ * *small_chunk0 on) run as one block per draw at the front of the grid, *n_small blocks in all; else 0 and *chunks.  *tm_blocks:
+ * blocks that write the fp32 tap-major segments (w_tm_cin), ahead of everything else.  *grid: blocks of a launch that wants the
+ * KL (the summing block included; one fewer without).  Returns what the launch entry returns for the same segments: 0, BBB_EINVAL,
+ * BBB_EALIGN, or BBB_ESHAPE when a count does not fit 32 bits.  Out-pointers may be NULL. */
+int bbb_reparam_kl_plan(const bbb_segment_t* segs, int nseg, int draws, int slots, int32_t* kernel, int32_t* gpt, int32_t* nt,
+                        int32_t* chunks, int32_t* n_small, int32_t* small_chunk0, int32_t* tm_blocks, int32_t* grid);
+
 /*
  * Backward of bbb_reparam_kl_fwd (what autograd derives for the reference):
  *   grad_mu  = sum_e gw[e] + gkl * (mu - mu0) / sigma^2

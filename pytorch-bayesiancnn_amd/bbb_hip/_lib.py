@@ -55,6 +55,7 @@ _SIGNATURES = {
     "bbb_reparam_kl_fwd": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_float, c_float, c_u64, c_u32, c_u32,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bbb_reparam_partials": (c_i64, [ctypes.POINTER(Segment), c_int]),
+    "bbb_reparam_kl_plan": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_int] + [ctypes.POINTER(c_i32)] * 8),
     "bbb_reparam_kl_bwd": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_float, c_float, c_u64, c_u32, c_u32,
                                    c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
     "bbb_adam_step": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,

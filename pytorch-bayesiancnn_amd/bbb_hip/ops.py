@@ -177,6 +177,34 @@ def reparam_kl_backward(mus, rhos, gws, gkl, prior_mu, prior_sigma, stream_ids, 
     return gmu, grho
 
 
+REPARAM_PLAN_FIELDS = ("kernel", "gpt", "nt", "chunks", "n_small", "small_chunk0", "tm_blocks", "grid")
+
+
+def reparam_plan(segs, draws, slots=0, nseg=None):
+    """What bbb_reparam_kl_fwd launches for `segs` (bbb_reparam_kl_plan: the launch entry's own plan, host only): a dict of
+    REPARAM_PLAN_FIELDS with kernel "fast" | "generic" and nt a bool.  segs: a ctypes array of Segment as the launch takes it, or a
+    sequence whose items are element counts or dicts of Segment fields (mu, rho and w then get a placeholder address that is never
+    read).  slots <= 0: the current device's resident blocks, as the launcher asks."""
+    if isinstance(segs, ctypes.Array):
+        arr, nseg = segs, (len(segs) if nseg is None else nseg)
+    else:
+        nseg = len(segs)
+        arr = (Segment * max(nseg, 1))()
+        for s, item in zip(arr, segs):
+            fields = {"n": item} if isinstance(item, int) else dict(item)
+            s.mu = s.rho = s.w = 16
+            for k, v in fields.items():
+                setattr(s, k, v)
+            if "draw_stride" not in fields:
+                s.draw_stride = s.n
+    out = [ctypes.c_int32(0) for _ in REPARAM_PLAN_FIELDS]
+    check(_lib.lib().bbb_reparam_kl_plan(arr, nseg, draws, slots, *[ctypes.byref(o) for o in out]), "bbb_reparam_kl_plan")
+    plan = {k: o.value for k, o in zip(REPARAM_PLAN_FIELDS, out)}
+    plan["kernel"] = ("fast", "generic")[plan["kernel"]]
+    plan["nt"] = bool(plan["nt"])
+    return plan
+
+
 def eps_dump(n, seed, call, stream_id, device, start=0):
     out = torch.empty(n, dtype=torch.float32, device=device)
     with on_device(out.device):

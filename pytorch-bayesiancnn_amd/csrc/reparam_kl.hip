@@ -15,11 +15,12 @@
 
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
+#include "reparam_kl_plan.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kChunk = kThreads * 4;                         // elements per (block, group slot): 4 per thread
+constexpr int kThreads = reparam_plan::kThreads;
+constexpr int kChunk = reparam_plan::kChunk;                 // elements per (block, group slot): 4 per thread
 // A KL partial slot that has not been published yet holds this bit pattern (an all-ones NaN; the scratch is filled with
 // 0xFF bytes once by the host, and every launch re-arms the slots it consumed).
 constexpr unsigned long long kUnpublished = 0xFFFFFFFFFFFFFFFFull;
@@ -75,7 +76,10 @@ __device__ __forceinline__ float kl_term(float mu, float sigma, float mu0, float
     return 0.5f * t;
 }
 
-// kl_term on four elements with packed math (same operations per element, same bits); returns the terms, unsummed.
+// kl_term on four elements with packed math; returns the terms, unsummed.  The same expression per element, but NOT always the same
+// bits: the compiler contracts a * a + b * b into fused multiply-adds in its own way for the packed and for the scalar form, and on
+// an MI355X the fast and the generic kernel's KL sums were measured one fp32 ulp apart (tests/test_gpu_reparam_sweep.py).  Each kernel
+// is bitwise reproducible on its own, and both stay inside the 1e-6 relative bound on the sum.
 __device__ __forceinline__ bbb_f32x4 kl_term4(bbb_f32x4 mu, bbb_f32x4 sigma, float mu0, float sig0, float l2s0, float is0, bool textbook) {
     using bbb::pk_fma;
     using bbb::pk_splat;
@@ -589,28 +593,11 @@ __global__ __launch_bounds__(kThreads) void eps_dump_kernel(float* out, int64_t 
     }
 }
 
+// The segment checks and the chunk walk are the plan's (reparam_kl_plan.h); this copies the descriptors next to them.
 int fill_args(ReparamArgs& a, const bbb_segment_t* segs, int nseg, int draws, bool bwd, int gpt = 1) {
-    if (segs == nullptr || nseg <= 0 || nseg > BBB_MAX_SEGMENTS || draws <= 0) return BBB_EINVAL;
-    int chunks = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const bbb_segment_t& g = segs[s];
-        if (g.mu == nullptr || g.rho == nullptr || g.n <= 0) return BBB_EINVAL;
-        if (g.draw_stride < g.n && draws > 1 && (g.w || g.eps)) return BBB_EINVAL;
-        if ((((uintptr_t)g.mu | (uintptr_t)g.rho | (g.w_row_len ? 0 : (uintptr_t)g.w) | (uintptr_t)g.sigma | (uintptr_t)g.eps) & 3u) != 0)
-            return BBB_EALIGN;
-        if (g.w_row_len != 0 && (bwd || g.w == nullptr || g.n % g.w_row_len != 0 || ((uintptr_t)g.w & 1u))) return BBB_EINVAL;
-        if (g.w_tm_cin != 0) {      // fp32 tap-major output: dense Philox-sampled fp32 segment, [rows][C][T] with C % 8 == 0, 16-byte aligned
-            if (bwd || g.w_row_len != 0 || g.w_taps < 2 || g.w_taps > 128 || g.w_tm_cin % 8 != 0 || g.w == nullptr || g.eps != nullptr ||
-                g.n % ((int64_t)g.w_tm_cin * g.w_taps) != 0)
-                return BBB_EINVAL;
-            if ((((uintptr_t)g.mu | (uintptr_t)g.rho | (uintptr_t)g.w) & 15u) != 0 || (g.draw_stride & 3) != 0) return BBB_EALIGN;
-        } else if (g.w_taps > 1 && (g.w_row_len == 0 || g.w_row_len % g.w_taps != 0)) return BBB_EINVAL;
-        a.seg[s] = g;
-        a.chunk_begin[s] = chunks;
-        chunks += (int)((g.n + (int64_t)kChunk * gpt - 1) / ((int64_t)kChunk * gpt));
-        (void)bwd;
-    }
-    for (int s = nseg; s <= BBB_MAX_SEGMENTS; ++s) a.chunk_begin[s] = chunks;
+    const int chunks = reparam_plan::segments(segs, nseg, draws, bwd, gpt, a.chunk_begin);
+    if (chunks < 0) return chunks;
+    for (int s = 0; s < nseg; ++s) a.seg[s] = segs[s];
     a.nseg = nseg;
     a.draws = draws;
     return chunks;
@@ -623,13 +610,6 @@ extern "C" int64_t bbb_reparam_partials(const bbb_segment_t* segs, int nseg) {
     int64_t chunks = 0;
     for (int s = 0; s < nseg; ++s) chunks += (segs[s].n + kChunk - 1) / kChunk;
     return chunks;
-}
-
-// The fast kernel applies when every segment is a dense fp32, Philox-sampled tensor (alignment is handled per segment).
-static bool fast_path_ok(const bbb_segment_t* segs, int nseg) {
-    for (int s = 0; s < nseg; ++s)
-        if (segs[s].eps != nullptr || segs[s].w_row_len != 0) return false;
-    return true;
 }
 
 // 256-thread blocks the current device keeps resident at once: 8 per CU (<= 64 VGPRs, 2 KB LDS; 32 waves per CU).
@@ -649,16 +629,24 @@ extern "C" int bbb_reparam_kl_fwd(const bbb_segment_t* segs, int nseg, int draws
                                   uint64_t seed, uint32_t call0, uint32_t flags, double* kl_partials, float* kl_out,
                                   double* kl_out64, const uint32_t* call_dev, void* stream) {
     ReparamArgs a = {};
-    int64_t total = 0;
-    if (segs != nullptr && nseg > 0 && nseg <= BBB_MAX_SEGMENTS)
-        for (int s = 0; s < nseg; ++s) total += segs[s].n;
-    const bool big = total > (int64_t)kChunk * 16384;               // > 16M elements: longer blocks, streaming stores
-    const int gpt = big ? 4 : 1;
-    const int chunks = fill_args(a, segs, nseg, draws, false, gpt);
-    if (chunks < 0) return chunks;
+    reparam_plan::Plan p;
+    int rc = reparam_plan::forward_shape(segs, nseg, draws, &p);
+    if (rc != 0) return rc;
     const bool want_kl = (kl_out != nullptr) || (kl_out64 != nullptr);
     if (want_kl && (kl_partials == nullptr || ((uintptr_t)kl_partials & 7u) != 0)) return BBB_EINVAL;
     if (!(prior_sigma > 0.0f)) return BBB_EINVAL;
+    rc = reparam_plan::forward_grid(&p, draws, p.kernel == 0 ? resident_blocks() : 0, want_kl);
+    if (rc != 0) return rc;
+    for (int s = 0; s < nseg; ++s) {
+        a.seg[s] = segs[s];
+        a.tm_cg[s] = p.tm_cg[s];
+    }
+    for (int s = 0; s <= BBB_MAX_SEGMENTS; ++s) {
+        a.chunk_begin[s] = p.chunk_begin[s];
+        a.tm_begin[s] = p.tm_begin[s];
+    }
+    a.nseg = nseg;
+    a.draws = draws;
     a.prior_mu = prior_mu;
     a.prior_sigma = prior_sigma;
     a.k0 = (uint32_t)seed;
@@ -669,61 +657,42 @@ extern "C" int bbb_reparam_kl_fwd(const bbb_segment_t* segs, int nseg, int draws
     a.out32 = kl_out;
     a.out64 = kl_out64;
     a.call_dev = call_dev;
-    a.n_chunks = chunks;
+    a.n_chunks = p.chunks;
+    a.tm_blocks = p.tm_blocks;
+    a.n_small = p.n_small;
+    a.small_chunk0 = p.small_chunk0;
+    a.sum_block = want_kl ? p.grid - p.tm_blocks - 1 : -1;      // the last block of the launch (counted behind the tap-major blocks)
     hipStream_t st = (hipStream_t)stream;
-    const dim3 block(kThreads);
-#ifdef BBB_FORCE_GENERIC_REPARAM     // timing experiments: the general kernel on inputs the fast one would take
-    const bool fast = false;
-#else
-    const bool fast = fast_path_ok(segs, nseg);
-#endif
-    if (fast) {
-        // tap-major segments: their draws come from extra blocks at the front of the grid (tm_block)
-        int tmb = 0;
-        for (int s = 0; s < nseg; ++s) {
-            a.tm_begin[s] = tmb;
-            a.tm_cg[s] = 0;
-            if (segs[s].w_tm_cin != 0) {
-                const int64_t rc_total = segs[s].n / segs[s].w_taps;
-                int64_t cg = (kChunk / (int)segs[s].w_taps) & ~7;
-                if (cg > rc_total) cg = rc_total;
-                a.tm_cg[s] = (int)cg;
-                const int64_t nb = (rc_total + cg - 1) / cg;
-                if (tmb + nb > 0x3fffffffLL) return BBB_ESHAPE;
-                tmb += (int)nb;
-            }
-        }
-        for (int s = nseg; s <= BBB_MAX_SEGMENTS; ++s) a.tm_begin[s] = tmb;
-        a.tm_blocks = tmb;
-        // A launch a little larger than one round of resident blocks (the model-sized case: 2137 chunks on 2048 slots) would
-        // run its excess blocks alone at the end, one wave per SIMD, for a whole 10-draw block time.  Instead the LAST
-        // `excess` chunks are cut into one block per draw and put FIRST in the grid: they finish early, the whole-chunk
-        // blocks behind them fill the freed slots, and the launch ends with every SIMD still sharing work.  (The block of
-        // draw 0 owns the chunk's KL partial and sigma output; partial indices = chunk indices, so the KL sum is unchanged.)
-        const int slots = resident_blocks();
-        int excess = 0;
-        if (gpt == 1 && draws > 1 && chunks > slots && chunks <= 3 * slots && tmb == 0) excess = chunks % slots;
-        a.n_small = excess * draws;
-        a.small_chunk0 = chunks - excess;
-        const int blocks = a.n_small + (chunks - excess);
-        a.sum_block = want_kl ? blocks : -1;
-        const dim3 grid(tmb + blocks + (want_kl ? 1 : 0));
-        // Store flavour of w (measured, AlexNet's 12 tensors, us per launch, plain / non-temporal): E=4 14.6 / 12.2, E=10
-        // 21.7 / 19.2, E=25 40.0 / 42.5 -- with plain stores the launch ends with up to 32 MB of dirty L2 lines to write back
-        // at the kernel boundary; streaming them out as they are produced wins until the launch is long enough to hide that.
-        const bool nt = big || draws <= 16;
-        if (big)     hipLaunchKernelGGL((reparam_kl_fast_kernel<4, true>), grid, block, 0, st, a);
-        else if (nt) hipLaunchKernelGGL((reparam_kl_fast_kernel<1, true>), grid, block, 0, st, a);
-        else         hipLaunchKernelGGL((reparam_kl_fast_kernel<1, false>), grid, block, 0, st, a);
+    const dim3 block(kThreads), grid(p.grid);
+    if (p.kernel == 0) {
+        if (p.gpt == 4)  hipLaunchKernelGGL((reparam_kl_fast_kernel<4, true>), grid, block, 0, st, a);
+        else if (p.nt)   hipLaunchKernelGGL((reparam_kl_fast_kernel<1, true>), grid, block, 0, st, a);
+        else             hipLaunchKernelGGL((reparam_kl_fast_kernel<1, false>), grid, block, 0, st, a);
     } else {
-        for (int s = 0; s < nseg; ++s)
-            if (segs[s].w_tm_cin != 0) return BBB_EINVAL;                 // tap-major outputs: Philox-sampled dense launches only
-        a.sum_block = want_kl ? chunks : -1;
-        const dim3 grid(chunks + (want_kl ? 1 : 0));
-        if (big) hipLaunchKernelGGL(reparam_kl_fwd_kernel<4>, grid, block, 0, st, a);
-        else     hipLaunchKernelGGL(reparam_kl_fwd_kernel<1>, grid, block, 0, st, a);
+        if (p.gpt == 4) hipLaunchKernelGGL(reparam_kl_fwd_kernel<4>, grid, block, 0, st, a);
+        else            hipLaunchKernelGGL(reparam_kl_fwd_kernel<1>, grid, block, 0, st, a);
     }
     return (int)hipGetLastError();
+}
+
+// What bbb_reparam_kl_fwd launches for these segments: the same plan, no launch.  Out-pointers may be NULL.
+extern "C" int bbb_reparam_kl_plan(const bbb_segment_t* segs, int nseg, int draws, int slots, int32_t* kernel, int32_t* gpt,
+                                   int32_t* nt, int32_t* chunks, int32_t* n_small, int32_t* small_chunk0, int32_t* tm_blocks,
+                                   int32_t* grid) {
+    reparam_plan::Plan p;
+    int rc = reparam_plan::forward_shape(segs, nseg, draws, &p);
+    if (rc != 0) return rc;
+    rc = reparam_plan::forward_grid(&p, draws, slots > 0 ? slots : (p.kernel == 0 ? resident_blocks() : 0), true);
+    if (rc != 0) return rc;
+    if (kernel) *kernel = p.kernel;
+    if (gpt) *gpt = p.gpt;
+    if (nt) *nt = p.nt;
+    if (chunks) *chunks = p.chunks;
+    if (n_small) *n_small = p.n_small;
+    if (small_chunk0) *small_chunk0 = p.small_chunk0;
+    if (tm_blocks) *tm_blocks = p.tm_blocks;
+    if (grid) *grid = p.grid;
+    return 0;
 }
 
 extern "C" int bbb_reparam_kl_bwd(const bbb_segment_t* segs, int nseg, int draws, float prior_mu, float prior_sigma,
