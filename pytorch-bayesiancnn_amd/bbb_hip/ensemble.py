@@ -1014,7 +1014,7 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     nll_loss(lse, target) * train_size + beta * kl is formed by the tail's own launches (ops.elbo_cb_autograd) and left in elbo[3];
     elbo[3] still None on return: the caller forms it.
     precision="bf16" with elbo (train.forward_loss(precision="bf16")) and autograd on: the bf16 training mode
-    (fast_train._MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing autograd."""
+    (fast_train.mc_logits_autograd -> _MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing autograd."""
     if precision == "bf16" and elbo is not None and torch.is_grad_enabled():
         if not (fuse_act and fast_autograd) or timers is not None or units is not None or int(groups) > 1 or share is not None or b_offset:
             raise _lib.BBBHipError("bf16 training runs on the batch-innermost autograd node only")

@@ -16,8 +16,16 @@ activated output; backward walks the layers in reverse with
                                        layer's contraction over (draw, channel) on the forward kernel + the bbb_input_grad_col2im
                                        gather; with frozen parameters the weight side above is skipped altogether,
 so no activation, pooling or convolution of the step runs through torch autograd.  What main_bayesian.py:43-58 does per batch:
-E forwards, KL, log_softmax / logmeanexp (the small tail stays in torch), ELBO, backward.
+E forwards, KL, log_softmax / logmeanexp, ELBO, backward -- on the training path the tail after the logits is HIP too
+(ops.elbo_cb_autograd: bbb_elbo_cb_fwd / bbb_elbo_cb_bwd); the entry points that return log-probabilities keep it in torch.
+
+Three nodes -- _MCForward (fp32), _MCForwardBF16 (bf16 storage), _MCForwardLRT (local reparameterisation) -- over one forward walk
+(_walk: layer / activation / pool pairing, the tape) and one backward schedule (_Schedule: which stream a layer's weight side runs
+on, the early fork, the join); _carry / _run_backward take the launch configuration and scratch scope from the forward to the
+backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weight side, its input gradient, its flips up front.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -113,319 +121,6 @@ def ws_shape(rec):
     return (E,) + tuple(m.W_mu.shape)
 
 
-class _MCForward(torch.autograd.Function):
-    """(x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (logits [E, C, B] batch-innermost, kl of one forward)."""
-
-    @staticmethod
-    def forward(ctx, cfg, x, *params):
-        from . import ensemble
-        _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
-        net, E, seed, call0 = cfg["net"], cfg["draws"], cfg["seed"], cfg["call0"]
-        mods = ensemble.flat_children(net)
-        layers = [m for m in mods if isinstance(m, _BBBLayer)]
-        mus, rhos, ids = [], [], []
-        for l in layers:
-            m, r, i = l._param_lists()
-            mus += [t.detach() for t in m]
-            rhos += [t.detach() for t in r]
-            ids += i
-        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
-        ws, _, kl = ops.reparam_kl_forward(mus, rhos, pm, ps, ids, seed, call0, draws=E)
-        B = x.shape[0]
-        h = ops.to_batch_innermost(x.detach()).unsqueeze(0)               # [1, C, H, W, B]
-        tape = []                                                          # per Bayesian layer, in forward order
-        li, i = 0, 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, _BBBLayer):
-                w, b = ws[2 * li], ws[2 * li + 1]
-                is_conv = isinstance(m, BBBConv2d)
-                geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
-                x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
-                w5 = w if is_conv else w.reshape(E, m.out_features, m.in_features, 1, 1)
-                act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
-                y = ops.conv2d_chwn_forward(x_in, w5, b, *geom, act=act)
-                rec = dict(layer=m, x=x_in, w=w5, y=y, act=act, geom=geom, pool=None, first=(li == 0))
-                if act is not None:
-                    i += 1
-                h = y
-                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d):
-                    pool = mods[i + 1]
-                    h = ops.maxpool_chwn(y, pool.kernel_size, pool.stride)
-                    rec["pool"] = (pool.kernel_size, pool.stride)
-                    i += 1
-                rec["out_shape"] = tuple(h.shape)
-                tape.append(rec)
-                li += 1
-            elif isinstance(m, nn.MaxPool2d):                              # a pool that does not follow a Bayesian layer: on the input
-                raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
-            elif isinstance(m, FlattenLayer):
-                h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
-            i += 1
-        logits = h.reshape(E, -1, B)
-        ctx.cfg, ctx.tape, ctx.meta = cfg, tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
-        ctx.launch_config = ops.current_config()              # backward runs on autograd's device thread: carry the modes along
-        ctx.scratch_token = ops.current_scratch_token()
-        ctx.x_nchw = x.detach()
-        ctx.versions = [(p, p._version) for p in params]      # backward re-reads the live (mu, rho): they must not have moved
-        return logits, kl
-
-    @staticmethod
-    def backward(ctx, g_logits, g_kl):
-        with ops.use_config(ctx.launch_config), ops.scratch_scope(token=ctx.scratch_token):
-            return _MCForward._backward(ctx, g_logits, g_kl)
-
-    @staticmethod
-    def _backward(ctx, g_logits, g_kl):
-        cfg, tape = ctx.cfg, ctx.tape
-        _check_versions(ctx.versions)
-        cfg["spent"] = True                                    # layers/_fused.py: no further draws are served from this graph
-        mus, rhos, ids, pm, ps, x_shape = ctx.meta
-        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-        B = x_shape[0]
-        # need_w False (frozen parameters: saliency maps, adversarial steps): no weight side at all -- no bias sums, weight gradients,
-        # im2col, parameter pass or side-stream forks; need_x: the first layer's input gradient (first_layer_input_grad) at the end
-        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        gws = [None] * len(mus)
-        dx = None
-        g = g_logits.contiguous() if g_logits is not None else None
-        # a layer's weight / bias gradients and its input gradient are independent: the former run on a side stream beside the latter
-        # (both are launches that leave the chip partly idle on their own); joined before the parameter pass's backward.  Tensors
-        # the side stream reads stay referenced in `keep` until the join (the allocator must not hand them out again before).
-        # (eager launches only: inside a captured step the forks cost more than the overlap gains -- 4.8 against 3.05 ms per step)
-        side = _side_stream(g.device) if (g is not None and need_w and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
-        main = torch.cuda.current_stream(g.device) if side is not None else None
-        keep = []
-        # the first layer's im2col depends on the batch alone: on a side stream NOW, beside the small last layers' launches, instead of
-        # in the tail of the chain where nothing else is left to run beside it
-        xk_first = [None]
-        r0 = tape[0]
-        if side is not None and g is not None and r0["x"].shape[1] % 4 != 0:
-            side.wait_stream(main)
-            xk_stream = side.current
-            with torch.cuda.stream(xk_stream):
-                xk_first[0] = ops.im2col_pbj(ctx.x_nchw, tuple(r0["w"].shape), *r0["geom"])
-            keep.append(xk_first[0])
-        # every layer's input-gradient weights (flipped, channel-transposed: they depend on the sampled weights alone) in ONE launch up
-        # front instead of one launch per layer on the chain -- for launch-bound steps (no side streams: captured, small).  A
-        # many-draw step keeps them on the chain: up front, even on the side stream, they cost it 40 us (2.45 -> 2.49 ms at 512 x 10,
-        # profiles/experiments/ab_flips_up_front.py)
-        w_flipped = {}
-        if flips_up_front[0] and side is None and g is not None and len(tape) > 1:
-            outs = ops.flip_transpose_w_multi([tape[li]["w"] for li in range(1, len(tape))])
-            w_flipped = {li: o for li, o in zip(range(1, len(tape)), outs)}
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            y, w5, x_in, act = rec["y"], rec["w"], rec["x"], rec["act"]
-            stride, padding, dilation = rec["geom"]
-            if g is None:
-                break
-            g = g.reshape(rec["out_shape"])
-            pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
-            if rec["pool"] is not None:
-                g_pre = ops.pool_act_backward_chwn(g, y, rec["pool"][0], rec["pool"][1], act, pad_planes=pad)
-            elif act is not None:
-                g_pre = ops.pool_act_backward_chwn(g, y, 0, 1, act, pad_planes=pad)
-            else:
-                g_pre = g
-            def weight_side(g_pre=g_pre, x_in=x_in, w5=w5, rec=rec, li=li, stride=stride, padding=padding, dilation=dilation):
-                gws[2 * li + 1] = ops.plane_sums(g_pre)                   # bias gradient [E, Cout]
-                Cin = x_in.shape[1]
-                if Cin % 4 == 0 or not rec["first"]:                     # (6-channel inputs etc.: padded to 8 inside)
-                    gw = ops.conv2d_chwn_weight_grad(g_pre, x_in, tuple(w5.shape), stride, padding, dilation)
-                else:
-                    # 3-channel first layer: its input is shared by all draws, so the draws stack into the GEMM's row dimension
-                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, tuple(w5.shape), stride, padding, dilation, xk=xk_first[0])
-                gws[2 * li] = gw.reshape(ws_shape(rec))
-
-            if side is not None and not rec["first"]:
-                keep.append(g_pre)
-                side.wait_stream(main)
-                with torch.cuda.stream(side.current):
-                    weight_side()
-            elif need_w:
-                if rec["first"] and xk_first[0] is not None:
-                    main.wait_stream(xk_stream)
-                weight_side()
-            if not rec["first"]:
-                g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li),
-                                               stride=stride)
-            else:
-                if need_x:
-                    dx = ops.first_layer_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), stride, padding, dilation).view(x_shape)
-                g = None
-        if side is not None:
-            for st_ in side.streams:
-                main.wait_stream(st_)
-        del keep
-        out = [None, dx]
-        if not need_w:
-            return tuple(out + [None] * (2 * len(mus)))
-        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        for a, b in zip(gmu, grho):
-            out += [a, b]
-        return tuple(out)
-
-
-class _MCForwardBF16(torch.autograd.Function):
-    """_MCForward in the bf16 storage mode (train.train_step(precision="bf16"); the arithmetic contract is DESIGN.md section 4.5):
-    (x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (fp32 logits [E, C, B] batch-innermost, fp32 kl of one forward).
-    Forward = the bf16 inference kernels with the pooling left unfused (the tape keeps every layer's pre-pool output): sampled
-    weights, the input and every hidden activated / pooled output stored as bf16, fp32 accumulation, fp32 logits and KL.  Tape:
-    each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the same walk as _MCForward._backward with
-      * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
-      * ops.plane_sums_bf16               bias gradients, the fp32 sum of that bf16 g_pre,
-      * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16 (a strided layer, admitted
-        under LaunchConfig.bf16_strided_train: the transposed launch on the same rows),
-      * ops.conv2d_chwn_weight_grad_bf16  wgrad on the bf16 GEMM with the roles swapped -> fp32,
-      * the first layer (3-channel input shared by every draw): ops.conv2d_chwn_weight_grad_shared_input on the fp32 kernel over
-        the fp32 values of the bf16 operands (a bf16 x bf16 product is exact in fp32: the same contraction),
-      * ops.reparam_kl_backward           unchanged (fp32)."""
-
-    @staticmethod
-    def forward(ctx, cfg, x, *params):
-        from . import ensemble
-        _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
-        net, E, seed, call0 = cfg["net"], cfg["draws"], cfg["seed"], cfg["call0"]
-        mods = ensemble.flat_children(net)
-        layers = [m for m in mods if isinstance(m, _BBBLayer)]
-        mus, rhos, ids = [], [], []
-        for l in layers:
-            m, r, i = l._param_lists()
-            mus += [t.detach() for t in m]
-            rhos += [t.detach() for t in r]
-            ids += i
-        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
-        kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E)
-        B = x.shape[0]
-        h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
-        tape = []
-        li, i = 0, 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, _BBBLayer):
-                w, b = ws[2 * li], ws[2 * li + 1]
-                is_conv = isinstance(m, BBBConv2d)
-                geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
-                x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
-                wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
-                ckk = wshape[1:]
-                act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
-                last = li == len(layers) - 1
-                if last and (act is not None or (i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d))):
-                    raise _lib.BBBHipError("bf16 training: the logits layer (fp32 output) must not be followed by an activation or a pool")
-                y = ops.conv2d_chwn_bf16_forward(x_in, w, b, ckk, *geom, act=act, out_f32=last,
-                                                 tap_major=is_conv and ops.bf16_tap_major(wshape))
-                rec = dict(layer=m, x=x_in, w=w, wshape=wshape, y=y, act=act, geom=geom, pool=None, first=(li == 0))
-                if act is not None:
-                    i += 1
-                h = y
-                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d):
-                    pool = mods[i + 1]
-                    h = ops.maxpool_chwn_bf16(y, pool.kernel_size, pool.stride)
-                    rec["pool"] = (pool.kernel_size, pool.stride)
-                    i += 1
-                rec["out_shape"] = tuple(h.shape)
-                tape.append(rec)
-                li += 1
-            elif isinstance(m, nn.MaxPool2d):
-                raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
-            elif isinstance(m, FlattenLayer):
-                h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
-            i += 1
-        logits = h.reshape(E, -1, B)
-        ctx.cfg, ctx.tape, ctx.meta = cfg, tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
-        ctx.launch_config = ops.current_config()
-        ctx.scratch_token = ops.current_scratch_token()
-        # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted)
-        ctx.x_nchw = x.detach().to(torch.bfloat16).to(torch.float32) if tape[0]["x"].shape[1] % 4 != 0 else None
-        ctx.versions = [(p, p._version) for p in params]
-        return logits, kl
-
-    @staticmethod
-    def backward(ctx, g_logits, g_kl):
-        with ops.use_config(ctx.launch_config), ops.scratch_scope(token=ctx.scratch_token):
-            return _MCForwardBF16._backward(ctx, g_logits, g_kl)
-
-    @staticmethod
-    def _backward(ctx, g_logits, g_kl):
-        cfg, tape = ctx.cfg, ctx.tape
-        _check_versions(ctx.versions)
-        cfg["spent"] = True
-        mus, rhos, ids, pm, ps, x_shape = ctx.meta
-        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-        gws = [None] * len(mus)
-        g = g_logits.contiguous() if g_logits is not None else None
-        # (as in _MCForward: weight / bias gradients on side streams beside the input gradients, eager launches only; tensors the side
-        # streams read stay referenced in `keep` until the join; the first layer's im2col on a side stream up front)
-        side = _side_stream(g.device) if (g is not None and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
-        main = torch.cuda.current_stream(g.device) if side is not None else None
-        keep = []
-        xk_first = [None]
-        r0 = tape[0]
-        shared0 = r0["x"].shape[1] % 4 != 0
-        if g is not None and shared0:
-            xk_stream = None
-            if side is not None:
-                side.wait_stream(main)
-                xk_stream = side.current
-                with torch.cuda.stream(xk_stream):
-                    xk_first[0] = ops.im2col_pbj(ctx.x_nchw, (E,) + r0["wshape"], *r0["geom"])
-                keep.append(xk_first[0])
-        # every layer's flipped input-gradient weight rows up front (captured / launch-bound steps, as in _MCForward)
-        w_flipped = {}
-        if flips_up_front[0] and side is None and g is not None:
-            w_flipped = {li: ops.flip_transpose_w_bf16(tape[li]["w"], tape[li]["wshape"]) for li in range(1, len(tape))}
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            if g is None:
-                break
-            y, w, x_in, act, wshape = rec["y"], rec["w"], rec["x"], rec["act"], rec["wshape"]
-            stride, padding, dilation = rec["geom"]
-            g = g.reshape(rec["out_shape"])
-            shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
-            k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
-            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
-                g_pre = g                                                 # already the bf16 output gradient
-            else:
-                g_pre = ops.pool_act_backward_chwn_bf16(g, y if y.dtype == torch.bfloat16 else None, k, s, act, out_f32=shared,
-                                                        pad_planes=shared)
-
-            def weight_side(g_pre=g_pre, x_in=x_in, rec=rec, li=li, shared=shared, stride=stride, padding=padding, dilation=dilation):
-                wsh = (E,) + rec["wshape"]
-                if shared:
-                    gws[2 * li + 1] = ops.plane_sums(g_pre)
-                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, stride, padding, dilation, xk=xk_first[0])
-                else:
-                    gws[2 * li + 1] = ops.plane_sums_bf16(g_pre)
-                    gw = ops.conv2d_chwn_weight_grad_bf16(g_pre, x_in, wsh, stride, padding, dilation)
-                gws[2 * li] = gw.reshape(ws_shape(rec))
-
-            if side is not None and not rec["first"]:
-                keep.append(g_pre)
-                side.wait_stream(main)
-                with torch.cuda.stream(side.current):
-                    weight_side()
-            else:
-                if rec["first"] and xk_first[0] is not None:
-                    main.wait_stream(xk_stream)
-                weight_side()
-            if not rec["first"]:
-                g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
-                                                    w_flipped=w_flipped.get(li), stride=stride)
-            else:
-                g = None
-        if side is not None:
-            for st_ in side.streams:
-                main.wait_stream(st_)
-        del keep
-        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        out = [None, None]
-        for a, b in zip(gmu, grho):
-            out += [a, b]
-        return tuple(out)
-
-
 fold_lrt_combine = [True]       # an LRT layer's g1 + 2 x g2 is formed inside the pooling / activation backward of the layer below
 flips_up_front = [True]         # every layer's flipped input-gradient weights in one launch at the start of the backward
 pair_lrt_backward = [True]      # an LRT layer's (mean, variance) gradient pairs as the two draws of one launch (see _MCForwardLRT._backward)
@@ -433,7 +128,7 @@ overlap_wgrad = [True]
 _side_streams = {}
 
 
-n_side_streams = [int(__import__("os").environ.get("BBB_TRAIN_SIDE_STREAMS", "2"))]      # (measured 1 / 2 / 3: 2.895 / 2.75 / 2.78 ms per bs 512 x 10 step)
+n_side_streams = [int(os.environ.get("BBB_TRAIN_SIDE_STREAMS", "2"))]      # (measured 1 / 2 / 3: 2.895 / 2.75 / 2.78 ms per bs 512 x 10 step)
 
 
 class _Sides:
@@ -469,6 +164,332 @@ def _check_versions(versions):
                                "before a delayed backward?)")
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# what the three nodes share: the parameter lists, the forward walk, the context they carry to the backward, the backward schedule
+# ---------------------------------------------------------------------------------------------------------------------------
+def _param_lists(layers, leaf):
+    """(mus, rhos, stream ids) of the layers in forward order -- per layer (W, bias) -- each parameter passed through `leaf`
+    (a node's forward: detach; mc_logits_autograd: the alias that roots the graph)."""
+    mus, rhos, ids = [], [], []
+    for l in layers:
+        m, r, i = l._param_lists()
+        mus += [leaf(t) for t in m]
+        rhos += [leaf(t) for t in r]
+        ids += i
+    return mus, rhos, ids
+
+
+def _walk(mods, h, is_layer, run_layer, pool):
+    """The forward walk over a flat model (ensemble.flat_children), one copy for the three nodes: -> (tape, final h).
+    h: the batch-innermost input [1, C, H, W, B].  is_layer(m): m is a Bayesian layer of the node's kind.
+    run_layer(m, li, x_in, is_conv, geom, act, pooled) -> a record holding at least `y`, the activated output [E', Cout, Ho, Wo, B]
+    (x_in: h, for a linear layer reshaped to [*, in_features, 1, 1, B]; geom: (stride, padding, dilation); act: the activation
+    module behind the layer, fused and skipped; pooled: a MaxPool2d follows that).  pool(y, kernel, stride): the node's pooling.
+    The walk completes the record -- layer, x, act, geom, pool (kernel, stride) or None, first, out_shape (of what the next layer
+    reads) -- and appends it to the tape."""
+    from . import ensemble
+    from layers.lrt import BBBConv2d as LRTConv2d
+    _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
+    B = h.shape[-1]
+    tape = []                                                              # per Bayesian layer, in forward order
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if is_layer(m):
+            is_conv = isinstance(m, (BBBConv2d, LRTConv2d))
+            geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
+            x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
+            act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
+            if act is not None:
+                i += 1
+            pool_mod = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d) else None
+            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None)
+            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, first=not tape)
+            h = rec["y"]
+            if pool_mod is not None:
+                h = pool(h, pool_mod.kernel_size, pool_mod.stride)
+                rec["pool"] = (pool_mod.kernel_size, pool_mod.stride)
+                i += 1
+            rec["out_shape"] = tuple(h.shape)
+            tape.append(rec)
+        elif isinstance(m, nn.MaxPool2d):                                  # a pool that does not follow a Bayesian layer: on the input
+            raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
+        elif isinstance(m, FlattenLayer):
+            h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
+        i += 1
+    return tape, h
+
+
+def _carry(ctx, cfg, params):
+    """forward: what every node's backward needs beside its tape."""
+    ctx.cfg = cfg
+    ctx.launch_config = ops.current_config()              # backward runs on autograd's device thread: carry the modes along
+    ctx.scratch_token = ops.current_scratch_token()
+    ctx.versions = [(p, p._version) for p in params]      # backward re-reads the live (mu, rho): they must not have moved
+
+
+def _run_backward(ctx, node_backward, *grads):
+    """backward: the node's _backward under the forward's launch configuration and scratch scope."""
+    with ops.use_config(ctx.launch_config), ops.scratch_scope(token=ctx.scratch_token):
+        _check_versions(ctx.versions)
+        ctx.cfg["spent"] = True                            # layers/_fused.py: no further draws are served from this graph
+        return node_backward(ctx, *grads)
+
+
+class _Schedule:
+    """Where the launches of one backward go.  A layer's weight / bias gradients and its input gradient are independent: the former
+    run on a side stream beside the latter (both are launches that leave the chip partly idle on their own), the streams taken
+    round robin, last layer first; the first layer's weight side runs on the main stream (nothing is left to run beside it); all
+    are joined before the parameter pass's backward.  Tensors a side stream reads stay referenced in `keep` until the join (the
+    allocator must not hand them out again before).  Eager launches only: inside a captured step the forks cost more than the
+    overlap gains -- 4.8 against 3.05 ms per step.
+    g: the incoming gradient (None: nothing to schedule); weight_side: the node runs weight sides at all."""
+
+    def __init__(self, g, weight_side):
+        self.run_weights = weight_side
+        forks = g is not None and weight_side and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()
+        self.side = _side_stream(g.device) if forks else None
+        self.main = torch.cuda.current_stream(g.device) if forks else None
+        self.keep = []
+        self.early = None                                  # the stream of fork_early's launch
+
+    def fork_early(self, launch):
+        """launch() on a side stream NOW (one turn of the round robin) -> its result, kept until the join; the first layer's
+        weight side waits for it."""
+        self.side.wait_stream(self.main)
+        self.early = self.side.current
+        with torch.cuda.stream(self.early):
+            out = launch()
+        self.keep.append(out)
+        return out
+
+    def weight_side(self, first, launch, reads):
+        """A layer's weight side: on the next side stream (which keeps `reads` alive) unless it is the first layer's or there are
+        no side streams; then on the main stream; not at all when the node runs no weight sides."""
+        if self.side is not None and not first:
+            self.keep += reads
+            self.side.wait_stream(self.main)
+            with torch.cuda.stream(self.side.current):
+                launch()
+        elif self.run_weights:
+            if first and self.early is not None:
+                self.main.wait_stream(self.early)
+            launch()
+
+    def join(self):
+        if self.side is not None:
+            for st_ in self.side.streams:
+                self.main.wait_stream(st_)
+        self.keep = []
+
+
+class _MCForward(torch.autograd.Function):
+    """(x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (logits [E, C, B] batch-innermost, kl of one forward)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *params):
+        from . import ensemble
+        _BBBLayer = _layers()[0]
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        mods = ensemble.flat_children(cfg["net"])
+        layers = [m for m in mods if isinstance(m, _BBBLayer)]
+        mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
+        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
+        ws, _, kl = ops.reparam_kl_forward(mus, rhos, pm, ps, ids, seed, call0, draws=E)
+
+        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
+            w, b = ws[2 * li], ws[2 * li + 1]
+            w5 = w if is_conv else w.reshape(E, m.out_features, m.in_features, 1, 1)
+            return dict(w=w5, y=ops.conv2d_chwn_forward(x_in, w5, b, *geom, act=act))
+
+        h = ops.to_batch_innermost(x.detach()).unsqueeze(0)               # [1, C, H, W, B]
+        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn)
+        _carry(ctx, cfg, params)
+        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
+        ctx.x_nchw = x.detach()
+        return h.reshape(E, -1, x.shape[0]), kl
+
+    @staticmethod
+    def backward(ctx, g_logits, g_kl):
+        return _run_backward(ctx, _MCForward._backward, g_logits, g_kl)
+
+    @staticmethod
+    def _backward(ctx, g_logits, g_kl):
+        cfg, tape = ctx.cfg, ctx.tape
+        mus, rhos, ids, pm, ps, x_shape = ctx.meta
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        # need_w False (frozen parameters: saliency maps, adversarial steps): no weight side at all -- no bias sums, weight gradients,
+        # im2col, parameter pass or side-stream forks; need_x: the first layer's input gradient (first_layer_input_grad) at the end
+        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        gws = [None] * len(mus)
+        dx = None
+        g = g_logits.contiguous() if g_logits is not None else None
+        sched = _Schedule(g, weight_side=need_w)
+        # the first layer's im2col depends on the batch alone: on a side stream NOW, beside the small last layers' launches, instead of
+        # in the tail of the chain where nothing else is left to run beside it (without side streams
+        # conv2d_chwn_weight_grad_shared_input builds it itself: xk None)
+        r0 = tape[0]
+        xk_first = None
+        if sched.side is not None and r0["x"].shape[1] % 4 != 0:
+            xk_first = sched.fork_early(lambda: ops.im2col_pbj(ctx.x_nchw, tuple(r0["w"].shape), *r0["geom"]))
+        # every layer's input-gradient weights (flipped, channel-transposed: they depend on the sampled weights alone) in ONE launch up
+        # front instead of one launch per layer on the chain -- for launch-bound steps (no side streams: captured, small).  A
+        # many-draw step keeps them on the chain: up front, even on the side stream, they cost it 40 us (2.45 -> 2.49 ms at 512 x 10,
+        # profiles/experiments/ab_flips_up_front.py)
+        w_flipped = {}
+        if flips_up_front[0] and sched.side is None and g is not None and len(tape) > 1:
+            outs = ops.flip_transpose_w_multi([tape[li]["w"] for li in range(1, len(tape))])
+            w_flipped = {li: o for li, o in zip(range(1, len(tape)), outs)}
+        for li in range(len(tape) - 1, -1, -1):
+            rec = tape[li]
+            y, w5, x_in, act = rec["y"], rec["w"], rec["x"], rec["act"]
+            stride, padding, dilation = rec["geom"]
+            if g is None:
+                break
+            g = g.reshape(rec["out_shape"])
+            pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
+            if rec["pool"] is not None:
+                g_pre = ops.pool_act_backward_chwn(g, y, rec["pool"][0], rec["pool"][1], act, pad_planes=pad)
+            elif act is not None:
+                g_pre = ops.pool_act_backward_chwn(g, y, 0, 1, act, pad_planes=pad)
+            else:
+                g_pre = g
+
+            def weight_side():
+                gws[2 * li + 1] = ops.plane_sums(g_pre)                   # bias gradient [E, Cout]
+                if x_in.shape[1] % 4 == 0 or not rec["first"]:           # (6-channel inputs etc.: padded to 8 inside)
+                    gw = ops.conv2d_chwn_weight_grad(g_pre, x_in, tuple(w5.shape), stride, padding, dilation)
+                else:
+                    # 3-channel first layer: its input is shared by all draws, so the draws stack into the GEMM's row dimension
+                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, tuple(w5.shape), stride, padding, dilation, xk=xk_first)
+                gws[2 * li] = gw.reshape(ws_shape(rec))
+
+            sched.weight_side(rec["first"], weight_side, reads=[g_pre])
+            if not rec["first"]:
+                g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li),
+                                               stride=stride)
+            else:
+                if need_x:
+                    dx = ops.first_layer_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), stride, padding, dilation).view(x_shape)
+                g = None
+        sched.join()
+        out = [None, dx]
+        if not need_w:
+            return tuple(out + [None] * (2 * len(mus)))
+        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
+        for a, b in zip(gmu, grho):
+            out += [a, b]
+        return tuple(out)
+
+
+class _MCForwardBF16(torch.autograd.Function):
+    """_MCForward in the bf16 storage mode (train.train_step(precision="bf16"); the arithmetic contract is DESIGN.md section 4.5):
+    (x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (fp32 logits [E, C, B] batch-innermost, fp32 kl of one forward).
+    Forward = the bf16 inference kernels with the pooling left unfused (the tape keeps every layer's pre-pool output): sampled
+    weights, the input and every hidden activated / pooled output stored as bf16, fp32 accumulation, fp32 logits and KL.  Tape:
+    each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the walk of _MCForward._backward on the same
+    _Schedule with
+      * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
+      * ops.plane_sums_bf16               bias gradients, the fp32 sum of that bf16 g_pre,
+      * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16 (a strided layer, admitted
+        under LaunchConfig.bf16_strided_train: the transposed launch on the same rows),
+      * ops.conv2d_chwn_weight_grad_bf16  wgrad on the bf16 GEMM with the roles swapped -> fp32,
+      * the first layer (3-channel input shared by every draw): ops.conv2d_chwn_weight_grad_shared_input on the fp32 kernel over
+        the fp32 values of the bf16 operands (a bf16 x bf16 product is exact in fp32: the same contraction),
+      * ops.reparam_kl_backward           unchanged (fp32)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *params):
+        from . import ensemble
+        _BBBLayer = _layers()[0]
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        mods = ensemble.flat_children(cfg["net"])
+        layers = [m for m in mods if isinstance(m, _BBBLayer)]
+        mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
+        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
+        kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E)
+
+        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
+            w, b = ws[2 * li], ws[2 * li + 1]
+            wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
+            last = li == len(layers) - 1
+            if last and (act is not None or pooled):
+                raise _lib.BBBHipError("bf16 training: the logits layer (fp32 output) must not be followed by an activation or a pool")
+            y = ops.conv2d_chwn_bf16_forward(x_in, w, b, wshape[1:], *geom, act=act, out_f32=last,
+                                             tap_major=is_conv and ops.bf16_tap_major(wshape))
+            return dict(w=w, wshape=wshape, y=y)
+
+        h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
+        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn_bf16)
+        _carry(ctx, cfg, params)
+        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
+        # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted)
+        ctx.x_nchw = x.detach().to(torch.bfloat16).to(torch.float32) if tape[0]["x"].shape[1] % 4 != 0 else None
+        return h.reshape(E, -1, x.shape[0]), kl
+
+    @staticmethod
+    def backward(ctx, g_logits, g_kl):
+        return _run_backward(ctx, _MCForwardBF16._backward, g_logits, g_kl)
+
+    @staticmethod
+    def _backward(ctx, g_logits, g_kl):
+        cfg, tape = ctx.cfg, ctx.tape
+        mus, rhos, ids, pm, ps, x_shape = ctx.meta
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        gws = [None] * len(mus)
+        g = g_logits.contiguous() if g_logits is not None else None
+        # weight_side=True whatever needs a gradient: this mode refuses x.requires_grad (bf16_train_refusal), so every backward
+        # it sees is one for the parameters
+        sched = _Schedule(g, weight_side=True)
+        r0 = tape[0]
+        shared0 = r0["x"].shape[1] % 4 != 0
+        xk_first = None                                                   # (as in _MCForward: the first layer's im2col forked up front)
+        if sched.side is not None and shared0:
+            xk_first = sched.fork_early(lambda: ops.im2col_pbj(ctx.x_nchw, (E,) + r0["wshape"], *r0["geom"]))
+        # every layer's flipped input-gradient weight rows up front (captured / launch-bound steps, as in _MCForward; one launch per
+        # layer: the rows have no multi-layer form)
+        w_flipped = {}
+        if flips_up_front[0] and sched.side is None and g is not None:
+            w_flipped = {li: ops.flip_transpose_w_bf16(tape[li]["w"], tape[li]["wshape"]) for li in range(1, len(tape))}
+        for li in range(len(tape) - 1, -1, -1):
+            rec = tape[li]
+            if g is None:
+                break
+            y, w, x_in, act, wshape = rec["y"], rec["w"], rec["x"], rec["act"], rec["wshape"]
+            stride, padding, dilation = rec["geom"]
+            g = g.reshape(rec["out_shape"])
+            shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
+            k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
+            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
+                g_pre = g                                                 # already the bf16 output gradient
+            else:
+                g_pre = ops.pool_act_backward_chwn_bf16(g, y if y.dtype == torch.bfloat16 else None, k, s, act, out_f32=shared,
+                                                        pad_planes=shared)
+
+            def weight_side():
+                wsh = (E,) + wshape
+                if shared:
+                    gws[2 * li + 1] = ops.plane_sums(g_pre)
+                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, stride, padding, dilation, xk=xk_first)
+                else:
+                    gws[2 * li + 1] = ops.plane_sums_bf16(g_pre)
+                    gw = ops.conv2d_chwn_weight_grad_bf16(g_pre, x_in, wsh, stride, padding, dilation)
+                gws[2 * li] = gw.reshape(ws_shape(rec))
+
+            sched.weight_side(rec["first"], weight_side, reads=[g_pre])
+            if not rec["first"]:
+                g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
+                                                    w_flipped=w_flipped.get(li), stride=stride)
+            else:
+                g = None
+        sched.join()
+        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
+        out = [None, None]
+        for a, b in zip(gmu, grho):
+            out += [a, b]
+        return tuple(out)
+
+
 def _inverse_act(y, act):
     """Pre-activation from the activated output (what the LRT backward needs to recover sqrt(act_var) * eps = v - act_mu)."""
     if act == "softplus":
@@ -488,76 +509,45 @@ class _MCForwardLRT(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, x, *params):
         from . import ensemble
-        from layers.lrt import BBBConv2d as LRTConv2d
-        _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
-        net, E, seed, call0 = cfg["net"], cfg["draws"], cfg["seed"], cfg["call0"]
-        mods = ensemble.flat_children(net)
-        B = x.shape[0]
+        _LRTLayer = _layers()[3]
+        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+
+        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
+            w_mu, w_var, b_mu, b_var = (t.detach() for t in params[4 * li:4 * li + 4])
+            if not is_conv:
+                shp = (m.out_features, m.in_features, 1, 1)
+                w_mu, w_var = w_mu.reshape(shp), w_var.reshape(shp)
+            sid = m._stream_base + 2
+            if x_in.shape[0] == 1 and E > 1:              # the shared first layer: one pair of moments, E samples of it
+                _, am, av = ops.lrt_conv2d_chwn_forward(x_in, w_mu, w_var, b_mu, b_var, seed, call0, sid, *geom, sample=False,
+                                                        want_moments=True, act=None)
+                y = ops.lrt_sample_chwn(am, av, E, seed, call0, sid, act=act)
+            else:
+                y, am, av = ops.lrt_conv2d_chwn_forward(x_in, w_mu, w_var, b_mu, b_var, seed, call0, sid, *geom, sample=True,
+                                                        want_moments=True, act=act)
+            return dict(w_mu=w_mu, w_var=w_var, y=y, am=am, av=av)
+
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)
-        tape, li, i = [], 0, 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, _LRTLayer):
-                w_mu, w_var, b_mu, b_var = (t.detach() for t in params[4 * li:4 * li + 4])
-                is_conv = isinstance(m, LRTConv2d)
-                geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
-                x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
-                if not is_conv:
-                    shp = (m.out_features, m.in_features, 1, 1)
-                    w_mu, w_var = w_mu.reshape(shp), w_var.reshape(shp)
-                act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
-                sid = m._stream_base + 2
-                shared = x_in.shape[0] == 1 and E > 1
-                if shared:
-                    _, am, av = ops.lrt_conv2d_chwn_forward(x_in, w_mu, w_var, b_mu, b_var, seed, call0, sid, *geom, sample=False,
-                                                            want_moments=True, act=None)
-                    y = ops.lrt_sample_chwn(am, av, E, seed, call0, sid, act=act)
-                else:
-                    y, am, av = ops.lrt_conv2d_chwn_forward(x_in, w_mu, w_var, b_mu, b_var, seed, call0, sid, *geom, sample=True,
-                                                            want_moments=True, act=act)
-                rec = dict(layer=m, x=x_in, w_mu=w_mu, w_var=w_var, y=y, am=am, av=av, act=act, geom=geom, pool=None, first=(li == 0))
-                if act is not None:
-                    i += 1
-                h = y
-                if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d):
-                    pool = mods[i + 1]
-                    h = ops.maxpool_chwn(y, pool.kernel_size, pool.stride)
-                    rec["pool"] = (pool.kernel_size, pool.stride)
-                    i += 1
-                rec["out_shape"] = tuple(h.shape)
-                tape.append(rec)
-                li += 1
-            elif isinstance(m, nn.MaxPool2d):
-                raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
-            elif isinstance(m, FlattenLayer):
-                h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
-            i += 1
-        ctx.cfg, ctx.tape = cfg, tape
-        ctx.launch_config = ops.current_config()
-        ctx.scratch_token = ops.current_scratch_token()
+        tape, h = _walk(ensemble.flat_children(cfg["net"]), h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn)
+        _carry(ctx, cfg, params)
+        ctx.tape = tape
         ctx.x_nchw = x.detach()
-        ctx.versions = [(p, p._version) for p in params]
-        return h.reshape(h.shape[0], -1, B)
+        return h.reshape(h.shape[0], -1, x.shape[0])
 
     @staticmethod
     def backward(ctx, g_logits):
-        with ops.use_config(ctx.launch_config), ops.scratch_scope(token=ctx.scratch_token):
-            return _MCForwardLRT._backward(ctx, g_logits)
+        return _run_backward(ctx, _MCForwardLRT._backward, g_logits)
 
     @staticmethod
     def _backward(ctx, g_logits):
         tape = ctx.tape
-        _check_versions(ctx.versions)
-        ctx.cfg["spent"] = True
         need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])         # (as in _MCForward)
         grads = [None] * (4 * len(tape))
         dx = None
         g = g_logits.contiguous()
-        # (as in _MCForward: the weight-side work of a layer on a second stream beside its input gradients, eager launches only)
-        side = _side_stream(g.device) if (need_w and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()) else None
-        main = torch.cuda.current_stream(g.device) if side is not None else None
-        keep = []
-        # (as in _MCForward: the flipped input-gradient weights of every layer -- mean and variance sets -- in one launch up front)
+        sched = _Schedule(g, weight_side=need_w)
+        # (as in _MCForward: the flipped input-gradient weights of every layer -- mean and variance sets -- in one launch up front;
+        # here whether or not there are side streams, there without them only)
         w_flipped = {}
         if flips_up_front[0] and len(tape) > 1:
             pairs = [(tape[li]["w_mu"].unsqueeze(0), tape[li]["w_var"].unsqueeze(0)) for li in range(1, len(tape))]
@@ -590,8 +580,8 @@ class _MCForwardLRT(torch.autograd.Function):
                 # (the two sums one set apart in one buffer: the input gradient reads them as the two draws of one launch)
                 both = torch.empty((2, 1) + tuple(g_mu.shape[1:]), dtype=torch.float32, device=g_mu.device)
                 g_mu, g_var = ops.sum_over_draws(g_mu, keepdim=True, out=both[0]), ops.sum_over_draws(g_var, keepdim=True, out=both[1])
-            def weight_side(g_mu=g_mu, g_var=g_var, x_in=x_in, w_mu=w_mu, rec=rec, li=li, stride=stride, padding=padding, dilation=dilation,
-                            g_pair=g_pair):
+
+            def weight_side():
                 wshape = (1,) + tuple(w_mu.shape)
                 Ed = g_mu.shape[0]
                 if g_pair is not None and Ed == 1:
@@ -609,6 +599,7 @@ class _MCForwardLRT(torch.autograd.Function):
                     gw_var = ops.conv2d_chwn_weight_grad(g_var, ops.square(x_in), wshape, stride, padding, dilation)
                     gw_mu, gw_var = ops.sum_over_draws(gw_mu), ops.sum_over_draws(gw_var)
                 else:
+                    # (built inside the weight side, on the main stream: this node forks no early im2col, _MCForward does)
                     xk = ops.im2col_pbj(ctx.x_nchw, wshape, stride, padding, dilation)      # (its square = the im2col of x^2)
                     gw_mu = ops.conv2d_chwn_weight_grad_shared_input(g_mu, None, wshape, stride, padding, dilation, xk=xk)[0]
                     gw_var = ops.conv2d_chwn_weight_grad_shared_input(g_var, None, wshape, stride, padding, dilation, xk=ops.square(xk))[0]
@@ -616,13 +607,7 @@ class _MCForwardLRT(torch.autograd.Function):
                 grads[4 * li] = gw_mu.reshape(m.W_mu.shape)
                 grads[4 * li + 1] = gw_var.reshape(m.W_mu.shape)
 
-            if side is not None and not rec["first"]:
-                keep += [g_mu, g_var]
-                side.wait_stream(main)
-                with torch.cuda.stream(side.current):
-                    weight_side()
-            elif need_w:
-                weight_side()
+            sched.weight_side(rec["first"], weight_side, reads=[g_mu, g_var])
             if rec["first"] and need_x:
                 dx = ops.first_layer_input_grad((g_mu, g_var), (w_mu, w_var), (x_in.shape[2], x_in.shape[3]), stride, padding, dilation,
                                                 x_lrt=ctx.x_nchw).view(ctx.x_nchw.shape)
@@ -641,10 +626,7 @@ class _MCForwardLRT(torch.autograd.Function):
                     g2 = ops.conv2d_chwn_input_grad(g_var, w_var.unsqueeze(0), hw, padding, dilation, w_flipped=t_var, stride=stride)
                 # (g1 + 2 x g2 is formed by the layer below's pooling / activation pass)
                 g = (g1, x_in, g2) if fold_lrt_combine[0] else ops.lrt_input_grad_combine(g1, x_in, g2)
-        if side is not None:
-            for st_ in side.streams:
-                main.wait_stream(st_)
-        del keep
+        sched.join()
         return (None, dx, *grads)
 
 
@@ -678,7 +660,6 @@ def bf16_train_refusal(net, x):
         return "a batch size that is a multiple of 8"
     return None
 
-
 def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32"):
     """Differentiable batched forward: -> (logits [E, C, B] batch-innermost, kl of one forward), gradients flow to every
     layer's W_mu, W_rho, bias_mu, bias_rho.  Call only when train_path_ok(net, x).
@@ -696,34 +677,19 @@ def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32")
         why = bf16_train_refusal(net, x)
         if why is not None:
             raise _lib.BBBHipError("bf16 training covers " + why)
-        params = []
-        for l in ensemble.bayesian_layers(net):
-            params += [A(l.W_mu), A(l.W_rho), A(l.bias_mu), A(l.bias_rho)]
-        cfg = dict(net=net, draws=int(draws), seed=seed, call0=call0)
-        logits, kl = _MCForwardBF16.apply(cfg, x, *params)
-        logits.bbb_cfg = cfg
-        return logits, kl
-    kind = train_path_ok(net, x)
-    if kind == "lrt":
-        layers = ensemble.bayesian_layers(net)
-        mus, rhos = [], []
-        for l in layers:
-            m, r, _ = l._param_lists()
-            mus += [A(t) for t in m]
-            rhos += [A(t) for t in r]
-        kl, s2, mu = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True,
-                                 mu_through=True)
-        flat = []
-        for li, l in enumerate(layers):
-            flat += [mu[2 * li], s2[2 * li], mu[2 * li + 1], s2[2 * li + 1]]
-        cfg = dict(net=net, draws=int(draws), seed=seed, call0=call0)
-        logits = _MCForwardLRT.apply(cfg, x, *flat)
-        logits.bbb_cfg = cfg
-        return logits, kl
+        node = _MCForwardBF16
+    else:
+        node = _MCForwardLRT if train_path_ok(net, x) == "lrt" else _MCForward
+    layers = ensemble.bayesian_layers(net)
+    mus, rhos, _ = _param_lists(layers, A)
+    if node is _MCForwardLRT:                # its leaves are (mu, sigma^2) from the KL pass, which carries the gradients to (mu, rho)
+        kl, rhos, mus = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True,
+                                    mu_through=True)
     params = []
-    for l in ensemble.bayesian_layers(net):
-        params += [A(l.W_mu), A(l.W_rho), A(l.bias_mu), A(l.bias_rho)]
+    for li in range(len(layers)):            # per layer: W_mu, W_rho (LRT: W_var), bias_mu, bias_rho (LRT: bias_var)
+        params += [mus[2 * li], rhos[2 * li], mus[2 * li + 1], rhos[2 * li + 1]]
     cfg = dict(net=net, draws=int(draws), seed=seed, call0=call0)
-    logits, kl = _MCForward.apply(cfg, x, *params)
+    out = node.apply(cfg, x, *params)
+    logits, kl = (out, kl) if node is _MCForwardLRT else out
     logits.bbb_cfg = cfg
     return logits, kl

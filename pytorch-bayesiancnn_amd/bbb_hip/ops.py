@@ -2023,7 +2023,8 @@ def lrt_conv2d(x, w_mu, w_var, b_mu, b_var, seed, call0, stream_id, stride=1, pa
 
 
 # ------------------------------------------------------------------------------------------------
-# batch-innermost backward helpers (training on the fast path, bbb_hip/fast_train.py)
+# batch-innermost backward helpers (training on the fast path: called from the nodes' _backward in bbb_hip/fast_train.py, on the
+# stream fast_train._Schedule puts them on)
 # ------------------------------------------------------------------------------------------------
 def padded_plane_pitch(K):
     """Row pitch for a [planes, K] matrix that a GEMM reads row-wise: K itself unless rows of K floats are a multiple of 4 KiB
@@ -2545,7 +2546,7 @@ def first_layer_input_grad(g_pre, w, x_hw, stride, padding, dilation, x_lrt=None
     return dx
 
 
-# ---- bf16 training backward (fast_train._MCForwardBF16) ------------------------------------------------
+# ---- bf16 training backward (fast_train._MCForwardBF16._backward on fast_train._Schedule) ---------------
 
 def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=False):
     """pool_act_backward_chwn on bf16 storage (bbb_pool_act_bwd_chwn_bf16): y = the stored bf16 activated output [..., H, W, B],

@@ -1,5 +1,5 @@
-"""Seeded sweep of the bf16 training backward (fast_train._MCForwardBF16, csrc/train_bf16.hip, the role-swapped launches of the bf16
-GEMM) over the geometries bf16_train_refusal admits -- what _train_path_static admits with B % 8 == 0 -- against CPU float64
+"""Seeded sweep of the bf16 training backward (fast_train._MCForwardBF16 on the shared fast_train._walk / _Schedule,
+csrc/train_bf16.hip, the role-swapped launches of the bf16 GEMM) over the geometries bf16_train_refusal admits -- what _train_path_static admits with B % 8 == 0 -- against CPU float64
 references computed on the SAME bf16 operands:
 
   * kernel level: conv2d_chwn_input_grad_bf16 (with / without up-front flipped rows), conv2d_chwn_weight_grad_bf16 (batch chunks on

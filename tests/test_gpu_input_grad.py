@@ -1,6 +1,6 @@
 """Input gradients (d loss / d x) of Monte-Carlo forwards on the batch-innermost path: ops.first_layer_input_grad (the first layer's
-contraction on the forward GEMM + bbb_input_grad_col2im), the autograd nodes' `x` output (fast_train._MCForward / _MCForwardLRT)
-and the routing of ensemble.mc_forward / mc_logits / train.forward_loss, frozen parameters included.
+contraction on the forward GEMM + bbb_input_grad_col2im), the autograd nodes' `x` output (fast_train._MCForward / _MCForwardLRT,
+whose frozen-parameter backward runs no weight side: fast_train._Schedule(weight_side=False)) and the routing of ensemble.mc_forward / mc_logits / train.forward_loss, frozen parameters included.
 
   * kernel sweep against float64 (torch.nn.grad.conv2d_input summed over draws) over first layers fast_train._train_path_static
     admits -- the zoo's three first layers at full channel counts, strides 2-4 with floor-dropped rows, dilations 2-3, rectangular
