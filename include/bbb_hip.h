@@ -365,6 +365,31 @@ int bbb_lrt_conv2d_chwn_splitk_fwd(const bbb_conv_desc_t* d, const float* x, con
                                    float* act_mu_out, float* act_var_out, const float* eps_ext,
                                    uint64_t seed, uint32_t call0, uint32_t stream_id, int sample,
                                    const uint32_t* call_dev, int k_split, void* scratch, int64_t scratch_bytes, void* stream);
+/*
+ * bbb_conv2d_chwn_plan: which launch form bbb_conv2d_chwn_fwd / _splitk_fwd (lrt == 0) or bbb_lrt_conv2d_chwn_fwd / _splitk_fwd
+ * (lrt != 0) takes for this descriptor, k_split as the launch would be given it and has_scratch != 0 when the launch would be
+ * given enough scratch for the cross-workgroup form.  Host only: launches nothing, needs no device.  *form: BBB_FP32_FORM_*;
+ * *bm: images per work item (64 | 128); *ilv: staging loads interleaved with the MFMAs; *items: work items; *blocks: workgroups
+ * (the cross-workgroup split: items * k_split, rounded up to 8).  Out-pointers may be NULL.  Returns 0 or what the launch entry
+ * returns for every check that does not involve an operand pointer; the two call the same plan (csrc/pconv_plan.h).
+ */
+#define BBB_FP32_FORM_64_ILV 0         /* pconv_gemm_kernel<64, false, ILV> */
+#define BBB_FP32_FORM_64 1
+#define BBB_FP32_FORM_128_ILV 2        /* 128-image tiles */
+#define BBB_FP32_FORM_128 3
+#define BBB_FP32_FORM_SEQ64_ILV 4      /* the layer's split inside one workgroup per item */
+#define BBB_FP32_FORM_SEQ64 5
+#define BBB_FP32_FORM_SEQ128_ILV 6
+#define BBB_FP32_FORM_SEQ128 7
+#define BBB_FP32_FORM_CROSS 8          /* ... across workgroups, through scratch */
+#define BBB_FP32_FORM_POOL 9           /* d->pool: MaxPool2d(2, 2) inside the launch */
+#define BBB_FP32_FORM_LRT64_ILV 10     /* the LRT kernel: 64-image tiles only */
+#define BBB_FP32_FORM_LRT64 11
+#define BBB_FP32_FORM_LRT_SEQ64 12
+#define BBB_FP32_FORM_LRT_CROSS 13
+#define BBB_FP32_FORM_LRT_POOL 14
+int bbb_conv2d_chwn_plan(const bbb_conv_desc_t* d, int lrt, int k_split, int has_scratch, int32_t* form, int32_t* bm, int32_t* ilv,
+                         int64_t* items, int64_t* blocks);
 
 /* nn.MaxPool2d(kernel_size=k, stride=s) (no padding, floor mode; models/BayesianModels/BayesianAlexNet.py:37)
  * on batch-innermost planes: x [planes][h][w][B] -> y [planes][(h-k)/s+1][(w-k)/s+1][B]. */

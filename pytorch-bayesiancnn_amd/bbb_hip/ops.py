@@ -998,6 +998,32 @@ def lrt_conv2d_chwn_forward(x, w_mu, w_var, b_mu, b_var, seed, call0, stream_id,
     return y, am, av
 
 
+FP32_FORMS = ("bbb-64-ilv", "bbb-64", "bbb-128-ilv", "bbb-128", "bbb-seq64-ilv", "bbb-seq64", "bbb-seq128-ilv", "bbb-seq128",
+              "bbb-cross", "bbb-pool", "lrt-64-ilv", "lrt-64", "lrt-seq64", "lrt-cross", "lrt-pool")      # BBB_FP32_FORM_* (include/bbb_hip.h)
+
+
+def fp32_fwd_plan(x_shape, w_shape, stride=1, padding=0, dilation=1, draws=None, lrt=False, pool=False, k_split=None, scratch=True):
+    """(form, images per item, interleaved staging, items, workgroups, k_split) of the launch conv2d_chwn_forward (lrt=False) or
+    lrt_conv2d_chwn_forward (lrt=True) makes for x_shape = [*, Cin, H, W, B], w_shape = [*, Cout, Cin, kh, kw] and `draws` output
+    slabs: form one of FP32_FORMS (bbb_conv2d_chwn_plan, the launch entries' own plan; host only: needs no device).  k_split: None =
+    the layer's own split when ops.current_config().split_k is on (what the two forwards pass), else the value to ask about;
+    scratch: the launch gets scratch for its cross-workgroup form, as the two forwards give it.  A geometry or a k_split the launch
+    refuses raises the launch's error."""
+    E = int(draws) if draws is not None else x_shape[0]
+    d, _, _ = _lrt_bf16_desc((E,) + tuple(x_shape[-4:]), w_shape[-4], tuple(w_shape[-3:]), stride, padding, dilation, E, False, None)
+    d.pool = 1 if pool else 0
+    if k_split is None:
+        ks = ctypes.c_int32(1)
+        if current_config().split_k:
+            _lib.lib().bbb_conv2d_chwn_splitk_scratch(ctypes.byref(d), 1 if lrt else 0, ctypes.byref(ks))
+        k_split = ks.value
+    fm, bm, ilv, items, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.lib().bbb_conv2d_chwn_plan(ctypes.byref(d), 1 if lrt else 0, int(k_split), 1 if scratch else 0, ctypes.byref(fm),
+                                          ctypes.byref(bm), ctypes.byref(ilv), ctypes.byref(items), ctypes.byref(blocks)),
+          "bbb_conv2d_chwn_plan")
+    return FP32_FORMS[fm.value], bm.value, bool(ilv.value), items.value, blocks.value, int(k_split)
+
+
 def lrt_sample_chwn(act_mu, act_var, draws, seed, call0, stream_id, act=None, b_offset=0):
     """E draws y[e] = act(act_mu + sqrt(act_var) * eps[e]) from one pair of LRT moments [1|-, C, Ho, Wo, B] ->
     [E, C, Ho, Wo, B]; eps as the LRT GEMM epilogue would draw it for draw e."""

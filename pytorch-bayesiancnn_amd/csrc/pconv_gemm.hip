@@ -28,6 +28,7 @@
 #include "pconv_args.h"
 #include "pconv_body.cuh"
 #include "pconv_bf16x3.cuh"
+#include "pconv_plan.h"
 
 namespace {
 
@@ -197,187 +198,79 @@ __global__ __launch_bounds__(256) void pool_act_bwd_chwn_kernel(const float* __r
     }
 }
 
+// the descriptor checks (pconv_plan.h, describe) -> the kernel-argument block
 int fill(const bbb_conv_desc_t* d, PConvArgs& a) {
-    if (d == nullptr) return BBB_EINVAL;
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 ||
-        d->draws <= 0 || d->act < 0 || d->act > 2)
-        return BBB_EINVAL;
-    if (d->batch % 4 != 0) return BBB_ESHAPE;        // batch-innermost rows are moved as 16-byte vectors
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    if ((int64_t)d->cin * d->h * d->w > 0x7fffffffLL || (int64_t)d->cin * d->kh * d->kw > 0x7fffffffLL) return BBB_ESHAPE;
-    // per-draw slabs are addressed through 32-bit buffer offsets
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 4 > 0xFFFE0000LL || (int64_t)d->cout * ho * wo * d->batch * 4 > 0xFFFE0000LL ||
-        ((int64_t)d->cout + 64) * d->cin * d->kh * d->kw * 4 > 0x3FFFFFFFLL || (int64_t)d->batch * 4 > 0x0FFFFFFFLL)
-        return BBB_ESHAPE;
-    a.x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 4u) & ~15u;   /* a ragged last tile reaches < 512 columns past the row */
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 4 > (int64_t)a.x_inv) return BBB_ESHAPE;
-    a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
-    a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = ho; a.Wo = wo; a.K = d->cin * d->kh * d->kw; a.khkw = d->kh * d->kw; a.act = d->act;
-    if (d->w_row_pitch < 0 || (d->w_row_pitch > 0 && d->w_row_pitch < a.K)) return BBB_EINVAL;
-    a.Kp = d->w_row_pitch > 0 ? d->w_row_pitch : a.K;
-    if (((int64_t)d->cout + 64) * a.Kp * 4 > 0x3FFFFFFFLL) return BBB_ESHAPE;
-    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride;
-    a.y_ds = (int64_t)d->cout * ho * wo * d->batch;
-    if (d->unit_div < 0 || d->unit_off < 0 || d->x_unit_mod < 0 || d->b_offset < 0) return BBB_EINVAL;
-    if (d->unit_div > 1 && d->unit_off >= d->unit_div) return BBB_EINVAL;          // passed reduced modulo S
-    if (d->x_unit_mod > 0 && d->x_unit_mod != d->unit_div) return BBB_EINVAL;
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && (d->unit_div > 1 || d->x_unit_off >= d->x_unit_div)) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
-    a.unit_div = d->unit_div; a.unit_off = d->unit_div > 1 ? d->unit_off : 0; a.x_mod = d->x_unit_mod; a.b_off = d->b_offset;
-    a.x_div = d->x_unit_div; a.x_off = d->x_unit_off;
-    if (d->pool != 0 && d->pool != 1) return BBB_EINVAL;
-    a.pool = d->pool;
-    if (d->w_tap_major != 0 && d->w_tap_major != 1) return BBB_EINVAL;
-    a.wtap = d->w_tap_major;
-    if (a.pool) {
-        if ((ho & 1) || (wo & 1)) return BBB_EINVAL;
-        a.y_ds = (int64_t)d->cout * (ho / 2) * (wo / 2) * d->batch;
-    }
+    pconv_plan::Geom g;
+    const int rc = pconv_plan::describe(d, &g);
+    if (rc != 0) return rc;
+    a.x_inv = g.x_inv;
+    a.B = g.B; a.Cin = g.Cin; a.H = g.H; a.W = g.W; a.Cout = g.Cout; a.kh = g.kh; a.kw = g.kw;
+    a.sh = g.sh; a.sw = g.sw; a.ph = g.ph; a.pw = g.pw; a.dh = g.dh; a.dw = g.dw;
+    a.Ho = g.Ho; a.Wo = g.Wo; a.K = g.K; a.khkw = g.khkw; a.act = g.act; a.Kp = g.Kp;
+    a.x_ds = g.x_ds; a.w_ds = g.w_ds; a.b_ds = g.b_ds; a.y_ds = g.y_ds;
+    a.unit_div = g.unit_div; a.unit_off = g.unit_off; a.x_mod = g.x_mod; a.b_off = g.b_off;
+    a.x_div = g.x_div; a.x_off = g.x_off; a.pool = g.pool; a.wtap = g.wtap;
     return 0;
 }
 
-// launches of more 64-image items than this run the in-workgroup form of a layer's split (measured, profiles/r03_notes.md
-// section 2 and r04_notes.md: above ~400 items the cross-workgroup form only adds partial-tile traffic; LRT items carry two
-// accumulator sets and their in-workgroup form runs at 3 waves per SIMD, so the crossover sits higher)
-#ifndef PCONV_ILV_MAX
-#define PCONV_ILV_MAX 12000          // launches of at most this many items interleave their staging loads with the MFMAs (see launch())
-#endif
-#ifndef PCONV_SPLIT_MAX
-#define PCONV_SPLIT_MAX 384
-#endif
-constexpr int64_t split_max_items(bool lrt) { return lrt ? 512 : PCONV_SPLIT_MAX; }
+// what the plan reads of a filled argument block
+pconv_plan::Geom geom_of(const PConvArgs& a) {
+    pconv_plan::Geom g = {};
+    g.B = a.B; g.Cin = a.Cin; g.H = a.H; g.W = a.W; g.Cout = a.Cout; g.kh = a.kh; g.kw = a.kw;
+    g.dh = a.dh; g.dw = a.dw; g.Ho = a.Ho; g.Wo = a.Wo; g.pool = a.pool;
+    return g;
+}
 
+// Which kernel, which grid: pconv_plan.h (plan) decides -- the tile width, interleaved staging or not, the layer's split across
+// workgroups or inside one, the pooled forms; this function starts what it names.
 template <bool LRT>
 int launch(PConvArgs& a, int draws, hipStream_t st) {
-    a.Ntiles = (a.Cout + BN - 1) / BN;
-    a.G = a.Ntiles * draws;
-    const int64_t pixels = (int64_t)a.Ho * a.Wo;
-    // tile choice: 128 images per workgroup (two accumulator chains per wave) unless that leaves fewer than 3
-    // workgroups per CU, then 64.  A 256-image tile (64x64 per wave) exists but measured 5-10 % slower on every
-    // AlexNet layer (3 instead of 4 workgroups per CU); the launcher never selects it.
-    // LRT stages two weight tiles and keeps two accumulator sets: 64-wide only.
-    if (a.pool) {
-        // one item per POOLED pixel, 128-image tiles (LRT: 64) (the callers fuse large launches only)
-        if (a.ksplit > 1 || a.part != nullptr) return BBB_EINVAL;
-        if (LRT && (a.y_mu != nullptr || a.y_var != nullptr)) return BBB_EINVAL;    // the moments of unpooled pixels are not kept
-        a.nbt = (a.B + (LRT ? 63 : 127)) / (LRT ? 64 : 128);
-        const int64_t mtp = (pixels / 4) * a.nbt;
-        const int64_t itp = (int64_t)a.G * mtp;
-        if (mtp > 0x7fffffffLL || itp > 0x7fffffffLL - 8) return BBB_ESHAPE;
-        a.Mtiles = (int)mtp;
-        const int64_t perp = (itp + 7) / 8;
-        a.per_xcd = (int32_t)perp;
-        // staging loads up front (ILV = false): with the running maximum in 32 more accumulation registers this form fits four
-        // workgroups per CU (60 + 64 registers) and the interleaved one does not (82 + 64: three; measured 492-494 us against 480-482
-        // for conv1 of the metric step, profiles/r04_notes.md section 7)
-        if constexpr (LRT) hipLaunchKernelGGL(pconv_gemm_pool_lrt_kernel, dim3((unsigned)(8 * perp)), dim3(kThreads), 0, st, a);
-        else               hipLaunchKernelGGL((pconv_gemm_pool_kernel<false>), dim3((unsigned)(8 * perp)), dim3(kThreads), 0, st, a);
-        return (int)hipGetLastError();
-    }
-    const int64_t nb128 = pixels * ((a.B + 127) / 128) * a.G;
-    int bm = (LRT || nb128 < 768) ? 64 : 128;        // (round 3 re-measured 600 / 300: conv4 +10 %, conv5 +25 % slower with 128)
-    // an image axis that 128-wide tiles would pad by >= 25 % and 64-wide ones by less (192 = the input channels of conv3's
-    // role-swapped weight gradient: 256 against 192): 64.  Same sums per element either way.
-    if (bm == 128 && (a.B + 127) / 128 * 128 * 4 >= a.B * 5 && (a.B + 63) / 64 * 64 < (a.B + 127) / 128 * 128) bm = 64;
-    const int64_t items64 = pixels * ((a.B + 63) / 64) * a.G;
-    const bool cross = a.ksplit > 1 && a.part != nullptr && items64 <= split_max_items(LRT);
-    if (cross) bm = 64;
-    a.nbt = (a.B + bm - 1) / bm;
-    const int64_t mt = pixels * a.nbt;
-    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mt;
-    const int64_t items = (int64_t)a.G * mt;
-    if (cross) {
-        // the layer's split contraction ACROSS workgroups: a launch this small cannot fill the chip otherwise
-        if (items * a.ksplit > 0x7fffffffLL) return BBB_EINVAL;
-        const int64_t perb = (items * a.ksplit + 7) / 8;
-        a.per_xcd = (int32_t)perb;
-        hipLaunchKernelGGL((pconv_gemm_splitk_kernel<64, LRT, true>), dim3((unsigned)(8 * perb)), dim3(kThreads), 0, st, a);
-        return (int)hipGetLastError();
-    }
-    const int64_t per = (items + 7) / 8;
-    const int64_t blocks = 8 * per;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
-    // staging loads interleaved with the MFMAs (ILV): round 1 measured it a loss beyond ~1.5 rounds of workgroups; re-measured in
-    // round 3 on the current kernel (profiles/r03_notes.md section 3) it is a 1-2 % gain up to ~12k items, one or three steps in flight
-    const bool ilv = items <= PCONV_ILV_MAX;
-    const dim3 grid((unsigned)blocks), block(kThreads);
-    if (a.ksplit > 1) {
-        // the same summation order inside ONE workgroup per item (pconv_body.cuh, SEQ): no scratch, no extra traffic
-        if constexpr (!LRT) {
-            if (bm == 128) {
-                // (88-100 VGPRs + 64 accumulation registers = three workgroups per CU; held to four by amdgpu_waves_per_eu the
-                // prefetched tile spills around the range folds and the launch is 4-9 % slower: profiles/r04_notes.md section 4)
-                if (ilv) hipLaunchKernelGGL((pconv_gemm_kernel<128, false, true, true>), grid, block, 0, st, a);
-                else     hipLaunchKernelGGL((pconv_gemm_kernel<128, false, false, true>), grid, block, 0, st, a);
-                return (int)hipGetLastError();
-            }
+    using namespace pconv_plan;
+    if (LRT && a.pool && (a.y_mu != nullptr || a.y_var != nullptr)) return BBB_EINVAL;    // the moments of unpooled pixels are not kept
+    Plan pl;
+    const int rc = plan(geom_of(a), draws, LRT, a.ksplit, a.part != nullptr, &pl);
+    if (rc != 0) return rc;
+    a.Ntiles = pl.Ntiles; a.G = pl.G; a.nbt = pl.nbt; a.Mtiles = pl.Mtiles; a.per_xcd = pl.per_xcd;
+    const dim3 grid((unsigned)pl.blocks), block(kThreads);
+    if constexpr (LRT) {
+        switch (pl.form) {
+            case kLrtPool:  hipLaunchKernelGGL(pconv_gemm_pool_lrt_kernel, grid, block, 0, st, a); break;
+            case kLrtCross: hipLaunchKernelGGL((pconv_gemm_splitk_kernel<64, true, true>), grid, block, 0, st, a); break;
+            case kLrtSeq64: hipLaunchKernelGGL((pconv_gemm_kernel<64, true, false, true>), grid, block, 0, st, a); break;
+            case kLrt64Ilv: hipLaunchKernelGGL((pconv_gemm_kernel<64, true, true>), grid, block, 0, st, a); break;
+            case kLrt64:    hipLaunchKernelGGL((pconv_gemm_kernel<64, true, false>), grid, block, 0, st, a); break;
+            default: return BBB_EINVAL;
         }
-        const bool ilv_seq = ilv && !LRT;        // LRT: the interleaved form needs 172 registers (2 waves per SIMD), the plain one 161 (3)
-        if (ilv_seq) hipLaunchKernelGGL((pconv_gemm_kernel<64, LRT, true, true>), grid, block, 0, st, a);
-        else         hipLaunchKernelGGL((pconv_gemm_kernel<64, LRT, false, true>), grid, block, 0, st, a);
-        return (int)hipGetLastError();
-    }
-    if constexpr (!LRT) {
-        if (bm == 128) {
-            if (ilv) hipLaunchKernelGGL((pconv_gemm_kernel<128, false, true>), grid, block, 0, st, a);
-            else     hipLaunchKernelGGL((pconv_gemm_kernel<128, false, false>), grid, block, 0, st, a);
-            return (int)hipGetLastError();
+    } else {
+        switch (pl.form) {
+            case kBbbPool:      hipLaunchKernelGGL((pconv_gemm_pool_kernel<false>), grid, block, 0, st, a); break;
+            case kBbbCross:     hipLaunchKernelGGL((pconv_gemm_splitk_kernel<64, false, true>), grid, block, 0, st, a); break;
+            case kBbbSeq128Ilv: hipLaunchKernelGGL((pconv_gemm_kernel<128, false, true, true>), grid, block, 0, st, a); break;
+            case kBbbSeq128:    hipLaunchKernelGGL((pconv_gemm_kernel<128, false, false, true>), grid, block, 0, st, a); break;
+            case kBbbSeq64Ilv:  hipLaunchKernelGGL((pconv_gemm_kernel<64, false, true, true>), grid, block, 0, st, a); break;
+            case kBbbSeq64:     hipLaunchKernelGGL((pconv_gemm_kernel<64, false, false, true>), grid, block, 0, st, a); break;
+            case kBbb128Ilv:    hipLaunchKernelGGL((pconv_gemm_kernel<128, false, true>), grid, block, 0, st, a); break;
+            case kBbb128:       hipLaunchKernelGGL((pconv_gemm_kernel<128, false, false>), grid, block, 0, st, a); break;
+            case kBbb64Ilv:     hipLaunchKernelGGL((pconv_gemm_kernel<64, false, true>), grid, block, 0, st, a); break;
+            case kBbb64:        hipLaunchKernelGGL((pconv_gemm_kernel<64, false, false>), grid, block, 0, st, a); break;
+            default: return BBB_EINVAL;
         }
     }
-    if (ilv) hipLaunchKernelGGL((pconv_gemm_kernel<64, LRT, true>), grid, block, 0, st, a);
-    else     hipLaunchKernelGGL((pconv_gemm_kernel<64, LRT, false>), grid, block, 0, st, a);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
 namespace {
-constexpr int64_t kTicketBytes = 16384;         // arrival counters of up to 4096 items
+using pconv_plan::kTicketBytes;
 
-// The split of a LAYER's contraction: a function of the layer's geometry ONLY (not of the batch, the number of draws or how a
-// step is partitioned), so that every launch that computes an output element of this layer -- one draw alone, a 10-draw
-// launch, a work unit of a sharded step, one of G steps per launch, a batch-parallel shard -- adds the same partial sums in the
-// same order (cross-workgroup SPLIT form for small launches, in-workgroup SEQ form otherwise: same bits).
-// Which layers: few (pixel, 64-channel tile) groups and a long contraction -- a draw of such a layer is a handful of workgroups
-// each walking a long serial k loop (AlexNet conv4: 4 pixels x 4 tiles, 48 k tiles; conv5: 4 x 2, 32 tiles; measured one draw,
-// bs 512: 42 -> 28 us and 28 -> 17 us with four ranges, profiles/r03_notes.md section 2).  Layers with more groups (conv2: 48, conv3:
-// 24) fill the chip from a few hundred images on and keep the plain chain.
-int canonical_ksplit(const PConvArgs& a) {
-    const int ntl = (a.Cout + BN - 1) / BN;
-    const int64_t groups = (int64_t)a.Ho * a.Wo * ntl;
-    if (groups > 16) return 1;
-    // longest contraction of any pixel, in 32-k tiles (taps that can fall inside the image)
-    const int nr = a.kh < (a.H - 1) / a.dh + 1 ? a.kh : (a.H - 1) / a.dh + 1;
-    const int nq = a.kw < (a.W - 1) / a.dw + 1 ? a.kw : (a.W - 1) / a.dw + 1;
-    const int tiles = (a.Cin * nr * nq + BK - 1) / BK;
-    if (tiles < 16) return 1;
-    const int s = tiles / 8;                                             // >= 8 tiles per range
-    return s > 4 ? 4 : s;
-}
-
-// Scratch bytes the cross-workgroup form of this launch needs (0: the launch is too large for it and runs the SEQ form).
-int64_t split_scratch_bytes(const PConvArgs& a, int draws, bool lrt, int s) {
-    if (s <= 1) return 0;
-    const int ntl = (a.Cout + BN - 1) / BN;
-    const int64_t items = (int64_t)a.Ho * a.Wo * ((a.B + 63) / 64) * ntl * draws;
-    if (items > split_max_items(lrt)) return 0;
-    // tickets live in a FIXED region at the start of the scratch (split launches have < 512 items), so that launches of
-    // different sizes sharing one scratch buffer never put partial tiles where another launch expects zeroed tickets
-    return kTicketBytes + items * s * (lrt ? 2 : 1) * 64 * 64 * 4;
-}
-
+// The layer's split (pconv_plan.h: canonical_ksplit, split_scratch_bytes) applied to one launch's argument block.
 int split_setup(PConvArgs& a, int draws, bool lrt, int k_split, void* scratch, int64_t scratch_bytes) {
     if (k_split <= 1) return 0;
-    if (k_split != canonical_ksplit(a)) return BBB_EINVAL;               // the split is the layer's, not the caller's choice
+    const pconv_plan::Geom g = geom_of(a);
+    if (k_split != pconv_plan::canonical_ksplit(g)) return BBB_EINVAL;   // the split is the layer's, not the caller's choice
     a.ksplit = k_split;
-    const int64_t need = split_scratch_bytes(a, draws, lrt, k_split);
+    const int64_t need = pconv_plan::split_scratch_bytes(g, draws, lrt, k_split);
     if (need > 0 && scratch != nullptr) {
         if (scratch_bytes < need || (((uintptr_t)scratch) & 255u) != 0) return BBB_EINVAL;
         a.tickets = static_cast<int32_t*>(scratch);
@@ -387,13 +280,30 @@ int split_setup(PConvArgs& a, int draws, bool lrt, int k_split, void* scratch, i
 }
 }  // namespace
 
+extern "C" int bbb_conv2d_chwn_plan(const bbb_conv_desc_t* d, int lrt, int k_split, int has_scratch, int32_t* form, int32_t* bm,
+                                    int32_t* ilv, int64_t* items, int64_t* blocks) {
+    pconv_plan::Geom g;
+    int rc = pconv_plan::describe(d, &g);
+    if (rc != 0) return rc;
+    if (lrt && (d->w_draw_stride != 0 || d->b_draw_stride != 0)) return BBB_EINVAL;     // as bbb_lrt_conv2d_chwn_splitk_fwd
+    pconv_plan::Plan pl;
+    if ((rc = pconv_plan::plan(g, d->draws, lrt != 0, k_split, has_scratch != 0, &pl)) != 0) return rc;
+    if (form) *form = pl.form;
+    if (bm) *bm = pl.bm;
+    if (ilv) *ilv = pl.ilv;
+    if (items) *items = pl.items;
+    if (blocks) *blocks = pl.blocks;
+    return 0;
+}
+
 extern "C" int64_t bbb_conv2d_chwn_splitk_scratch(const bbb_conv_desc_t* d, int lrt, int32_t* k_split) {
     PConvArgs a = {};
     if (k_split) *k_split = 1;
     if (fill(d, a) != 0) return 0;
-    const int s = canonical_ksplit(a);
+    const pconv_plan::Geom g = geom_of(a);
+    const int s = pconv_plan::canonical_ksplit(g);
     if (k_split) *k_split = s;
-    return split_scratch_bytes(a, d->draws, lrt != 0, s);
+    return pconv_plan::split_scratch_bytes(g, d->draws, lrt != 0, s);
 }
 
 extern "C" int bbb_conv2d_chwn_splitk_fwd(const bbb_conv_desc_t* d, const float* x, const float* w, const float* bias, float* y,

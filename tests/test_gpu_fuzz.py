@@ -1,11 +1,13 @@
 """Seeded random-geometry sweep of the three implicit-GEMM kernels (NCHW fp32, batch-innermost fp32, batch-innermost
 bf16) against the fp64 oracle convolution: ragged channel / batch tiles, strides, dilations, asymmetric kernels and
-paddings larger than the kernel reach.  Tolerances as in test_gpu_kernels.py / test_gpu_bf16.py.  Run with -m gpu."""
+paddings larger than the kernel reach.  Tolerances as in test_gpu_kernels.py / test_gpu_bf16.py.  The same geometries go through the
+two LRT kernels (NCHW and batch-innermost) with their moments, under the rounded tier of tests/pconv_contract.py.  Run with -m gpu."""
 import numpy as np
 import pytest
 import torch
 
 import bbb_numpy as O
+import pconv_contract as PC
 
 pytestmark = pytest.mark.gpu
 
@@ -82,3 +84,25 @@ def test_random_geometry_all_kernels(c):
             tol = 2e-5 * mag + 2e-6 + np.abs(want) * 2.0 ** -8
             err = np.abs(y16[e].cpu().numpy() - want)
             assert (err <= tol).all(), f"{name} draw {e}: excess {(err - tol).max():.3e}"
+
+
+@pytest.mark.parametrize("c", CASES, ids=[f"case{i}" for i in range(len(CASES))])
+def test_random_geometry_lrt_kernels(c):
+    """The LRT column: act_mu, act_var and the sampled, activated output of ops.lrt_conv2d_chwn_forward and ops.lrt_conv2d_forward,
+    every element against the float64 reference of one launch (pconv_contract.reference / check_rounded)."""
+    from bbb_hip import ops
+    B, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, E, xs, act = c
+    a = None if act == "none" else act
+    lc = PC.Case("fuzz%d" % CASES.index(c), "lrt", B, Cin, H, W, Cout, (kh, kw), (sh, sw), (ph, pw), (dh, dw), E=E,
+                 x=("div", E, 0) if xs and E > 1 else ("draw",), act=a, moments=True, seed=1000 + CASES.index(c))
+    o = PC.operands(lc, "rounded")
+    ref = PC.reference(lc, o)
+    dev = lambda v: torch.from_numpy(v).cuda()
+    geom = ((sh, sw), (ph, pw), (dh, dw))
+    args = (dev(o["w"]), dev(o["w_var"]), dev(o["b"]), dev(o["b_var"]), PC.SEED, PC.CALL0, PC.STREAM) + geom
+    y, am, av = ops.lrt_conv2d_chwn_forward(dev(o["x"]), *args, want_moments=True, act=a, x_div=lc.x[1] if lc.x[0] == "div" else 1, n_slabs=E)
+    PC.check_rounded(lc, dict(y=y.cpu().numpy(), act_mu=am.cpu().numpy(), act_var=av.cpu().numpy()), ref)
+    xn = dev(np.ascontiguousarray(np.stack([o["x"][lc.slab(e)[0]] for e in range(E)]).transpose(0, 4, 1, 2, 3)))      # [E, B, Cin, H, W]
+    y, am, av = ops.lrt_conv2d_forward(xn, *args, want_moments=True, act=a)
+    back = lambda t: t.permute(0, 2, 3, 4, 1).cpu().numpy()
+    PC.check_rounded(lc, dict(y=back(y), act_mu=back(am), act_var=back(av)), ref)
