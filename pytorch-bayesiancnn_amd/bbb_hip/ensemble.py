@@ -14,6 +14,7 @@ all_gather of [B*C + 1] floats (the block + its share of the KL sum) over RCCL i
 in rank order -- every rank ends with the same bits.
 """
 import math
+import types
 import weakref
 
 import torch
@@ -21,6 +22,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, rng, _lib
+from .infer_walk import (BAYES_FORMS, ChwnPartition, ChwnPlan, ChwnStep, chwn_partition, conv_flops,  # noqa: F401
+                         _act_name, _chwn_steps, _chwn_walk, _run)
 
 try:
     from layers.bbb import _BBBLayer, BBBConv2d as _BBBConv, BBBLinear as _BBBLin
@@ -189,10 +192,6 @@ class Timers:
         return agg
 
 
-def _run(timers, tag, info, fn):
-    return timers.bracket(tag, info, fn) if timers is not None else fn()
-
-
 def _sample_all(layers, draws, seed, call0, timers=None, eps=None, tm=()):
     """One fused launch (per <=16 tensors) for every BBB layer: -> ({layer: (w, b)}, kl).  tm: layers whose conv weights come out
     TAP-MAJOR, [draws, Cout, kh * kw, Cin] (ops.sample_weights_tm: the operand layout of ops.conv2d_c8x3_forward; inference)."""
@@ -294,27 +293,6 @@ def _variances_all(layers, timers=None):
     return out, kl
 
 
-def _act_name(mod):
-    if isinstance(mod, nn.ReLU):
-        return "relu"
-    if isinstance(mod, nn.Softplus) and mod.beta == 1 and mod.threshold == 20:
-        return "softplus"
-    return None
-
-
-def conv_flops(B, Cin, H, W, Cout, kh, kw, stride, padding, dilation, draws, contractions=1):
-    """(useful, im2col) FLOPs of a conv layer: useful counts only kernel taps that land inside the image."""
-    sh, sw = ops._pair(stride)
-    ph, pw = ops._pair(padding)
-    dh, dw = ops._pair(dilation)
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    vr = sum(1 for o in range(ho) for r in range(kh) if 0 <= o * sh - ph + r * dh < H)
-    vq = sum(1 for o in range(wo) for q in range(kw) if 0 <= o * sw - pw + q * dw < W)
-    base = 2.0 * contractions * draws * B * Cout * Cin
-    return base * vr * vq, base * ho * wo * kh * kw
-
-
 def _chwn_ok(net, x, any_batch=True):
     """The batch-innermost fast path handles: 4-d input, no autograd, and only module kinds it knows how to run in that layout
     (Bayesian layers, ReLU/Softplus, MaxPool2d without padding, FlattenLayer that flattens whole images).  Batch sizes that are
@@ -376,477 +354,129 @@ def _check_precision(precision, net, x, fast_path_allowed, dropin=False):
         raise _lib.BBBHipError("the drop-in loop in bf16 covers BBB (non-LRT) models; " + _BF16_LRT_HINT)
 
 
+def chwn_plan(net, x_shape, draws, precision="fp32", units=None, groups=1, share=None):
+    """Which launch every layer of `net` takes on the batch-innermost inference forward (_mc_logits_chwn) for an input of
+    x_shape under the current LaunchConfig: the list of ChwnStep, or None where that forward does not apply and its callers fall
+    back.  Host only: works on a CPU model (like ops.bf16_fwd_plan / ops.fp32_fwd_plan for one launch).  Raises what the forward
+    raises for a partition it refuses."""
+    children = flat_children(net)
+    if len(x_shape) != 4 or not _chwn_mods_ok(children):
+        return None
+    part = chwn_partition(tuple(x_shape), draws, 0, precision == "bf16", units, groups, share, 1)
+    x_shape = (x_shape[0] + part.pad,) + tuple(x_shape[1:])
+    plan = _chwn_steps(children, x_shape, part, precision, ops.current_config(), draws)
+    return None if plan is None else plan.steps
+
+
+def _cached_plan(net, children, x_shape, part, precision, cfg, draws, n_slabs):
+    """_chwn_steps, remembered in the model's structure cache (the eager paths are host-bound: the rules are asked once per model,
+    shape, partition and LaunchConfig instead of on every forward)."""
+    cache = _structure(net).setdefault("chwn_plans", {})
+    key = (x_shape, precision, draws, n_slabs, part.E, part.B, part.nblk, part.x_div, cfg.key())
+    if key not in cache:
+        if len(cache) > 64:
+            cache.clear()
+        cache[key] = _chwn_steps(children, x_shape, part, precision, cfg, draws, n_slabs)
+    return cache[key]
+
+
+def _chwn_operands(c, bbb, lrt, bf16):
+    """Every launch in front of the walk, driven by the plan: the weight draws of the BBB layers (tap-major for the layers of
+    plan.tm) or the variances of the LRT layers, with the KL; the bf16 (W_mu, sigma^2) rows of bf16 LRT layers; the tap-major LRT
+    weights; the space-to-depth image and weights of the first layer, or the input as batch-innermost blocks.  Fills c."""
+    plan, part, timers, x = c.plan, c.part, c.timers, c.x
+    c.kl, c.sampled, c.variances, c.lrt_b16, c.lrt_tm, c.xs2d, c.w_s2d, c.xt = None, {}, {}, {}, {}, None, None, None
+    if bbb:
+        c.sampled, c.kl = _sample_all_bf16(bbb, part.n_draws, c.seed, part.call0, timers) if bf16 else \
+            _sample_all(bbb, part.n_draws, c.seed, part.call0, timers, tm=plan.tm)
+    if lrt:
+        c.variances, k2 = _variances_all(lrt, timers)
+        c.kl = k2 if c.kl is None else c.kl + k2
+    if plan.bf16_lrt:                                             # LRT layer -> bf16 (W_mu, sigma^2) rows: one conversion launch per step
+        srcs = []
+        for l in lrt:
+            srcs += [l.W_mu, c.variances[l][0]]
+        rows = _run(timers, "layout", None, lambda: ops.lrt_weights_bf16(srcs))
+        c.lrt_b16 = {l: (rows[2 * k], rows[2 * k + 1]) for k, l in enumerate(lrt)}
+    for l in (l for l in lrt if plan.lrt_mode and l in plan.tm):  # LRT layer -> (W_mu, W_sigma^2) tap-major [Cout, taps, Cin]
+        wm, wv = l.W_mu.detach(), c.variances[l][0]
+        if wm.dim() == 2:
+            c.lrt_tm[l] = (wm.reshape(wm.shape[0], 1, wm.shape[1]), wv.reshape(wv.shape[0], 1, wv.shape[1]))
+        else:
+            c.lrt_tm[l] = (_run(timers, "layout", None, lambda wm=wm: ops.w_tap_major(wm.unsqueeze(0))[0]),
+                           _run(timers, "layout", None, lambda wv=wv: ops.w_tap_major(wv.unsqueeze(0))[0]))
+    l0, nblk = plan.s2d_first, part.nblk
+    if l0 is not None:
+        c.xs2d = _run(timers, "layout", None, lambda: ops.s2d_c8s3(x, nblk, l0.kernel_size, l0.stride, l0.padding, squares=plan.lrt_mode))   # [nblk, 3|6, C'/8, Hb, Wb, B, 8]
+        if plan.lrt_mode:
+            c.w_s2d = (_run(timers, "layout", None, lambda: ops.w_s2d_tap_major(l0.W_mu.detach().unsqueeze(0), l0.stride)[0]),
+                       _run(timers, "layout", None, lambda: ops.w_s2d_tap_major(c.variances[l0][0].unsqueeze(0), l0.stride)[0]))
+        else:
+            c.w_s2d = _run(timers, "layout", None, lambda: ops.w_s2d_tap_major(c.sampled[l0][0], l0.stride))              # [n_draws, Cout, m*m, C']
+    elif c.partitioned:                                         # [S, C, H, W, B/S]: one batch-innermost block per slice / per step
+        c.xt = ops.to_batch_innermost_bf16_slices(x, nblk) if bf16 else ops.to_batch_innermost_slices(x, nblk)
+    else:
+        c.xt = (ops.to_batch_innermost_bf16(x) if bf16 else ops.to_batch_innermost(x)).unsqueeze(0)   # [1, C, H, W, B], shared by all draws
+
+
 def _mc_logits_chwn(net, x, draws, seed, call0, timers=None, streams=1, precision="fp32", units=None, b_offset=0, groups=1,
                     share=None):
     """Inference path of mc_logits in the batch-innermost layout ([E, C, H, W, B]): pixel-major GEMMs that
-    skip padding taps, activation fused into the GEMM epilogue, pooling on contiguous image vectors.
-    units = (S, lo, hi): instead of `draws` whole draws starting at call0, run the work units lo..hi-1 of the draw-major
-    (draw, batch slice) grid with S slices per draw (call0 = the call index of draw 0); returns logits [hi-lo, C, B/S].
-    b_offset: global index of x's first image (batch-parallel shards): LRT activation noise is keyed by the global image.
-    groups = G > 1: x holds G batches back to back ([G * B, C, H, W]) and the launches run G consecutive Monte-Carlo steps of
-    `draws` forwards each -- slab g * draws + j = draw j of step g, on batch g, under noise call call0 + g * draws + j, i.e.
-    exactly what G separate steps would compute (GraphedMC steps > 1); returns logits [G * draws, C, B].
-    share = (D, off): one rank's part of a group of steps (group_share): `draws` consecutive slabs of the draw-major (step, draw)
-    enumeration with D draws per step, the first being draw `off` of its step; x holds the ceil((draws + off) / D) batches they
-    touch, call0 = the call index of the first local slab; returns logits [draws, C, B]."""
-    layers = bayesian_layers(net)
-    bbb = [l for l in layers if isinstance(l, _BBBLayer)]
-    lrt = [l for l in layers if isinstance(l, _LRTLayer)]
-    kl, sampled, variances = None, {}, {}
-    bf16 = precision == "bf16"
-    E, B = draws, x.shape[0]
-    ukw = {}
-    G = int(groups)
+    skip padding taps, activation fused into the GEMM epilogue, pooling on contiguous image vectors.  -> (logits [E, C, B], kl), or
+    None: the caller falls back.  The pieces: chwn_partition (units / groups / share: how the step is cut up, what is returned),
+    _chwn_steps (which launch every layer takes; ensemble.chwn_plan asks it without a device), _chwn_operands (the launches in front
+    of the walk) and _chwn_walk (one loop over the plan's steps, one launch function per form).
+    b_offset: global index of x's first image (batch-parallel shards): LRT activation noise is keyed by the global image."""
+    children = flat_children(net)
+    bbb = [l for l in bayesian_layers(net) if isinstance(l, _BBBLayer)]
+    lrt = [l for l in bayesian_layers(net) if isinstance(l, _LRTLayer)]
+    bf16, cfg = precision == "bf16", ops.current_config()
+    part = chwn_partition(tuple(x.shape), draws, call0, bf16, units, groups, share, streams)
     rows_real = None
-    if B % 4 != 0 and not bf16 and G == 1 and share is None and (units is None or units[0] <= 1):
-        # an odd batch stays on the batch-innermost kernels: zero images fill it up to the next multiple of 4 (every image is
-        # its own GEMM column -- BBB weights are shared, LRT noise is keyed by the global image index -- so the real images'
-        # results are those of an unpadded run), and their output rows (they come last, also behind a flatten that cuts images
-        # into several rows) are dropped again.  One small copy instead of the ~2x slower reference-layout kernels.
+    if part.pad:
         rows_real = output_rows(net, tuple(x.shape))
-        x = torch.cat([x, x.new_zeros((-B % 4,) + tuple(x.shape[1:]))], dim=0)
-        B = x.shape[0]
-    if G > 1:
-        if units is not None and units[0] > 1:
-            raise _lib.BBBHipError("several steps per launch and work units do not combine")
-        if B % G or (B // G) % (8 if bf16 else 4):
-            raise _lib.BBBHipError("several steps per launch: every batch must hold a multiple of 4 (bf16: 8) images")
-        B = B // G
-        E = G * draws
-        streams = 1
-    x_div0, x_off0, nb = (draws if (G > 1 and draws > 1) else 1), 0, G
-    if share is not None:
-        if G > 1 or (units is not None and units[0] > 1):
-            raise _lib.BBBHipError("a share of a group of steps combines with neither work units nor whole groups")
-        D, off = int(share[0]), int(share[1])
-        nb = -(-(draws + off) // D)
-        if not 0 <= off < D or B % nb or (B // nb) % (8 if bf16 else 4):
-            raise _lib.BBBHipError("share of a group of steps: x must hold the batches it touches, multiples of 4 (bf16: 8) images")
-        B = B // nb
-        x_div0, x_off0 = (D, off) if D > 1 else (1, 0)
-        streams = 1
-    if units is not None and units[0] > 1:
-        S, lo, hi = units
-        if B % S or (B // S) % (8 if bf16 else 4):
-            raise _lib.BBBHipError("work units: batch slices must hold a multiple of 4 (bf16: 8) images")
-        E, B = hi - lo, B // S
-        j_lo = lo // S
-        n_draws = (hi - 1) // S - j_lo + 1                     # weight sets this rank needs
-        call0 = call0 + j_lo
-        ukw = dict(units=(S, lo % S), n_units=E)
-        streams = 1
-    else:
-        S, n_draws = 1, E
-    bf16_lrt = bf16 and bool(lrt)
-    if bf16 and (B % 8 != 0 or (lrt and not ops.current_config().bf16_lrt)):
+        x = torch.cat([x, x.new_zeros((part.pad,) + tuple(x.shape[1:]))], dim=0)
+    if bf16 and (part.B % 8 != 0 or (lrt and not cfg.bf16_lrt)):
         raise _lib.BBBHipError("the bf16 path covers BBB (non-LRT) layers and batch sizes that are multiples of 8; " + _BF16_LRT_HINT)
-    if bf16_lrt:
+    if bf16 and lrt:
         if bbb:
             raise _lib.BBBHipError("bf16: a model mixes BBB and LRT layers (all one kind or the other)")
-        if ukw or share is not None or b_offset:
+        if part.ukw or share is not None or b_offset:
             raise _lib.BBBHipError("bf16 on LRT models: no work units, shares of a group of steps or batch offsets")
-    # split-bf16 mode: BBB layers with Cin % 32 == 0 (never the first one: its input is the caller's fp32 batch) run on the
-    # MFMA-ready-operand kernel (ops.conv2d_c8x3_forward) -- their input travels channel-interleaved and already split ("c8 S3"),
-    # their weights come tap-major from the parameter pass.  Which kernel a layer takes is a property of the LAYER (not of the
-    # launch size), so that a work unit, a share of a group of steps and the whole step are the same bits.
-    children = flat_children(net)
-    last_bayes = max((i for i, m in enumerate(children) if isinstance(m, (_BBBLayer, _LRTLayer))), default=-1)
-    tail_is_last = last_bayes == len(children) - 1
-    split_any = (precision == "bf16x3" or ops.current_config().gemm_mode == "bf16x3") and not bf16 and tail_is_last
-    split_mode = split_any and not lrt and bool(bbb)
-    # ... LRT models (every Bayesian layer local-reparameterisation) the same way, on the kernel's LRT form: six-plane slabs (values +
-    # squares), W_mu / W_sigma^2 tap-major (rearranged once per launch: LRT weights do not depend on the draw)
-    lrt_mode = split_any and bool(lrt) and not bbb and ops.current_config().c8x3
-    c8_set = set()
-    if lrt_mode:
-        for l in lrt[1:]:
-            cin = l.in_channels if isinstance(l, _LRTConv) else l.in_features
-            cout = l.out_channels if isinstance(l, _LRTConv) else l.out_features
-            if ops.c8x3_layer_ok(cin, cout, is_logits=(l is children[last_bayes])):
-                c8_set.add(l)
-    if split_mode and ops.current_config().c8x3:
-        for l in bbb[1:]:
-            cin = l.in_channels if isinstance(l, _BBBConv) else l.in_features
-            cout = l.out_channels if isinstance(l, _BBBConv) else l.out_features
-            if ops.c8x3_layer_ok(cin, cout, is_logits=(l is children[last_bayes])):
-                c8_set.add(l)
-    # ... and a strided first layer on few channels (AlexNet conv1) joins the chain in space-to-depth form (ops.s2d_layer_ok): its block
-    # image is cut from the caller's NCHW batch in c8 S3 directly, its dense weight draws are rearranged by one small launch
-    s2d_first = None
-    first_l = bbb[0] if (split_mode and bbb) else (lrt[0] if (lrt_mode and lrt) else None)
-    if first_l is not None and ops.current_config().c8x3 and ops.current_config().c8x3_s2d and children and children[0] is first_l and \
-            isinstance(first_l, (_BBBConv, _LRTConv)) and first_l not in c8_set and x.dim() == 4 and last_bayes != 0:
-        l0 = first_l
-        # (an LRT first layer whose input AND weights are the same for all E > 1 draws stays on the fp32 kernel: it runs its two
-        # contractions ONCE and samples E times -- the block form would run them E times: 6.1 against 5.1 M samples/s at bs 512 x 10)
-        # -- for EVERY partition of such a step (work units, shares of a group): which kernel a layer takes is a property of the step)
-        lrt_shared_first = lrt_mode and int(draws) > 1
-        if not lrt_shared_first and \
-                ops.s2d_layer_ok(l0.in_channels, l0.out_channels, l0.kernel_size, l0.stride, l0.padding, l0.dilation, x.shape[2], x.shape[3]):
-            s2d_first = l0
-    if bbb:
-        sampled, kl = _sample_all_bf16(bbb, n_draws, seed, call0, timers) if bf16 else _sample_all(bbb, n_draws, seed, call0, timers, tm=c8_set)
-    if lrt:
-        variances, k2 = _variances_all(lrt, timers)
-        kl = k2 if kl is None else kl + k2
-    lrt_b16 = {}                                                  # LRT layer -> bf16 (W_mu, sigma^2) rows: one conversion launch per step
-    if bf16_lrt:
-        srcs = []
-        for l in lrt:
-            srcs += [l.W_mu, variances[l][0]]
-        rows = _run(timers, "layout", None, lambda: ops.lrt_weights_bf16(srcs))
-        lrt_b16 = {l: (rows[2 * k], rows[2 * k + 1]) for k, l in enumerate(lrt)}
-    to_cb = ops.to_batch_innermost_bf16 if bf16 else ops.to_batch_innermost
-    nblk = (S if S > 1 else nb) if (S > 1 or G > 1 or share is not None) else 1
-    xs2d = w_s2d = None
-    lrt_tm = {}                                                   # LRT layer -> (W_mu, W_sigma^2) tap-major [Cout, taps, Cin]
-    for l in (c8_set if lrt_mode else ()):
-        wm = l.W_mu.detach()
-        wv = variances[l][0]
-        if wm.dim() == 2:
-            lrt_tm[l] = (wm.reshape(wm.shape[0], 1, wm.shape[1]), wv.reshape(wv.shape[0], 1, wv.shape[1]))
-        else:
-            lrt_tm[l] = (_run(timers, "layout", None, lambda wm=wm: ops.w_tap_major(wm.unsqueeze(0))[0]),
-                         _run(timers, "layout", None, lambda wv=wv: ops.w_tap_major(wv.unsqueeze(0))[0]))
-    if s2d_first is not None:
-        l0 = s2d_first
-        xt = None
-        xs2d = _run(timers, "layout", None, lambda: ops.s2d_c8s3(x, nblk, l0.kernel_size, l0.stride, l0.padding, squares=lrt_mode))   # [nblk, 3|6, C'/8, Hb, Wb, B, 8]
-        if lrt_mode:
-            w_s2d = (_run(timers, "layout", None, lambda: ops.w_s2d_tap_major(l0.W_mu.detach().unsqueeze(0), l0.stride)[0]),
-                     _run(timers, "layout", None, lambda: ops.w_s2d_tap_major(variances[l0][0].unsqueeze(0), l0.stride)[0]))
-        else:
-            w_s2d = _run(timers, "layout", None, lambda: ops.w_s2d_tap_major(sampled[l0][0], l0.stride))              # [n_draws, Cout, m*m, C']
-    elif nblk > 1 or S > 1 or G > 1 or share is not None:       # [S, C, H, W, B/S]: one batch-innermost block per slice / per step
-        xt = ops.to_batch_innermost_bf16_slices(x, nblk) if bf16 else ops.to_batch_innermost_slices(x, nblk)
+    E = part.E
+    nsplit = 1 if timers is not None else max(1, min(int(part.streams), E))
+    bounds = [draw_range(E, r, nsplit) for r in range(nsplit)]
+    plans = [_cached_plan(net, children, tuple(x.shape), part, precision, cfg, draws, e1 - e0) for e0, e1 in bounds]
+    if any(p is None for p in plans):
+        return None                                              # (decided before anything is launched)
+    c = types.SimpleNamespace(plan=plans[0], part=part, timers=timers, x=x, seed=seed, b_offset=b_offset, bf16=bf16,
+                              bf16x3=True if precision == "bf16x3" else None,        # None: the current LaunchConfig's gemm_mode decides
+                              partitioned=part.nblk > 1 or part.S > 1 or int(groups) > 1 or share is not None)
+    _chwn_operands(c, bbb, lrt, bf16)
+    n_out = c.plan.n_out
+    c.logits_buf = torch.empty((E, n_out, part.B), dtype=torch.float32, device=x.device) if n_out is not None else None
+    stats["launch"] = "layers"
+    if nsplit == 1:
+        out = _chwn_walk(c, plans[0].steps, 0, E)
     else:
-        xt = to_cb(x).unsqueeze(0)                              # [1, C, H, W, B], shared by all draws
-    n_out = getattr(children[last_bayes], "out_features", None) if tail_is_last else None
-    logits_buf = torch.empty((E, n_out, B), dtype=torch.float32, device=x.device) if n_out is not None else None
-
-    bf16x3 = True if precision == "bf16x3" else None        # None: the current LaunchConfig's gemm_mode decides
-    # split-bf16 mode, steps large enough that every conv launch takes that kernel: the activations between the layers travel in
-    # the split format S3 (three bf16 planes holding the exact fp32 values; ops.conv2d_chwn_forward x_s3 / out_s3) -- each
-    # element is cut into its pieces ONCE, by the launch that produces it, instead of by every workgroup that stages it
-    s3_chain = split_mode and not c8_set and B % 8 == 0 and E * B >= ops.current_config().s3_min_images
-
-    def run(e0, e1):
-        """Layers for draws [e0, e1) on the current stream -> logits [e1-e0, C, B] (or None: fall back)."""
-        nonlocal logits_buf
-        B = xs2d.shape[5] if xs2d is not None else xt.shape[-1]
-        Es = e1 - e0
-        h = xt
-        s3 = False                     # h is an S3 tensor [E, 3, C, H, W, B] (split-bf16 chain)
-        c8s3 = False                   # h is a c8 S3 tensor [E, 3, C / 8, H, W, B, 8] (split-bf16 chain over MFMA-ready operands)
-        boff = int(b_offset)           # global index of the first local "image" (rows multiply at a flatten that cuts images up)
-        per_slice = bool(ukw)          # work units: until the first Bayesian layer, h is one block per batch slice
-        x_div, x_off = x_div0, x_off0  # several steps per launch: the first layer's slab e reads batch (e + x_off) // x_div
-        i = 0
-        while i < len(children):
-            mod = children[i]
-            nxt = children[i + 1] if i + 1 < len(children) else None
-            act = _act_name(nxt) if nxt is not None else None
-            if mod is s2d_first and i == 0 and lrt_mode:
-                # an LRT first layer in space-to-depth form (values and squares of the block image; no pooled form: the pool follows)
-                wm_, wv_ = w_s2d
-                m_ = int(round(wm_.shape[1] ** 0.5))
-                zb = ops.s2d_zero_border(mod.in_channels, mod.kernel_size, mod.stride, mod.padding, x.shape[2], x.shape[3])
-                ukw3 = dict(ukw, x_per_slice=True) if ukw else ({"x_div": x_div, "x_off": x_off, "n_slabs": Es} if x_div > 1 else {"n_slabs": Es})
-                x_div = 1
-                per_slice = False
-                fl = conv_flops(B, mod.in_channels, x.shape[2], x.shape[3], wm_.shape[0], *mod.kernel_size, mod.stride, mod.padding, mod.dilation, Es, 2) \
-                    if timers is not None else None
-                h = _run(timers, "lrt_gemm", fl, lambda wm_=wm_, wv_=wv_, m_=m_, act=act, ukw3=ukw3, zb=zb, mod=mod, boff=boff:
-                         ops.lrt_conv2d_c8x3_forward(xs2d, wm_, wv_, mod.bias_mu if mod.use_bias else None, variances[mod][1], (m_, m_), seed,
-                                                     call0 + e0, mod._stream_base + 2, 1, 0, 1, act=act, b_offset=boff, zero_border=zb, **ukw3))
-                c8s3 = True
-                i += (1 if act is not None else 0) + 1
-                continue
-            if mod is s2d_first and i == 0:
-                # the first layer in space-to-depth form: an m x m layer, stride 1, no padding, on the block image; [activation ->]
-                # MaxPool2d(2, 2) inside the launch (every window walks the same taps: the parallel-window form)
-                w, b = w_s2d, sampled[mod][1]
-                if not ukw:
-                    w = w[e0:e1]
-                    b = None if b is None else b[e0:e1]
-                m_ = int(round(w.shape[2] ** 0.5))
-                g_ = ops.s2d_geometry(mod.in_channels, mod.kernel_size, mod.stride, mod.padding, mod.dilation, x.shape[2], x.shape[3])
-                pool_at = i + (2 if act is not None else 1)
-                pool_mod = children[pool_at] if pool_at < len(children) and isinstance(children[pool_at], nn.MaxPool2d) else None
-                fuse_pool = pool_mod is not None and g_[4] % 2 == 0 and g_[5] % 2 == 0 and ops.is_pool_2x2(pool_mod)
-                ukw3 = dict(ukw, x_per_slice=True) if ukw else ({"x_div": x_div, "x_off": x_off} if x_div > 1 else {})
-                x_div = 1
-                per_slice = False
-                fl = conv_flops(B, mod.in_channels, x.shape[2], x.shape[3], w.shape[1], *mod.kernel_size, mod.stride, mod.padding, mod.dilation, Es) \
-                    if timers is not None else None
-                zb = ops.s2d_zero_border(mod.in_channels, mod.kernel_size, mod.stride, mod.padding, x.shape[2], x.shape[3])
-                h = _run(timers, "conv_gemm", fl, lambda w=w, b=b, m_=m_, act=act, ukw3=ukw3, fuse_pool=fuse_pool, zb=zb:
-                         ops.conv2d_c8x3_forward(xs2d, w, b, (m_, m_), 1, 0, 1, act=act, pool=fuse_pool, zero_border=zb, **ukw3))
-                c8s3 = True
-                i += (1 if act is not None else 0) + (1 if fuse_pool else 0) + 1
-                continue
-            if isinstance(mod, (_BBBLayer, _LRTLayer)):
-                is_conv = isinstance(mod, (_BBBConv, _LRTConv))
-                geom = (mod.stride, mod.padding, mod.dilation) if is_conv else (1, 0, 1)
-                use_c8 = mod in c8_set
-                if c8s3 and not use_c8:
-                    h, c8s3 = ops.c8s3_to_f32(h), False
-                if use_c8 and not c8s3:
-                    hf = h if is_conv else h.reshape(h.shape[0], mod.in_features, 1, 1, -1)
-                    if hf.dim() != 5 or hf.shape[-1] != B:
-                        return None
-                    h = _run(timers, "layout", None, lambda hf=hf: ops.c8s3_from_f32(hf, squares=lrt_mode))
-                    c8s3 = True
-                if c8s3:
-                    h5 = h if is_conv else h.reshape(h.shape[0], h.shape[1], mod.in_features // 8, 1, 1, h.shape[5], 8)
-                    if h5.shape[5] != B or h5.shape[2] * 8 != (mod.in_channels if is_conv else mod.in_features):
-                        return None
-                elif s3:
-                    h5 = h if is_conv else h.reshape(h.shape[0], 3, mod.in_features, 1, 1, -1)
-                else:
-                    h5 = h if is_conv else h.reshape(h.shape[0], mod.in_features, 1, 1, -1)
-                c8 = bf16 and h5.dim() == 6                      # channel-interleaved [E, C / 8, H, W, B, 8] (ops.to_c8), written by the layer before
-                if not c8s3 and (h5.dim() != (6 if (s3 or c8) else 5) or h5.shape[4 if c8 else -1] != B):
-                    return None                                  # flatten quirk etc.: caller falls back
-                ukw2 = dict(ukw, x_per_slice=per_slice) if ukw else ({"x_div": x_div, "x_off": x_off} if x_div > 1 else {})
-                per_slice = False
-                x_div = 1
-                if isinstance(mod, _BBBLayer) and bf16:
-                    w, b = sampled[mod]
-                    if not ukw:
-                        w = w[e0:e1]
-                        b = None if b is None else b[e0:e1]
-                    ckk = (mod.in_channels, *mod.kernel_size) if is_conv else (mod.in_features, 1, 1)
-                    fl = conv_flops(B, h5.shape[1] * (8 if c8 else 1), h5.shape[2], h5.shape[3], w.shape[1], ckk[1], ckk[2], *geom, Es) \
-                        if timers is not None else None
-                    is_logits = logits_buf is not None and i == last_bayes and not is_conv
-                    dst = logits_buf[e0:e1] if is_logits else None
-                    tapm = is_conv and ops.bf16_tap_major(tuple(mod.W_mu.shape))
-                    of32 = i == last_bayes and tail_is_last
-                    # [activation ->] MaxPool2d after a first layer with a short contraction: one launch (ops.bf16_pool_fusion_ok)
-                    pool_at = i + (2 if act is not None else 1)
-                    pool_mod = children[pool_at] if pool_at < len(children) and isinstance(children[pool_at], nn.MaxPool2d) else None
-                    fuse_pool = is_conv and ops.bf16_pool_fusion_ok(ckk, tapm, of32, pool_mod, tuple(h5.shape), geom, Es)
-                    pool_ks = (pool_mod.kernel_size, pool_mod.stride if pool_mod.stride is not None else pool_mod.kernel_size) if fuse_pool else None
-                    # the pooled first layer writes its output channel-interleaved when the layer that reads it has the strip form over
-                    # that layout (3Conv3FC conv1 + pool1 -> conv2; ops.bf16_c8_input_ok): same values, 8 channels of an image adjacent
-                    out_c8 = False
-                    nb = children[pool_at + 1] if (fuse_pool and pool_at + 1 < len(children)) else None
-                    if isinstance(nb, _BBBConv) and w.shape[1] % 8 == 0 and dst is None:
-                        hw = [(h5.shape[2 + a] + 2 * _p2(geom[1])[a] - _p2(geom[2])[a] * (ckk[1 + a] - 1) - 1) // _p2(geom[0])[a] + 1 for a in (0, 1)]
-                        hw = [(v - _p2(pool_ks[0])[a]) // _p2(pool_ks[1])[a] + 1 for a, v in enumerate(hw)]
-                        out_c8 = ops.bf16_c8_input_ok((nb.in_channels, *nb.kernel_size), (nb.stride, nb.padding, nb.dilation),
-                                                      ops.bf16_tap_major(tuple(nb.W_mu.shape)), pool_at + 1 == last_bayes and tail_is_last,
-                                                      (hw[0], hw[1], B), Es)
-                    # (operands bound as defaults: bench.py's LaunchRecorder replays these closures after the loop has moved on)
-                    y = _run(timers, "conv_gemm", fl,
-                             lambda h5=h5, w=w, b=b, ckk=ckk, geom=geom, act=act, dst=dst, ukw2=ukw2, tapm=tapm, of32=of32, pool_ks=pool_ks,
-                             out_c8=out_c8:
-                             ops.conv2d_chwn_bf16_forward(h5, w, b, ckk, *geom, act=act, out_f32=of32, out=dst, tap_major=tapm,
-                                                          pool=pool_ks, out_c8=out_c8, **ukw2))
-                    if fuse_pool:
-                        i += 1                                   # the pooling module is done too
-                elif use_c8 and lrt_mode:
-                    wm_, wv_ = lrt_tm[mod]
-                    ks = mod.kernel_size if is_conv else (1, 1)
-                    fl = conv_flops(B, h5.shape[2] * 8, h5.shape[3], h5.shape[4], wm_.shape[0], ks[0], ks[1], *geom, Es, 2) if timers is not None else None
-                    is_logits = logits_buf is not None and i == last_bayes and not is_conv
-                    of32 = i == last_bayes
-                    dst = logits_buf[e0:e1] if is_logits else None
-                    ukw3 = {k: v for k, v in ukw2.items() if k != "x_per_slice"}
-                    if not ukw:
-                        ukw3["n_slabs"] = Es
-                    y = _run(timers, "lrt_gemm", fl, lambda h5=h5, wm_=wm_, wv_=wv_, ks=ks, geom=geom, act=act, dst=dst, ukw3=ukw3, of32=of32, mod=mod, boff=boff:
-                             ops.lrt_conv2d_c8x3_forward(h5, wm_, wv_, mod.bias_mu if mod.use_bias else None, variances[mod][1], ks, seed,
-                                                         call0 + e0, mod._stream_base + 2, *geom, act=act, out_f32=of32, out=dst, b_offset=boff,
-                                                         **ukw3))
-                    c8s3 = not of32
-                elif use_c8:
-                    w, b = sampled[mod]
-                    if not ukw:
-                        w = w[e0:e1]
-                        b = None if b is None else b[e0:e1]
-                    ks = mod.kernel_size if is_conv else (1, 1)
-                    w = w.reshape(w.shape[0], w.shape[1], ks[0] * ks[1], -1)      # tap-major rows (a linear layer's rows as they are)
-                    fl = conv_flops(B, h5.shape[2] * 8, h5.shape[3], h5.shape[4], w.shape[1], ks[0], ks[1], *geom, Es) if timers is not None else None
-                    is_logits = logits_buf is not None and i == last_bayes and not is_conv
-                    of32 = i == last_bayes
-                    dst = logits_buf[e0:e1] if is_logits else None
-                    ukw3 = {k: v for k, v in ukw2.items() if k != "x_per_slice"}
-                    y = _run(timers, "conv_gemm", fl, lambda h5=h5, w=w, b=b, ks=ks, geom=geom, act=act, dst=dst, ukw3=ukw3, of32=of32:
-                             ops.conv2d_c8x3_forward(h5, w, b, ks, *geom, act=act, out_f32=of32, out=dst, **ukw3))
-                    c8s3 = not of32
-                elif isinstance(mod, _BBBLayer):
-                    w, b = sampled[mod]
-                    if not ukw:
-                        w = w[e0:e1]
-                        b = None if b is None else b[e0:e1]
-                    if not is_conv:
-                        w = w.reshape(w.shape[0], mod.out_features, mod.in_features, 1, 1)
-                    fl = conv_flops(B, *h5.shape[-4:-1], w.shape[1], w.shape[3], w.shape[4], *geom, Es) if timers is not None else None
-                    dst = logits_buf[e0:e1] if (logits_buf is not None and i == last_bayes and not is_conv) else None
-                    o_s3 = s3_chain and i != last_bayes          # intermediate layers hand their output on already split
-                    # [activation ->] MaxPool2d(2, 2) after a conv layer: one launch with it when the launch is large enough
-                    # (ops.pool_fusion_ok; same bits as the separate pooling launch)
-                    pool_at = i + (2 if act is not None else 1)
-                    pool_mod = children[pool_at] if pool_at < len(children) and isinstance(children[pool_at], nn.MaxPool2d) else None
-                    # (a chain over MFMA-ready operands: the layers outside it -- the first one -- take the fp32 kernel, pooled form included)
-                    bx3 = False if c8_set else bf16x3
-                    fuse_pool = (pool_mod is not None and is_conv and not s3 and not o_s3 and (bf16x3 is None or bool(c8_set)) and
-                                 ops.pool_fusion_ok(tuple(h5.shape), tuple(w.shape), *geom, Es, pool_mod, fp32_kernel=bool(c8_set)))
-                    y = _run(timers, "conv_gemm", fl, lambda h5=h5, w=w, b=b, geom=geom, act=act, dst=dst, ukw2=ukw2, s3=s3, o_s3=o_s3, fuse_pool=fuse_pool, bx3=bx3:
-                             ops.conv2d_chwn_forward(h5, w, b, *geom, act=act, out=dst, bf16x3=bx3, x_s3=s3, out_s3=o_s3,
-                                                     pool=fuse_pool, **ukw2))
-                    s3 = o_s3
-                    if fuse_pool:
-                        i += 1                                   # the pooling module is done too
-                elif bf16:
-                    # an LRT layer on bf16 storage (LaunchConfig.bf16_lrt): both contractions in one launch of the dual-accumulator
-                    # bf16 GEMM, weights shared by every slab, the fp32 path's noise elements
-                    wm_b, wv_b = lrt_b16[mod]
-                    b_var = variances[mod][1]
-                    ckk = (mod.in_channels, *mod.kernel_size) if is_conv else (mod.in_features, 1, 1)
-                    tapm = is_conv and ops.bf16_tap_major(tuple(mod.W_mu.shape))
-                    of32 = i == last_bayes and tail_is_last
-                    dst = logits_buf[e0:e1] if (logits_buf is not None and i == last_bayes and not is_conv) else None
-                    shared_in = h5.shape[0] == 1 and Es > 1 and G == 1 and not of32
-                    fl = conv_flops(B, h5.shape[1], h5.shape[2], h5.shape[3], wm_b.shape[0], ckk[1], ckk[2],
-                                    *geom, 1 if shared_in else Es, 2) if timers is not None else None
-                    if shared_in:
-                        # same input AND same weights for every draw: the two contractions run once (moments only), the E draws
-                        # differ only in the noise -- bitwise the same result as E full launches
-                        _, am, av = _run(timers, "lrt_gemm", fl,
-                                         lambda h5=h5, wm_b=wm_b, wv_b=wv_b, b_var=b_var, mod=mod, geom=geom, ckk=ckk, tapm=tapm:
-                                         ops.lrt_conv2d_chwn_bf16_forward(h5, wm_b, wv_b, mod.bias_mu if mod.use_bias else None, b_var, ckk,
-                                                                          seed, call0 + e0, mod._stream_base + 2, *geom, sample=False,
-                                                                          moments_only=True, tap_major=tapm))
-                        y = _run(timers, "lrt_sample", None,
-                                 lambda am=am, av=av, mod=mod, act=act:
-                                 ops.lrt_sample_chwn_bf16(am, av, Es, seed, call0 + e0, mod._stream_base + 2, act=act))
-                    else:
-                        y = _run(timers, "lrt_gemm", fl,
-                                 lambda h5=h5, wm_b=wm_b, wv_b=wv_b, b_var=b_var, mod=mod, geom=geom, ckk=ckk, tapm=tapm, act=act, ukw2=ukw2,
-                                 of32=of32, dst=dst:
-                                 ops.lrt_conv2d_chwn_bf16_forward(h5, wm_b, wv_b, mod.bias_mu if mod.use_bias else None, b_var, ckk, seed,
-                                                                  call0 + e0, mod._stream_base + 2, *geom, sample=True, act=act,
-                                                                  out_f32=of32, out=dst, tap_major=tapm, n_slabs=Es, **ukw2)[0])
-                else:
-                    w_var, b_var = variances[mod]
-                    w_mu = mod.W_mu
-                    if not is_conv:
-                        shp = (mod.out_features, mod.in_features, 1, 1)
-                        w_mu, w_var = w_mu.reshape(shp), w_var.reshape(shp)
-                    shared_in = h5.shape[0] == 1 and Es > 1 and not ukw and G == 1 and share is None
-                    fl = conv_flops(B, h5.shape[1], h5.shape[2], h5.shape[3], w_mu.shape[0], w_mu.shape[2], w_mu.shape[3],
-                                    *geom, 1 if shared_in else Es, 2) if timers is not None else None
-                    if shared_in:
-                        # same input AND same (mu, sigma^2) weights for every draw: the two contractions run once, the E
-                        # draws differ only in the epilogue noise (bitwise the same result as E full launches)
-                        _, am, av = _run(timers, "lrt_gemm", fl,
-                                         lambda h5=h5, w_mu=w_mu, w_var=w_var, b_var=b_var, mod=mod, geom=geom:
-                                         ops.lrt_conv2d_chwn_forward(h5, w_mu, w_var, mod.bias_mu if mod.use_bias else None,
-                                                                     b_var, seed, call0 + e0, mod._stream_base + 2, *geom,
-                                                                     sample=False, want_moments=True, act=None))
-                        y = _run(timers, "lrt_sample", None,
-                                 lambda am=am, av=av, mod=mod, act=act, boff=boff: ops.lrt_sample_chwn(am, av, Es, seed, call0 + e0, mod._stream_base + 2, act=act, b_offset=boff))
-                    else:
-                        y = _run(timers, "lrt_gemm", fl,
-                                 lambda h5=h5, w_mu=w_mu, w_var=w_var, b_var=b_var, mod=mod, geom=geom, act=act, ukw2=ukw2, boff=boff:
-                                 ops.lrt_conv2d_chwn_forward(h5, w_mu, w_var, mod.bias_mu if mod.use_bias else None, b_var,
-                                                             seed, call0 + e0, mod._stream_base + 2, *geom, sample=True,
-                                                             act=act, b_offset=boff, **ukw2,
-                                                             **({"n_slabs": Es} if "x_div" in ukw2 else {}))[0])
-                h = y
-                if act is not None:
-                    i += 1
-            elif isinstance(mod, FlattenLayer):
-                if c8s3:
-                    if h.shape[3] * h.shape[4] == 1 and h.shape[2] * 8 == mod.num_features:
-                        i += 1                                   # [E, 3, F / 8, 1, 1, B, 8] already is the flattened feature order
-                        continue
-                    h, c8s3 = ops.c8s3_to_f32(h), False
-                if s3 and h.shape[2] * h.shape[3] * h.shape[4] != mod.num_features:
-                    h, s3 = ops.s3_to_f32(h), False              # the flatten quirk below works on the fp32 tensor
-                if h.dim() != (6 if s3 else 5):
-                    return None
-                chw = h.shape[-4] * h.shape[-3] * h.shape[-2]
-                if s3:
-                    h = h.reshape(h.shape[0], 3, mod.num_features, 1, 1, B)
-                elif chw == mod.num_features:
-                    h = h.reshape(h.shape[0], mod.num_features, 1, 1, B)
-                else:
-                    # the reference's view(-1, num_features) on a larger map (AlexNet on 224x224: [B,128,7,7] -> [B*49,128])
-                    # cuts each image's NCHW memory into rows of num_features: go through the NCHW order once, on this
-                    # small tensor, and continue batch-innermost with B' = B*chw/num_features "images"
-                    if chw % mod.num_features != 0 or bf16:
-                        return None
-                    rows = h.permute(0, 4, 1, 2, 3).reshape(h.shape[0], -1, mod.num_features)     # [E|1, B', F]
-                    boff *= chw // mod.num_features
-                    B = rows.shape[1]
-                    if B % 4 != 0:
-                        return None
-                    h = rows.permute(0, 2, 1).contiguous().reshape(h.shape[0], mod.num_features, 1, 1, B)
-                    if logits_buf is not None and logits_buf.shape[2] != B:
-                        logits_buf = torch.empty((E, n_out, B), dtype=torch.float32, device=x.device)
-            elif isinstance(mod, nn.MaxPool2d):
-                pool = ops.maxpool_c8s3 if c8s3 else ops.maxpool_chwn_s3 if s3 else (ops.maxpool_chwn_bf16 if bf16 else ops.maxpool_chwn)
-                h = _run(timers, "maxpool", None, lambda: pool(h, mod.kernel_size, mod.stride))
-            elif isinstance(mod, nn.ReLU):
-                if s3:
-                    h, s3 = ops.s3_to_f32(h), False
-                if c8s3:
-                    h, c8s3 = ops.c8s3_to_f32(h), False
-                h = torch.relu(h)
-            else:
-                if s3:
-                    h, s3 = ops.s3_to_f32(h), False
-                if c8s3:
-                    h, c8s3 = ops.c8s3_to_f32(h), False
-                h = F.softplus(h)
-            i += 1
-        if s3:
-            h, s3 = ops.s3_to_f32(h), False
-        if c8s3:
-            h, c8s3 = ops.c8s3_to_f32(h), False
-        if h.shape[0] == 1 and Es > 1:
-            h = h.expand(Es, *h.shape[1:])
-        h = h.reshape(Es, -1, B)
-        if logits_buf is not None and h.shape[1] == logits_buf.shape[1]:
-            dst = logits_buf[e0:e1]
-            if h.data_ptr() != dst.data_ptr():
-                dst.copy_(h)
-            return dst
-        return h
-
-    nsplit = max(1, min(int(streams), E))
-    if nsplit == 1 or timers is not None:
-        stats["launch"] = "layers"
-        out = run(0, E)
-        if out is None:
-            return None
-    else:
-        stats["launch"] = "layers"
         # Independent sub-ensembles on separate HIP streams: each GEMM launch is one wave of workgroups with a ramp
         # and a tail, and the other stream's kernels fill those bubbles (and the launch gaps).
         main = torch.cuda.current_stream(x.device)
         pool = _side_streams(x.device, nsplit)
-        bounds = [draw_range(E, r, nsplit) for r in range(nsplit)]
         parts = []
-        for st, (e0, e1) in zip(pool, bounds):
+        for st, plan, (e0, e1) in zip(pool, plans, bounds):
             st.wait_stream(main)
             with torch.cuda.stream(st):
-                parts.append(run(e0, e1))
+                parts.append(_chwn_walk(c, plan.steps, e0, e1))
         for st in pool:
             main.wait_stream(st)
-        if any(pt is None for pt in parts):
-            return None
-        out = logits_buf if (logits_buf is not None and all(pt.data_ptr() == logits_buf[b0:b1].data_ptr()
-                                                            for pt, (b0, b1) in zip(parts, bounds))) \
+        buf = c.logits_buf
+        out = buf if (buf is not None and all(pt.data_ptr() == buf[b0:b1].data_ptr() for pt, (b0, b1) in zip(parts, bounds))) \
             else torch.cat(parts, dim=0)
-    stats["path"] = "chwn-bf16-lrt" if bf16_lrt else "chwn"
+    stats["path"] = "chwn-bf16-lrt" if c.plan.bf16_lrt else "chwn"
     if rows_real is not None:
         out = out[:, :, :rows_real]                              # (a view: the consumers' .contiguous() compacts it)
-    return out, kl                                               # logits stay batch-innermost: [E, C, B]
+    return out, c.kl                                             # logits stay batch-innermost: [E, C, B]
 
 
 _stream_pool = {}
@@ -1029,48 +659,32 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
         logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias)
         stats["path"] = "chwn-autograd"
         return _autograd_tail(logits_cb, kl1, mean_over, elbo)
+    # one tail for the four ways the step is cut up: (the mc_tail_* launch, _mc_logits_chwn's partition argument, streams, the
+    # error where the batch-innermost path is the only one)
+    tail = None
     if share is not None:
         D, off = int(share[0]), int(share[1])
         n_steps = -(-(draws + off) // D)
-        out = _mc_logits_chwn(net, x, draws, seed, call0, timers, 1, precision, share=(D, off))
-        if out is None:
-            raise _lib.BBBHipError("a share of a group of steps needs the batch-innermost path")
-        if step_end is not None and timers is None:
-            lse, klf = ops.mc_tail_share(out[0], n_steps, D, off, step_end=(out[1], step_end[0], step_end[1], step_end[2]))
-            step_end[3] = True
-            return lse, klf
-        lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail_share(out[0], n_steps, D, off))
-        return lse, out[1]
-    if int(groups) > 1:
-        out = _mc_logits_chwn(net, x, draws, seed, call0, timers, 1, precision, groups=groups)
-        if out is None:
-            raise _lib.BBBHipError("several steps per launch need the batch-innermost path")
-        if step_end is not None and timers is None:
-            lse, klf = ops.mc_tail_groups(out[0], groups, draws, mean_over=mean_over,
-                                          step_end=(out[1], step_end[0], step_end[1], step_end[2]))
-            step_end[3] = True
-            return lse, klf
-        lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail_groups(out[0], groups, draws, mean_over=mean_over))
-        return lse, out[1]
-    if units is not None and units[0] > 1:
-        out = _mc_logits_chwn(net, x, draws, seed, call0, timers, 1, precision, units=units)
-        if out is None:
-            raise _lib.BBBHipError("work units need the batch-innermost path (checked by units_ok before planning)")
-        if step_end is not None and timers is None:
-            lse, klf = ops.mc_tail_units(out[0], units[0], units[1], mean_over=mean_over, step_end=(out[1], step_end[0], step_end[1], step_end[2]))
-            step_end[3] = True
-            return lse, klf
-        lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail_units(out[0], units[0], units[1], mean_over=mean_over))
-        return lse, out[1]
-    if fuse_act and _chwn_ok(net, x):
-        out = _mc_logits_chwn(net, x, draws, seed, call0, timers, streams, precision, b_offset=b_offset)
+        tail, kw, n_str = (lambda lg, **k: ops.mc_tail_share(lg, n_steps, D, off, **k)), dict(share=(D, off)), 1
+        need = "a share of a group of steps needs the batch-innermost path"
+    elif int(groups) > 1:
+        tail, kw, n_str = (lambda lg, **k: ops.mc_tail_groups(lg, groups, draws, mean_over=mean_over, **k)), dict(groups=groups), 1
+        need = "several steps per launch need the batch-innermost path"
+    elif units is not None and units[0] > 1:
+        tail, kw, n_str = (lambda lg, **k: ops.mc_tail_units(lg, units[0], units[1], mean_over=mean_over, **k)), dict(units=units), 1
+        need = "work units need the batch-innermost path (checked by units_ok before planning)"
+    elif fuse_act and _chwn_ok(net, x):
+        tail, kw, n_str, need = (lambda lg, **k: ops.mc_tail_cb(lg, mean_over=mean_over, **k)), dict(b_offset=b_offset), streams, None
+    if tail is not None:
+        out = _mc_logits_chwn(net, x, draws, seed, call0, timers, n_str, precision, **kw)
+        if out is None and need is not None:
+            raise _lib.BBBHipError(need)
         if out is not None:
             if step_end is not None and timers is None:
-                lse, klf = ops.mc_tail_cb(out[0], mean_over=mean_over, step_end=(out[1], step_end[0], step_end[1], step_end[2]))
+                lse, klf = tail(out[0], step_end=(out[1], step_end[0], step_end[1], step_end[2]))
                 step_end[3] = True
                 return lse, klf
-            lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail_cb(out[0], mean_over=mean_over))
-            return lse, out[1]
+            return _run(timers, "mc_tail", 0, lambda: tail(out[0])), out[1]
     if b_offset:
         raise _lib.BBBHipError("a batch offset needs the batch-innermost inference path (checked: this model / input does not fit it)")
     if precision == "bf16":
@@ -1725,10 +1339,6 @@ class GraphedLogits:
         self.counter.fill_(d - (1 << 32) if d >= (1 << 31) else d)     # the kernels add it modulo 2^32
         self.graph.replay()
         return self.logits, self.kl
-
-
-def _p2(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
 
 
 class _null_ctx:

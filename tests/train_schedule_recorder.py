@@ -34,40 +34,63 @@ def _flat(d):
     return "(" + " ".join(_flat(t) if t is not None else "-" for t in d) + ")" if isinstance(d, list) else d
 
 
+def _is_scalar(a):
+    return a is None or isinstance(a, (bool, int, float, str)) or (isinstance(a, tuple) and all(_is_scalar(t) for t in a))
+
+
+def _describe_all(a):
+    """_describe, and scalar arguments (None, bools, numbers, strings, tuples of those) as their repr; other objects -> None."""
+    if _is_scalar(a):
+        return repr(a)
+    if isinstance(a, (list, tuple)):
+        return [_describe_all(t) for t in a]
+    return _describe(a)
+
+
+def _train_sides(device):
+    from bbb_hip import fast_train
+    sides = fast_train._side_streams.get((device.index, fast_train.n_side_streams[0]))
+    return [] if sides is None else sides.streams
+
+
 class Recorder:
     """with Recorder(monkeypatch, device) as rec: ...; rec.events is the trace, one string per event:
-    '<stream> <op> <tensor arguments>' and 'wait <waiting stream> <- <awaited stream>'."""
+    '<stream> <op> <tensor arguments>' and 'wait <waiting stream> <- <awaited stream>'.
+    callers: the modules whose calls are recorded; sides(device) -> their side streams, in order; scalars: the scalar arguments
+    (None, bools, numbers, strings, tuples of those) are recorded too; skip: names of bbb_hip.ops that are left alone."""
 
-    def __init__(self, monkeypatch, device):
-        from bbb_hip import fast_train, ops
+    def __init__(self, monkeypatch, device, callers=(CALLER,), sides=_train_sides, scalars=False, skip=()):
+        from bbb_hip import ops
         self.mp, self.device = monkeypatch, torch.device(device)
-        self.fast_train, self.ops = fast_train, ops
+        self.callers, self.sides, self.ops = tuple(callers), sides, ops
+        self.describe = _describe_all if scalars else _describe
+        self.skip = frozenset(skip)
         self.events = []
         self.depth = 0
         self.main = None
 
     def called_ops(self):
-        """Every public callable of bbb_hip.ops that fast_train's source names (called there, or handed on as a callback)."""
+        """Every public callable of bbb_hip.ops that the callers' source names (called there, or handed on as a callback)."""
+        import importlib
         import inspect
-        names = sorted(set(re.findall(r"\bops\.([A-Za-z]\w*)", inspect.getsource(self.fast_train))))
+        src = "".join(inspect.getsource(importlib.import_module(c)) for c in self.callers)
+        names = sorted(set(re.findall(r"\bops\.([A-Za-z]\w*)", src)) - self.skip)
         return [n for n in names if callable(getattr(self.ops, n, None))]
 
     def tag(self, stream):
         if stream == self.main:
             return "main"
-        sides = self.fast_train._side_streams.get((self.device.index, self.fast_train.n_side_streams[0]))
-        if sides is not None:
-            for i, s in enumerate(sides.streams):
-                if stream == s:
-                    return f"side{i}"
+        for i, s in enumerate(self.sides(self.device)):
+            if stream == s:
+                return f"side{i}"
         return "other"
 
     def _wrap(self, name, fn):
         def wrapper(*args, **kwargs):
-            # only what fast_train itself calls: not what one ops function asks of another (depth), nor other modules' calls
-            mine = self.depth == 0 and sys._getframe(1).f_globals.get("__name__") == CALLER
+            # only what the callers themselves call: not what one ops function asks of another (depth), nor other modules' calls
+            mine = self.depth == 0 and sys._getframe(1).f_globals.get("__name__") in self.callers
             if mine:
-                descr = [_describe(a) for a in args] + [(k, _describe(v)) for k, v in sorted(kwargs.items())]
+                descr = [self.describe(a) for a in args] + [(k, self.describe(v)) for k, v in sorted(kwargs.items())]
                 parts = [_flat(d) for d in descr if not isinstance(d, tuple) and d is not None]
                 parts += [f"{k}={_flat(d)}" for k, d in (d for d in descr if isinstance(d, tuple)) if d is not None]
                 self.events.append(" ".join([self.tag(torch.cuda.current_stream(self.device)), name] + parts))
@@ -87,7 +110,7 @@ class Recorder:
         rec = self
 
         def wait_stream(self, other):
-            if sys._getframe(1).f_globals.get("__name__") == CALLER:
+            if sys._getframe(1).f_globals.get("__name__") in rec.callers:
                 rec.events.append(f"wait {rec.tag(self)} <- {rec.tag(other)}")
             return orig_wait(self, other)
         self.mp.setattr(torch.cuda.Stream, "wait_stream", wait_stream)
