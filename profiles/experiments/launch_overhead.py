@@ -40,7 +40,7 @@ with torch.no_grad():
     w = torch.rand(1, 8, 8, 3, 3, device=dev)
     b = torch.rand(1, 8, device=dev)
     y = ops.conv2d_chwn_forward(x, w, b, 1, 1, 1)
-    d, ho, wo = ops._desc_chwn(x, w, 1, 1, 1, 1, False, False, None)
+    d, ho, wo = ops.conv_desc(8, 8, (4, 4), 8, (3, 3), 1, 1, 1)
     st = ops.cur_stream(dev)
     args = (ctypes.byref(d), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), st)
     out["direct_ctypes_conv_call_us"] = per_call(lambda: L.bbb_conv2d_chwn_fwd(*args))

@@ -19,7 +19,8 @@ import weakref
 import torch
 
 from . import _lib, rng
-from ._lib import Segment, ConvDesc, check, ptr, require_device, cur_stream, on_device
+from ._lib import Segment, check, ptr, require_device, cur_stream, on_device
+from .conv_desc import ACT_CODE, _pair, bf16_flags, c8x3_flags, conv_desc, out_map, pool_code, pooled_map, slab_rule  # noqa: F401  (ops.ACT_CODE)
 
 _scratch = {}
 _retired = []     # (key, buffer) of outgrown scratch buffers: a captured hipGraph may have their address baked in, so a per-stream
@@ -213,41 +214,18 @@ def eps_dump(n, seed, call, stream_id, device, start=0):
     return out
 
 
-def _pair(v):
-    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+def _same_channels(cin, w_cin):
+    if cin != w_cin:
+        raise _lib.BBBHipError(f"channel mismatch: input has {cin}, weight expects {w_cin}")
 
 
-ACT_CODE = {None: 0, "none": 0, "relu": 1, "softplus": 2}
-
-
-class _Shape:
-    """A stand-in for a tensor where only `.shape` is read (_desc): building a meta tensor costs ~3 us of host time per launch."""
-    __slots__ = ("shape",)
-
-    def __init__(self, shape):
-        self.shape = tuple(shape)
-
-
-def _desc(x, w, stride, padding, dilation, draws, x_shared, w_shared, act):
-    """x: [E|1... folded][B, Cin, H, W] given as 5-d [Ex, B, Cin, H, W]; w: [Ew, Cout, Cin, kh, kw]."""
-    d = ConvDesc()
-    Ex, B, Cin, H, W = x.shape
-    Ew, Cout, Cin2, kh, kw = w.shape
-    if Cin != Cin2:
-        raise _lib.BBBHipError(f"channel mismatch: input has {Cin}, weight expects {Cin2}")
-    sh, sw = _pair(stride)
-    ph, pw = _pair(padding)
-    dh, dw = _pair(dilation)
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, Cout, kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
-    d.draws = draws
-    d.x_draw_stride = 0 if x_shared else B * Cin * H * W
-    d.w_draw_stride = 0 if w_shared else Cout * Cin * kh * kw
-    d.b_draw_stride = 0 if w_shared else Cout
-    d.act = ACT_CODE[act]
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    return d, ho, wo
+def _out_tensor(out, shape, dtype, device):
+    """The launch's output: a fresh tensor, or the caller's `out=` viewed as `shape`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.numel() != math.prod(shape) or not out.is_contiguous() or out.dtype != dtype:
+        raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
+    return out.view(shape)
 
 
 def conv2d_forward(x, w, bias, stride=1, padding=0, dilation=1, act=None):
@@ -257,11 +235,12 @@ def conv2d_forward(x, w, bias, stride=1, padding=0, dilation=1, act=None):
     require_device(x, w, bias)
     x, w = x.contiguous(), w.contiguous()
     bias = None if bias is None else bias.contiguous()
-    E = max(x.shape[0], w.shape[0])
-    if x.shape[0] not in (1, E) or w.shape[0] not in (1, E):
-        raise _lib.BBBHipError("leading (draw) dims of x and w must be 1 or equal")
-    d, ho, wo = _desc(x, w, stride, padding, dilation, E, x.shape[0] == 1 and E > 1, w.shape[0] == 1 and E > 1, act)
-    y = torch.empty((E, x.shape[1], w.shape[1], ho, wo), dtype=torch.float32, device=x.device)
+    Ex, B, Cin, H, W = x.shape
+    Ew, Cout, w_cin, kh, kw = w.shape
+    _same_channels(Cin, w_cin)
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act)
+    E, _, _ = slab_rule(d, Ex, Ew)
+    y = torch.empty((E, B, Cout, ho, wo), dtype=torch.float32, device=x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_conv2d_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(),
                                         cur_stream(x.device)), "bbb_conv2d_fwd")
@@ -277,11 +256,12 @@ def lrt_conv2d_forward(x, w_mu, w_var, b_mu, b_var, seed, call0, stream_id, stri
     w_mu, w_var = w_mu.contiguous(), w_var.contiguous()
     b_mu = None if b_mu is None else b_mu.contiguous()
     b_var = None if b_var is None else b_var.contiguous()
-    E = x.shape[0]
-    d, ho, wo = _desc(x, w_mu.unsqueeze(0), stride, padding, dilation, E, False, True, act)
-    d.w_draw_stride = 0
-    d.b_draw_stride = 0
-    shape = (E, x.shape[1], w_mu.shape[0], ho, wo)
+    E, B, Cin, H, W = x.shape
+    Cout, w_cin, kh, kw = w_mu.shape
+    _same_channels(Cin, w_cin)
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act)
+    slab_rule(d, E, 1, weights_shared=True)
+    shape = (E, B, Cout, ho, wo)
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     am = torch.empty(shape, dtype=torch.float32, device=x.device) if want_moments else None
     av = torch.empty(shape, dtype=torch.float32, device=x.device) if want_moments else None
@@ -473,25 +453,6 @@ def _split_scratch(d, lrt, device):
     return ks_v, buf
 
 
-def _apply_units(d, units, x_per_slice):
-    """units = (S, off) or None: the launch's slabs are work units u = off + e of the draw-major (draw, batch slice) grid
-    (see bbb_conv_desc_t).  x_per_slice: the input is an [S][...] per-slice tensor shared by all draws (first layer)."""
-    if units is None:
-        return
-    S, off = int(units[0]), int(units[1])
-    if S > 1:
-        d.unit_div, d.unit_off = S, off % S
-        d.x_unit_mod = S if x_per_slice else 0
-
-
-def _desc_chwn(x, w, stride, padding, dilation, draws, x_shared, w_shared, act):
-    """x: [Ex, Cin, H, W, B]; w: [Ew, Cout, Cin, kh, kw]."""
-    Ex, Cin, H, W, B = x.shape
-    d, ho, wo = _desc(_Shape((Ex, B, Cin, H, W)), w, stride, padding, dilation, draws, x_shared, w_shared, act)
-    d.x_draw_stride = 0 if x_shared else Cin * H * W * B
-    return d, ho, wo
-
-
 class overlapped_launches(use_config):
     """Context: the launches enqueued inside run concurrently with other streams' kernels (a lane of a GraphedPipeline)."""
 
@@ -537,9 +498,9 @@ def _pool_fusion_rule(x_shape, w_shape, stride, padding, dilation, draws, pool_m
     if pool_module is not None and not is_pool_2x2(pool_module):
         return False
     B = x_shape[-1]
-    xm = torch.empty((1,) + tuple(x_shape[-4:]), device="meta")
-    wm = torch.empty((1,) + tuple(w_shape[-4:]), device="meta")
-    d, ho, wo = _desc_chwn(xm, wm, stride, padding, dilation, int(draws), False, False, None)
+    Cin, H, W = x_shape[-4:-1]
+    _same_channels(Cin, w_shape[-3])
+    d, ho, wo = conv_desc(B, Cin, (H, W), w_shape[-4], tuple(w_shape[-2:]), stride, padding, dilation, int(draws))
     if ho % 2 or wo % 2 or B % 4:
         return False
     ks = ctypes.c_int32(1)
@@ -580,59 +541,33 @@ def conv2d_chwn_forward(x, w, bias, stride=1, padding=0, dilation=1, act=None, o
     require_device(x, dtype=torch.bfloat16 if x_s3 else torch.float32)
     x, w = x.contiguous(), w.contiguous()
     bias = None if bias is None else bias.contiguous()
-    w_mem = w
     if w_tap_major:
         if x_s3 or out_s3 or bf16x3:
             raise _lib.BBBHipError("w_tap_major: fp32 kernel only")
         bf16x3 = False
-        w = _Shape((w.shape[0], w.shape[1], w.shape[4], w.shape[2], w.shape[3]))
-    if x_s3:
-        if x.dim() != 6 or x.shape[1] != 3 or x.shape[5] % 8:
-            raise _lib.BBBHipError("an S3 input is a bf16 tensor [E|1, 3, C, H, W, B] with B % 8 == 0")
-        x5 = _Shape((x.shape[0],) + tuple(x.shape[2:]))
+        Ew, Cout, kh, kw, w_cin = w.shape
     else:
-        x5 = x
-    if units is not None and units[0] > 1:
-        E = int(n_units)
-        if x5.shape[0] != (units[0] if x_per_slice else E):
-            raise _lib.BBBHipError("work units: x must hold one slab per unit, or one per batch slice with x_per_slice")
-        d, ho, wo = _desc_chwn(x5, w, stride, padding, dilation, E, False, False, act)
-        _apply_units(d, units, x_per_slice)
-    elif int(x_div) > 1:
-        E = w.shape[0]
-        if not 0 <= int(x_off) < int(x_div) or x5.shape[0] != -(-(E + int(x_off)) // int(x_div)):
-            raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E weight sets")
-        d, ho, wo = _desc_chwn(x5, w, stride, padding, dilation, E, False, False, act)
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
-    else:
-        E = max(x5.shape[0], w.shape[0])
-        if x5.shape[0] not in (1, E) or w.shape[0] not in (1, E):
-            raise _lib.BBBHipError("leading (draw) dims of x and w must be 1 or equal")
-        d, ho, wo = _desc_chwn(x5, w, stride, padding, dilation, E, x5.shape[0] == 1 and E > 1, w.shape[0] == 1 and E > 1, act)
-    if x_s3:
-        d.x_draw_stride *= 3                                   # bf16 elements per S3 slab
+        Ew, Cout, w_cin, kh, kw = w.shape
+    if x_s3 and (x.dim() != 6 or x.shape[1] != 3 or x.shape[5] % 8):
+        raise _lib.BBBHipError("an S3 input is a bf16 tensor [E|1, 3, C, H, W, B] with B % 8 == 0")
+    Ex, Cin, H, W, B = (x.shape[0], *x.shape[2:]) if x_s3 else x.shape
+    _same_channels(Cin, w_cin)
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act, x_planes=3 if x_s3 else 1)
+    E, _, _ = slab_rule(d, Ex, Ew, units=units, n_units=n_units, x_per_slice=x_per_slice, x_div=x_div, x_off=x_off)
     if w_tap_major:
         d.w_tap_major = 1
-    B = x5.shape[4]
     if pool:
         if x_s3 or out_s3 or bf16x3 or ho % 2 or wo % 2:
             raise _lib.BBBHipError("pool=True: fp32 kernel only, even output height and width")
         d.pool = 1
         ho, wo = ho // 2, wo // 2
-    shape = (E, 3, w.shape[1], ho, wo, B) if out_s3 else (E, w.shape[1], ho, wo, B)
-    odt = torch.bfloat16 if out_s3 else torch.float32
     if out_s3 and B % 8:
         raise _lib.BBBHipError("an S3 output needs B % 8 == 0")
-    if out is None:
-        y = torch.empty(shape, dtype=odt, device=x.device)
-    else:
-        if out.numel() != E * (3 if out_s3 else 1) * w.shape[1] * ho * wo * B or not out.is_contiguous() or out.dtype != odt:
-            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
-        y = out.view(shape)
+    y = _out_tensor(out, (E, 3, Cout, ho, wo, B) if out_s3 else (E, Cout, ho, wo, B), torch.bfloat16 if out_s3 else torch.float32, x.device)
     with on_device(x.device):
         if x_s3 or out_s3 or (not pool and (bf16x3 if bf16x3 is not None else current_config().gemm_mode == "bf16x3")
-                              and E * ho * wo * -(-w.shape[1] // 64) * -(-B // 128) >= current_config().bf16x3_min_workgroups):
-            check(_lib.lib().bbb_conv2d_chwn_bf16x3_fwd(ctypes.byref(d), x.data_ptr(), w_mem.data_ptr(), ptr(bias), y.data_ptr(),
+                              and E * ho * wo * -(-Cout // 64) * -(-B // 128) >= current_config().bf16x3_min_workgroups):
+            check(_lib.lib().bbb_conv2d_chwn_bf16x3_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(),
                                                         (1 if x_s3 else 0) | (2 if out_s3 else 0), cur_stream(x.device)),
                   "bbb_conv2d_chwn_bf16x3_fwd")
             return y
@@ -640,11 +575,11 @@ def conv2d_chwn_forward(x, w, bias, stride=1, padding=0, dilation=1, act=None, o
         if ks > 1 and pool:
             raise _lib.BBBHipError("pool=True: this layer's contraction is split (conv + maxpool_chwn instead)")
         if ks > 1:
-            check(_lib.lib().bbb_conv2d_chwn_splitk_fwd(ctypes.byref(d), x.data_ptr(), w_mem.data_ptr(), ptr(bias), y.data_ptr(), ks,
+            check(_lib.lib().bbb_conv2d_chwn_splitk_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(), ks,
                                                         ptr(scr), 0 if scr is None else scr.numel(), cur_stream(x.device)),
                   "bbb_conv2d_chwn_splitk_fwd")
         else:
-            check(_lib.lib().bbb_conv2d_chwn_fwd(ctypes.byref(d), x.data_ptr(), w_mem.data_ptr(), ptr(bias), y.data_ptr(),
+            check(_lib.lib().bbb_conv2d_chwn_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(),
                                                  cur_stream(x.device)), "bbb_conv2d_chwn_fwd")
     return y
 
@@ -822,26 +757,8 @@ def conv2d_c8x3_forward(x, w_tm, bias, kernel_size, stride=1, padding=0, dilatio
     Ew, Cout, T, Cin = w_tm.shape
     if T != kh * kw or Cin != CG * 8:
         raise _lib.BBBHipError(f"weights [{Cout}, {T}, {Cin}] do not match a {kh} x {kw} layer on {CG * 8} channels")
-    x5 = _Shape((Ex, Cin, H, W, B))
-    w5 = _Shape((Ew, Cout, Cin, kh, kw))
-    if units is not None and units[0] > 1:
-        E = int(n_units)
-        if Ex != (units[0] if x_per_slice else E):
-            raise _lib.BBBHipError("work units: x must hold one slab per unit, or one per batch slice with x_per_slice")
-        d, ho, wo = _desc_chwn(x5, w5, stride, padding, dilation, E, False, False, act)
-        _apply_units(d, units, x_per_slice)
-    elif int(x_div) > 1:
-        E = Ew
-        if not 0 <= int(x_off) < int(x_div) or Ex != -(-(E + int(x_off)) // int(x_div)):
-            raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E weight sets")
-        d, ho, wo = _desc_chwn(x5, w5, stride, padding, dilation, E, False, False, act)
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
-    else:
-        E = max(Ex, Ew)
-        if Ex not in (1, E) or Ew not in (1, E):
-            raise _lib.BBBHipError("leading (draw) dims of x and w must be 1 or equal")
-        d, ho, wo = _desc_chwn(x5, w5, stride, padding, dilation, E, Ex == 1 and E > 1, Ew == 1 and E > 1, act)
-    d.x_draw_stride *= 3                                       # bf16 elements per slab of three planes
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act, x_planes=3)
+    E, _, _ = slab_rule(d, Ex, Ew, units=units, n_units=n_units, x_per_slice=x_per_slice, x_div=x_div, x_off=x_off)
     if pool:
         if out_f32 or ho % 2 or wo % 2 or _pair(padding) != (0, 0):
             raise _lib.BBBHipError("pool=True: c8 S3 output, no padding, even output height and width")
@@ -852,21 +769,10 @@ def conv2d_c8x3_forward(x, w_tm, bias, kernel_size, stride=1, padding=0, dilatio
         if Cout % 8:
             raise _lib.BBBHipError("a c8 S3 output needs a multiple of 8 output channels")
         shape, odt = (E, 3, Cout // 8, ho, wo, B, 8), torch.bfloat16
-    if out is None:
-        y = torch.empty(shape, dtype=odt, device=x.device)
-    else:
-        n = 1
-        for v in shape:
-            n *= v
-        if out.numel() != n or not out.is_contiguous() or out.dtype != odt:
-            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
-        y = out.view(shape)
+    y = _out_tensor(out, shape, odt, x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_conv2d_c8x3_fwd(ctypes.byref(d), x.data_ptr(), w_tm.data_ptr(), ptr(bias), y.data_ptr(),
-                                             (1 if out_f32 else 0) | {None: 0, 128: 2, 256: 4, 32: 2, 64: 4}[tile] | (8 if pool else 0) |
-                                             ({None: 0, 2: 2, 3: 3, 4: 4}[nt] << 4) | (min(15, zero_border[0]) << 8) |
-                                             (min(15, zero_border[1]) << 12) | (min(15, zero_border[2]) << 16) | (min(15, zero_border[3]) << 20),
-                                             cur_stream(x.device)),
+                                             c8x3_flags(out_f32, tile, zero_border, nt, bool(pool)), cur_stream(x.device)),
               "bbb_conv2d_c8x3_fwd")
     return y
 
@@ -908,42 +814,18 @@ def lrt_conv2d_c8x3_forward(x, w_mu_tm, w_var_tm, b_mu, b_var, kernel_size, seed
     Cout, T, Cin = w_mu_tm.shape
     if T != kh * kw or Cin != CG * 8:
         raise _lib.BBBHipError(f"weights [{Cout}, {T}, {Cin}] do not match a {kh} x {kw} layer on {CG * 8} channels")
-    x5 = _Shape((Ex, Cin, H, W, B))
-    w5 = _Shape((1, Cout, Cin, kh, kw))
-    E = (int(n_slabs) if n_slabs is not None else Ex * int(x_div)) if (units is None or units[0] <= 1) else int(n_units)
-    d, ho, wo = _desc_chwn(x5, w5, stride, padding, dilation, E, Ex == 1 and E > 1 and int(x_div) <= 1 and (units is None or units[0] <= 1),
-                           True, act)
-    if units is not None and units[0] > 1:
-        if Ex != (units[0] if x_per_slice else E):
-            raise _lib.BBBHipError("work units: x must hold one slab per unit, or one per batch slice with x_per_slice")
-        _apply_units(d, units, x_per_slice)
-    elif int(x_div) > 1:
-        if not 0 <= int(x_off) < int(x_div) or Ex != -(-(E + int(x_off)) // int(x_div)):
-            raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E output slabs")
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
-    elif Ex not in (1, E):
-        raise _lib.BBBHipError("x must hold one slab, or one per output slab")
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act, x_planes=6)
+    E, _, _ = slab_rule(d, Ex, 1, units=units, n_units=n_units, x_per_slice=x_per_slice, x_div=x_div, x_off=x_off, n_slabs=n_slabs,
+                        weights_shared=True)
     d.b_offset = int(b_offset)
-    d.w_draw_stride = 0
-    d.b_draw_stride = 0
-    d.x_draw_stride *= 6                                       # bf16 elements per slab of six planes
     if out_f32:
         shape, odt = (E, Cout, ho, wo, B), torch.float32
     else:
         if Cout % 8:
             raise _lib.BBBHipError("a c8 S3 output needs a multiple of 8 output channels")
         shape, odt = (E, 6, Cout // 8, ho, wo, B, 8), torch.bfloat16
-    if out is None:
-        y = torch.empty(shape, dtype=odt, device=x.device)
-    else:
-        n = 1
-        for v in shape:
-            n *= v
-        if out.numel() != n or not out.is_contiguous() or out.dtype != odt:
-            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
-        y = out.view(shape)
-    flags = (1 if out_f32 else 0) | {None: 0, 128: 2, 256: 4}[tile] | (min(15, zero_border[0]) << 8) | (min(15, zero_border[1]) << 12) | \
-        (min(15, zero_border[2]) << 16) | (min(15, zero_border[3]) << 20)
+    y = _out_tensor(out, shape, odt, x.device)
+    flags = c8x3_flags(out_f32, tile, zero_border)
     with on_device(x.device):
         check(_lib.lib().bbb_lrt_conv2d_c8x3_fwd(ctypes.byref(d), x.data_ptr(), w_mu_tm.data_ptr(), w_var_tm.data_ptr(), ptr(b_mu), ptr(b_var),
                                                  y.data_ptr(), seed, call0 & 0xFFFFFFFF, stream_id, 1 if sample else 0,
@@ -962,24 +844,21 @@ def lrt_conv2d_chwn_forward(x, w_mu, w_var, b_mu, b_var, seed, call0, stream_id,
     w_mu, w_var = w_mu.contiguous(), w_var.contiguous()
     b_mu = None if b_mu is None else b_mu.contiguous()
     b_var = None if b_var is None else b_var.contiguous()
-    E = (int(n_slabs) if n_slabs is not None else x.shape[0] * int(x_div)) if (units is None or units[0] <= 1) else int(n_units)
-    d, ho, wo = _desc_chwn(x, w_mu.unsqueeze(0), stride, padding, dilation, E, False, True, act)
-    if units is not None and units[0] > 1:
-        _apply_units(d, units, x_per_slice)
-    elif int(x_div) > 1:
-        if not 0 <= int(x_off) < int(x_div) or x.shape[0] != -(-(E + int(x_off)) // int(x_div)):
-            raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E output slabs")
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)   # several steps per launch: slab e = step (e + x_off) // x_div on that step's batch
+    Ex, Cin, H, W, B = x.shape
+    Cout, w_cin, kh, kw = w_mu.shape
+    _same_channels(Cin, w_cin)
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act)
+    E, _, _ = slab_rule(d, Ex, 1, units=units, n_units=n_units, x_per_slice=x_per_slice, x_div=x_div, x_off=x_off, n_slabs=n_slabs,
+                        weights_shared=True)
     d.b_offset = int(b_offset)
-    d.w_draw_stride = 0
-    d.b_draw_stride = 0
     if pool:
         # [activation ->] MaxPool2d(2, 2) inside the launch (pconv_body.cuh, POOL + LRT): the sampling epilogue per window pixel with
         # the CONV output's noise elements, running maximum in registers -- bit for bit maxpool_chwn of the unpooled launch
         if want_moments or ho % 2 or wo % 2:
             raise _lib.BBBHipError("pool=True: even output height / width, and no moment outputs (the unpooled pixels are not kept)")
         d.pool = 1
-    shape = (E, w_mu.shape[0], ho // 2, wo // 2, x.shape[4]) if pool else (E, w_mu.shape[0], ho, wo, x.shape[4])
+        ho, wo = ho // 2, wo // 2
+    shape = (E, Cout, ho, wo, B)
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     am = torch.empty(shape, dtype=torch.float32, device=x.device) if want_moments else None
     av = torch.empty(shape, dtype=torch.float32, device=x.device) if want_moments else None
@@ -1010,7 +889,8 @@ def fp32_fwd_plan(x_shape, w_shape, stride=1, padding=0, dilation=1, draws=None,
     scratch: the launch gets scratch for its cross-workgroup form, as the two forwards give it.  A geometry or a k_split the launch
     refuses raises the launch's error."""
     E = int(draws) if draws is not None else x_shape[0]
-    d, _, _ = _lrt_bf16_desc((E,) + tuple(x_shape[-4:]), w_shape[-4], tuple(w_shape[-3:]), stride, padding, dilation, E, False, None)
+    Cin, H, W, B = x_shape[-4:]
+    d, _, _ = conv_desc(B, Cin, (H, W), w_shape[-4], tuple(w_shape[-2:]), stride, padding, dilation, E, w_stride=0, b_stride=0)
     d.pool = 1 if pool else 0
     if k_split is None:
         ks = ctypes.c_int32(1)
@@ -1033,7 +913,7 @@ def lrt_sample_chwn(act_mu, act_var, draws, seed, call0, stream_id, act=None, b_
     y = torch.empty((draws, C, Ho, Wo, B), dtype=torch.float32, device=act_mu.device)
     with on_device(act_mu.device):
         check(_lib.lib().bbb_lrt_sample_chwn(act_mu.data_ptr(), act_var.data_ptr(), y.data_ptr(), draws, C, Ho * Wo, B, int(b_offset),
-                                             {None: 0, "relu": 1, "softplus": 2}[act], seed, call0 & 0xFFFFFFFF, stream_id,
+                                             ACT_CODE[act], seed, call0 & 0xFFFFFFFF, stream_id,
                                              rng.call_dev_ptr(act_mu.device), cur_stream(act_mu.device)), "bbb_lrt_sample_chwn")
     return y
 
@@ -1188,10 +1068,8 @@ def bf16_pool_fusion_ok(cin_khkw, tap_major, out_f32, pool_module, x_shape=None,
         return False
     if x_shape is None:
         return True
-    (sh, sw), (ph, pw), (dh, dw) = _pair(geom[0]), _pair(geom[1]), _pair(geom[2])
     H, W, B = x_shape[-3], x_shape[-2], x_shape[-1]
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    ho, wo = out_map(H, W, (kh, kw), *geom)
     pk, pst = ks[0][0], ks[1][0]
     if ho < pk or wo < pk:
         return False
@@ -1220,49 +1098,24 @@ def conv2d_chwn_bf16_forward(x, w, bias, cin_khkw, stride=1, padding=0, dilation
         x = x.view(x.shape[0], x.shape[1] * 8, x.shape[2], x.shape[3], x.shape[4])      # same bytes; only the element order differs
     bias = None if bias is None else bias.contiguous()
     cin, kh, kw = cin_khkw
-    sharded = units is not None and units[0] > 1
-    grouped = not sharded and int(x_div) > 1
-    E = int(n_units) if sharded else (w.shape[0] if grouped else max(x.shape[0], w.shape[0]))
-    if grouped and (not 0 <= int(x_off) < int(x_div) or x.shape[0] != -(-(E + int(x_off)) // int(x_div))):
-        raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E weight sets")
-    if not sharded and not grouped and (x.shape[0] not in (1, E) or w.shape[0] not in (1, E)):
-        raise _lib.BBBHipError("leading (draw) dims of x and w must be 1 or equal")
     Ex, Cin, H, W, B = x.shape
-    if Cin != cin or w.shape[2] != bf16_row_pitch(cin * kh * kw):
+    Ew, Cout, Kp = w.shape
+    if Cin != cin or Kp != bf16_row_pitch(cin * kh * kw):
         raise _lib.BBBHipError("weight pitch / channel count do not match the geometry")
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, w.shape[1], kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
-    d.draws = E
-    d.x_draw_stride = 0 if (Ex == 1 and E > 1 and not sharded and not grouped) else Cin * H * W * B
-    if grouped:
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
-    d.w_draw_stride = 0 if (w.shape[0] == 1 and E > 1 and not sharded) else w.shape[1] * w.shape[2]
-    d.b_draw_stride = 0 if (bias is None or (bias.shape[0] == 1 and E > 1 and not sharded)) else w.shape[1]
-    d.act = {None: 0, "relu": 1, "softplus": 2}[act]
-    if sharded:
-        _apply_units(d, units, x_per_slice)
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    d, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation, act=act, w_stride=Cout * Kp)
+    E, _, _ = slab_rule(d, Ex, Ew, units=units, n_units=n_units, x_per_slice=x_per_slice, x_div=x_div, x_off=x_off)
+    if bias is None or (bias.shape[0] == 1 and E > 1 and not d.unit_div):
+        d.b_draw_stride = 0
     if pool is not None:
-        pk, pst = int(pool[0]), int(pool[1])
-        d.pool = 1 if (pk, pst) == (2, 2) else ((pk << 8) | pst)
-        ho, wo = (ho - pk) // pst + 1, (wo - pk) // pst + 1
-    if out_c8 and (out_f32 or w.shape[1] % 8):
+        d.pool = pool_code(pool)
+        ho, wo = pooled_map(ho, wo, pool)
+    if out_c8 and (out_f32 or Cout % 8):
         raise _lib.BBBHipError("out_c8: bf16 output with a multiple of 8 channels")
-    shape = (E, w.shape[1] // 8, ho, wo, B, 8) if out_c8 else (E, w.shape[1], ho, wo, B)
-    dt = torch.float32 if out_f32 else torch.bfloat16
-    if out is None:
-        y = torch.empty(shape, dtype=dt, device=x.device)
-    else:
-        if out.numel() != E * w.shape[1] * ho * wo * B or not out.is_contiguous() or out.dtype != dt:
-            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
-        y = out.view(shape)
+    y = _out_tensor(out, (E, Cout // 8, ho, wo, B, 8) if out_c8 else (E, Cout, ho, wo, B), torch.float32 if out_f32 else torch.bfloat16,
+                    x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_conv2d_chwn_bf16_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(),
-                                                  (1 if out_f32 else 0) | (2 if tap_major else 0) | (4 if x_c8 else 0) |
-                                                  (8 if out_c8 else 0), cur_stream(x.device)),
+                                                  bf16_flags(out_f32, tap_major, x_c8, out_c8), cur_stream(x.device)),
               "bbb_conv2d_chwn_bf16_fwd")
     return y
 
@@ -1294,26 +1147,17 @@ def lrt_weights_bf16(weights):
     return outs
 
 
-def _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, x_shared, act):
-    Ex, Cin, H, W, B = x_shape
-    cin, kh, kw = cin_khkw
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, cout, kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
-    d.draws = E
-    d.x_draw_stride = 0 if x_shared else Cin * H * W * B
-    d.act = {None: 0, "relu": 1, "softplus": 2}[act]
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    return d, ho, wo
+def _bf16_plan_desc(x_shape, cout, cin_khkw, stride, padding, dilation, draws, w_stride):
+    """The descriptor the bf16 plan queries ask about: `draws` (default x_shape[0]) slabs of x_shape = [E, Cin, H, W, B]."""
+    _, Cin, H, W, B = x_shape
+    return conv_desc(B, Cin, (H, W), cout, cin_khkw[1:], stride, padding, dilation, int(draws) if draws is not None else x_shape[0],
+                     w_stride=w_stride, b_stride=0)[0]
 
 
 def lrt_bf16_plan(x_shape, cout, cin_khkw, stride=1, padding=0, dilation=1, draws=None):
     """(tile shape 22 | 14 | 12, k-groups, wave-specialised) the library picks for lrt_conv2d_chwn_bf16_forward on this geometry
     (bbb_lrt_conv2d_chwn_bf16_plan; host only: needs no device)."""
-    E = int(draws) if draws is not None else x_shape[0]
-    d, _, _ = _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, False, None)
+    d = _bf16_plan_desc(x_shape, cout, cin_khkw, stride, padding, dilation, draws, 0)
     sh, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
     check(_lib.lib().bbb_lrt_conv2d_chwn_bf16_plan(ctypes.byref(d), 0, ctypes.byref(sh), ctypes.byref(kg), ctypes.byref(ws)),
           "bbb_lrt_conv2d_chwn_bf16_plan")
@@ -1329,12 +1173,10 @@ def bf16_fwd_plan(x_shape, cout, cin_khkw, stride=1, padding=0, dilation=1, draw
     form one of BF16_FORMS; for "general" the tile shape 22 | 14 | 12, 1 | 2 | 4 k-groups and whether the launch is
     wave-specialised, (0, 0, False) otherwise (bbb_conv2d_chwn_bf16_plan, the launch entry's own plan; host only: needs no device).
     A geometry the launch refuses raises the launch's error."""
-    E = int(draws) if draws is not None else x_shape[0]
-    d, _, _ = _lrt_bf16_desc(x_shape, cout, cin_khkw, stride, padding, dilation, E, False, None)
-    d.w_draw_stride = cout * bf16_row_pitch(cin_khkw[0] * cin_khkw[1] * cin_khkw[2])
-    if pool is not None:
-        d.pool = 1 if tuple(pool) == (2, 2) else ((int(pool[0]) << 8) | int(pool[1]))
-    flags = (1 if out_f32 else 0) | (2 if tap_major else 0) | (4 if x_c8 else 0) | (8 if out_c8 else 0)
+    d = _bf16_plan_desc(x_shape, cout, cin_khkw, stride, padding, dilation, draws,
+                        cout * bf16_row_pitch(cin_khkw[0] * cin_khkw[1] * cin_khkw[2]))
+    d.pool = pool_code(pool)
+    flags = bf16_flags(out_f32, tap_major, x_c8, out_c8)
     fm, sh, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
     check(_lib.lib().bbb_conv2d_chwn_bf16_plan(ctypes.byref(d), flags, ctypes.byref(fm), ctypes.byref(sh), ctypes.byref(kg),
                                                ctypes.byref(ws)), "bbb_conv2d_chwn_bf16_plan")
@@ -1356,31 +1198,16 @@ def lrt_conv2d_chwn_bf16_forward(x, w_mu, w_var, b_mu, b_var, cin_khkw, seed, ca
     b_mu = None if b_mu is None else b_mu.contiguous()
     b_var = None if b_var is None else b_var.contiguous()
     cin, kh, kw = cin_khkw
-    grouped = int(x_div) > 1
-    E = int(n_slabs) if n_slabs is not None else x.shape[0] * int(x_div)
-    if grouped and (not 0 <= int(x_off) < int(x_div) or x.shape[0] != -(-(E + int(x_off)) // int(x_div))):
-        raise _lib.BBBHipError("x_div: x must hold ceil((E + x_off) / x_div) input slabs for the E output slabs")
-    if not grouped and x.shape[0] not in (1, E):
-        raise _lib.BBBHipError("the leading (draw) dim of x must be 1 or the number of slabs")
     if x.shape[1] != cin or w_mu.shape != w_var.shape or w_mu.dim() != 2 or w_mu.shape[1] != bf16_row_pitch(cin * kh * kw):
         raise _lib.BBBHipError("weight pitch / channel count do not match the geometry")
     if moments_only and sample:
         raise _lib.BBBHipError("moments_only: sample=False")
-    cout, B = w_mu.shape[0], x.shape[4]
-    d, ho, wo = _lrt_bf16_desc(x.shape, cout, cin_khkw, stride, padding, dilation, E, x.shape[0] == 1 and E > 1 and not grouped, act)
-    if grouped:
-        d.x_unit_div, d.x_unit_off = int(x_div), int(x_off)
+    (Ex, _, H, W, B), cout = x.shape, w_mu.shape[0]
+    d, ho, wo = conv_desc(B, cin, (H, W), cout, (kh, kw), stride, padding, dilation, act=act)
+    E, _, _ = slab_rule(d, Ex, 1, x_div=x_div, x_off=x_off, n_slabs=n_slabs, weights_shared=True)
     d.b_offset = int(b_offset)
     shape = (E, cout, ho, wo, B)
-    dt = torch.float32 if out_f32 else torch.bfloat16
-    if moments_only:
-        y = None
-    elif out is None:
-        y = torch.empty(shape, dtype=dt, device=x.device)
-    else:
-        if out.numel() != E * cout * ho * wo * B or not out.is_contiguous() or out.dtype != dt:
-            raise _lib.BBBHipError("out= must be a contiguous tensor of the output's size and dtype")
-        y = out.view(shape)
+    y = None if moments_only else _out_tensor(out, shape, torch.float32 if out_f32 else torch.bfloat16, x.device)
     moments = want_moments or moments_only
     am = torch.empty(shape, dtype=torch.float32, device=x.device) if moments else None
     av = torch.empty(shape, dtype=torch.float32, device=x.device) if moments else None
@@ -1388,7 +1215,7 @@ def lrt_conv2d_chwn_bf16_forward(x, w_mu, w_var, b_mu, b_var, cin_khkw, seed, ca
         check(_lib.lib().bbb_lrt_conv2d_chwn_bf16_fwd(ctypes.byref(d), x.data_ptr(), w_mu.data_ptr(), w_var.data_ptr(), ptr(b_mu),
                                                       ptr(b_var), ptr(y), ptr(am), ptr(av), seed, call0 & 0xFFFFFFFF, stream_id,
                                                       1 if sample else 0, rng.call_dev_ptr(x.device),
-                                                      (1 if out_f32 else 0) | (2 if tap_major else 0), cur_stream(x.device)),
+                                                      bf16_flags(out_f32, tap_major), cur_stream(x.device)),
               "bbb_lrt_conv2d_chwn_bf16_fwd")
     return y, am, av
 
@@ -1402,7 +1229,7 @@ def lrt_sample_chwn_bf16(act_mu, act_var, draws, seed, call0, stream_id, act=Non
     y = torch.empty((draws, C, Ho, Wo, B), dtype=torch.bfloat16, device=act_mu.device)
     with on_device(act_mu.device):
         check(_lib.lib().bbb_lrt_sample_chwn_bf16(act_mu.data_ptr(), act_var.data_ptr(), y.data_ptr(), draws, C, Ho * Wo, B,
-                                                  int(b_offset), {None: 0, "relu": 1, "softplus": 2}[act], seed, call0 & 0xFFFFFFFF,
+                                                  int(b_offset), ACT_CODE[act], seed, call0 & 0xFFFFFFFF,
                                                   stream_id, rng.call_dev_ptr(act_mu.device), cur_stream(act_mu.device)),
               "bbb_lrt_sample_chwn_bf16")
     return y
@@ -1805,12 +1632,10 @@ def conv2d_splitk(x, w, bias, stride=1, padding=0, dilation=1):
     would occupy fewer than ~512 workgroups, the input channels are split into S chunks that run as extra "draws" of one
     launch and are summed afterwards in a fixed order (deterministic).  Same result up to fp32 summation order -- which is
     why the inference paths, whose loop / batched forms must agree bit for bit, never come through here."""
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
     Ex, B, Cin, H, W = x.shape
     Ew, Cout, _, kh, kw = w.shape
     E = max(Ex, Ew)
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    ho, wo = out_map(H, W, (kh, kw), stride, padding, dilation)
     tiles = E * -(-B * ho * wo // 64) * -(-Cout // 64)
     S = 1
     while tiles * S < 512 and Cin % (2 * S) == 0 and (Cin // (2 * S)) * kh * kw >= 64:
@@ -1832,11 +1657,9 @@ def conv2d_splitk(x, w, bias, stride=1, padding=0, dilation=1):
 def _small_launch(x, w, stride, padding, dilation):
     """True when a conv of x [E,B,Cin,H,W] with w [*,Cout,Cin,kh,kw] would occupy fewer than 512 64x64 output tiles and its
     channels can be split (the conv2d_splitk criterion)."""
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
     E, B, Cin, H, W = x.shape
     Cout, kh, kw = w.shape[1], w.shape[3], w.shape[4]
-    ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    ho, wo = out_map(H, W, (kh, kw), stride, padding, dilation)
     tiles = E * -(-B * ho * wo // 64) * -(-Cout // 64)
     return tiles < 512 and Cin % 2 == 0 and (Cin // 2) * kh * kw >= 64
 
@@ -2285,12 +2108,14 @@ def conv2d_chwn_input_grad(g_pre, w, x_hw, padding, dilation, w_flipped=None, st
         raise _lib.BBBHipError("conv2d_chwn_input_grad: strides are positive")
     require_device(g_pre, w_t)
     g_pre, w_t = g_pre.contiguous(), w_t.contiguous()
-    E = max(g_pre.shape[0], w_t.shape[0])
-    if g_pre.dim() != 5 or w_t.dim() != 5 or g_pre.shape[0] not in (1, E) or w_t.shape[0] not in (1, E):
-        raise _lib.BBBHipError("leading (draw) dims of g_pre and w must be 1 or equal")
+    if g_pre.dim() != 5 or w_t.dim() != 5:
+        raise _lib.BBBHipError("g_pre [E|1, Cout, Ho, Wo, B] and flipped weights [E|1, Cin, Cout, kh, kw] expected")
     H, W = int(x_hw[0]), int(x_hw[1])
-    d, _, _ = _desc_chwn(g_pre, w_t, 1, (qh, qw), (dh, dw), E, g_pre.shape[0] == 1 and E > 1, w_t.shape[0] == 1 and E > 1, None)
-    gx = torch.empty((E, w_t.shape[1], H, W, g_pre.shape[4]), dtype=torch.float32, device=g_pre.device)
+    Eg, Cout, Ho, Wo, B = g_pre.shape
+    _same_channels(Cout, w_t.shape[2])
+    d, _, _ = conv_desc(B, Cout, (Ho, Wo), w_t.shape[1], (kh, kw), 1, (qh, qw), (dh, dw))        # the stride-1 launch on the flipped weights
+    E, _, _ = slab_rule(d, Eg, w_t.shape[0])
+    gx = torch.empty((E, w_t.shape[1], H, W, B), dtype=torch.float32, device=g_pre.device)
     with on_device(g_pre.device):
         check(_lib.lib().bbb_conv2d_chwn_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
                                                cur_stream(g_pre.device)), "bbb_conv2d_chwn_dgrad")
@@ -2450,9 +2275,11 @@ def im2col_pbj(x_nchw, w_shape, stride, padding, dilation):
     training step may build it off the gradient chain; its elementwise square is the im2col of x^2 (the LRT variance side)."""
     _, Cout, Cin, kh, kw = w_shape
     x_nchw = x_nchw.contiguous()
-    dd, ho, wo = _desc(x_nchw.unsqueeze(0), _Shape((1, Cout, Cin, kh, kw)), stride, padding, dilation, 1, False, False, None)
+    B, x_cin, H, W = x_nchw.shape
+    _same_channels(x_cin, Cin)
+    dd, ho, wo = conv_desc(B, Cin, (H, W), Cout, (kh, kw), stride, padding, dilation)
     Jp = (Cin * kh * kw + 3) // 4 * 4
-    xk = torch.empty((ho * wo, x_nchw.shape[0], Jp), dtype=torch.float32, device=x_nchw.device)
+    xk = torch.empty((ho * wo, B, Jp), dtype=torch.float32, device=x_nchw.device)
     with on_device(x_nchw.device):
         check(_lib.lib().bbb_im2col_pbj(x_nchw.data_ptr(), xk.data_ptr(), ctypes.byref(dd), cur_stream(x_nchw.device)), "bbb_im2col_pbj")
     return xk
@@ -2479,15 +2306,8 @@ def conv2d_chwn_weight_grad_shared_input(g_pre, x_nchw, w_shape, stride, padding
     M = E * Cout
     S = shared_input_k_slices(M, Jp, K)
     Ks = K // S
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = Jp, Ks, 1, 1, M, 1, 1
-    d.stride_h = d.stride_w = d.dil_h = d.dil_w = 1
-    d.pad_h = d.pad_w = 0
-    d.draws = S
-    d.x_draw_stride = Ks * Jp
-    d.w_draw_stride = Ks
-    d.b_draw_stride = 0
-    d.act = 0
+    # the 1x1 "layer": Jp "images" of Ks channels, M filters; its S draws are the K slices, Ks columns apart inside G's rows
+    d, _, _ = conv_desc(Jp, Ks, (1, 1), M, (1, 1), draws=S, w_stride=Ks, b_stride=0)
     # G's rows must not be a multiple of 4 KiB apart (128 KiB for 64 pixels x 512 images: the 64 rows of a weight tile would
     # all sit in the same memory channel).  pool_act_backward_chwn(pad_planes=True) already wrote g_pre at the padded pitch;
     # anything else is copied once.
@@ -2550,8 +2370,10 @@ def first_layer_input_grad(g_pre, w, x_hw, stride, padding, dilation, x_lrt=None
     Cin, kh, kw = ws[0].shape[-3:]
     H, W = int(x_hw[0]), int(x_hw[1])
     J, M = Cin * kh * kw, E * Cout
-    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
-    if ((H + 2 * ph - dh * (kh - 1) - 1) // sh + 1 != Ho or (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1 != Wo
+    # (the layer itself, for bbb_input_grad_col2im: one slab, no operand of its own)
+    d, ho, wo = conv_desc(B, Cin, (H, W), 1, (kh, kw), stride, padding, dilation, w_stride=0, b_stride=0)
+    d.x_draw_stride = 0
+    if ((ho, wo) != (Ho, Wo)
             or any(t.numel() != M * J for t in ws) or (lrt and (len(gs) != 2 or x_lrt.numel() != B * Cin * H * W))):
         raise _lib.BBBHipError("first_layer_input_grad: geometry mismatch")
     xg, P = _gemm_rows(gs)
@@ -2560,10 +2382,6 @@ def first_layer_input_grad(g_pre, w, x_hw, stride, padding, dilation, x_lrt=None
         for i, t in enumerate(ws):
             check(_lib.lib().bbb_transpose2d(t.data_ptr(), wt[i].data_ptr(), M, J, cur_stream(xg.device)), "bbb_transpose2d")
     dcol = conv2d_chwn_forward(xg, wt, None)                          # [len(gs), J, 1, 1, P]
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, Cin, H, W, 1, kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w = sh, sw, ph, pw, dh, dw
-    d.draws = 1
     xc = x_lrt.contiguous() if lrt else None
     dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=xg.device)
     with on_device(dx.device):
@@ -2640,18 +2458,10 @@ def flip_transpose_w_bf16(w, w_shape):
     return out
 
 
-def _bf16_dgrad_desc(B, cin, cout, kh, kw, g_hw, pad, dilation, E, g_shared=False, w_shared=False):
-    """The descriptor of bbb_conv2d_chwn_bf16_dgrad: the stride-1 launch on the flipped rows of a layer with weights (cout, cin, kh,
-    kw) over g's map g_hw, pad = dilation * (k - 1) - the layer's padding."""
-    (dh, dw), (qh, qw) = _pair(dilation), _pair(pad)
-    d = ConvDesc()
-    d.batch, d.cin, d.h, d.w, d.cout, d.kh, d.kw = B, cout, g_hw[0], g_hw[1], cin, kh, kw
-    d.stride_h = d.stride_w = 1
-    d.pad_h, d.pad_w, d.dil_h, d.dil_w = qh, qw, dh, dw
-    d.draws = E
-    d.x_draw_stride = 0 if g_shared else cout * g_hw[0] * g_hw[1] * B
-    d.w_draw_stride = 0 if w_shared else cin * bf16_row_pitch(cout * kh * kw)
-    return d
+def _bf16_dgrad_launch(B, cin, cout, kh, kw, g_hw, pad, dilation, draws):
+    """The descriptor of bbb_conv2d_chwn_bf16_dgrad: the stride-1 launch on the flipped rows [cin, Kp'] of a layer with weights (cout,
+    cin, kh, kw) over g's map g_hw, pad = dilation * (k - 1) - the layer's padding."""
+    return conv_desc(B, cout, g_hw, cin, (kh, kw), 1, pad, dilation, draws, w_stride=cin * bf16_row_pitch(cout * kh * kw), b_stride=0)[0]
 
 
 def bf16_dgrad_form(B, cin, cout, kh, kw, x_hw, stride, dilation, draws):
@@ -2663,8 +2473,8 @@ def bf16_dgrad_form(B, cin, cout, kh, kw, x_hw, stride, dilation, draws):
     (sh, sw), (dh, dw) = _pair(stride), _pair(dilation)
     H, W = int(x_hw[0]), int(x_hw[1])
     tap_major = bf16_tap_major((cin, cout, kh, kw))
-    g_hw = ((H + dh * (kh - 1) - 1) // sh + 1, (W + dw * (kw - 1) - 1) // sw + 1)
-    d = _bf16_dgrad_desc(B, cin, cout, kh, kw, g_hw, 0, (dh, dw), int(draws))
+    g_hw = out_map(H, W, (kh, kw), (sh, sw), (dh * (kh - 1), dw * (kw - 1)), (dh, dw))
+    d = _bf16_dgrad_launch(B, cin, cout, kh, kw, g_hw, 0, (dh, dw), int(draws))
     shape, kg, ws = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
     check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad_plan(ctypes.byref(d), sh, sw, H, W, 2 if tap_major else 0, ctypes.byref(shape),
                                                      ctypes.byref(kg), ctypes.byref(ws)), "bbb_conv2d_chwn_bf16_dgrad_plan")
@@ -2695,14 +2505,13 @@ def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_fl
         raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: strides are positive")
     require_device(g_pre, w_t, dtype=torch.bfloat16)
     g_pre, w_t = g_pre.contiguous(), w_t.contiguous()
-    E = max(g_pre.shape[0], w_t.shape[0])
-    if g_pre.dim() != 5 or w_t.dim() != 3 or g_pre.shape[0] not in (1, E) or w_t.shape[0] not in (1, E):
-        raise _lib.BBBHipError("leading (draw) dims of g_pre and w must be 1 or equal")
+    if g_pre.dim() != 5 or w_t.dim() != 3:
+        raise _lib.BBBHipError("g_pre [E|1, Cout, Ho, Wo, B] and flipped rows [E|1, Cin, Kp] expected")
     if g_pre.shape[1] != Cout or w_t.shape[1] != Cin or w_t.shape[2] != bf16_row_pitch(Cout * kh * kw):
         raise _lib.BBBHipError("conv2d_chwn_input_grad_bf16: rows do not match the weight shape")
     H, W, B = int(x_hw[0]), int(x_hw[1]), g_pre.shape[4]
-    d = _bf16_dgrad_desc(B, Cin, Cout, kh, kw, (g_pre.shape[2], g_pre.shape[3]), (qh, qw), (dh, dw), E,
-                         g_pre.shape[0] == 1 and E > 1, w_t.shape[0] == 1 and E > 1)
+    d = _bf16_dgrad_launch(B, Cin, Cout, kh, kw, (g_pre.shape[2], g_pre.shape[3]), (qh, qw), (dh, dw), 1)
+    E, _, _ = slab_rule(d, g_pre.shape[0], w_t.shape[0])
     gx = torch.empty((E, Cin, H, W, B), dtype=torch.bfloat16, device=g_pre.device)
     with on_device(g_pre.device):
         check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
