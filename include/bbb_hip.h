@@ -152,7 +152,12 @@ int bbb_adam_step(const bbb_adam_segment_t* segs, int nseg, double lr, double be
 /* Test entry: materialise n elements of a noise stream starting at element `start`. */
 int bbb_eps_dump(float* out, int64_t n, int64_t start, uint64_t seed, uint32_t call, uint32_t stream_id, void* stream);
 
-/* Geometry of one conv2d / linear contraction, batched over Monte-Carlo draws. */
+/* Geometry of one conv2d / linear contraction, batched over Monte-Carlo draws.
+ * Every entry that takes one makes the same checks on it first (csrc/conv_desc_check.h): sizes, strides and dilations are positive
+ * and paddings non-negative (BBB_EINVAL); the output map ho = (h + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1 (wo alike) exists and
+ * fits an int (BBB_ESHAPE).  A kernel that reaches past the padded input -- h + 2 pad_h - dil_h (kh - 1) - 1 < 0 on either axis --
+ * has no output pixel and is BBB_ESHAPE in EVERY entry, whatever the stride (before this rule only bbb_conv2d_chwn_fwd and its
+ * split / LRT forms refused it; the others let C's division round the negative numerator towards zero and computed one row). */
 typedef struct bbb_conv_desc {
     int32_t batch;        /* B images per draw */
     int32_t cin, h, w;    /* input  [draws|1][B][cin][h][w]  (linear: h = w = 1) */
@@ -315,6 +320,37 @@ int bbb_c8s3_convert(const void* src, void* dst, int64_t slabs, int channels, in
 int bbb_lrt_conv2d_c8x3_fwd(const bbb_conv_desc_t* d, const void* x, const float* w_mu, const float* w_var, const float* b_mu,
                             const float* b_var, void* y, uint64_t seed, uint32_t call0, uint32_t stream_id, int sample,
                             const uint32_t* call_dev, uint32_t flags, void* stream);
+/*
+ * bbb_conv2d_c8x3_plan: which of its 20 kernel instantiations bbb_conv2d_c8x3_fwd (lrt == 0) or bbb_lrt_conv2d_c8x3_fwd (lrt != 0)
+ * starts for this descriptor and flags word.  Host only: launches nothing, needs no device.  *form: BBB_C8X3_FORM_*; *nt: 32-channel
+ * tiles per workgroup (2 | 3 | 4); *images_per_wg: 128 | 256 (pooled: 32 | 64); *items: work items; *blocks: workgroups (items rounded
+ * up to 8).  Out-pointers may be NULL.  Returns 0 or what the launch entry returns for every check that does not involve an operand
+ * pointer; the two call the same plan (csrc/pconv_c8x3_plan.h).
+ * Forms: ((NT - 2) * 2 + (MT - 1)) * 3 + output, MT = 32-image fragments per wave, output 0 = c8 S3, 1 = fp32, 2 = pooled c8 S3;
+ * then the two LRT instantiations (NT 2, MT 1).
+ */
+#define BBB_C8X3_FORM_NT2_MT1_S3 0
+#define BBB_C8X3_FORM_NT2_MT1_F32 1
+#define BBB_C8X3_FORM_NT2_MT1_POOL 2
+#define BBB_C8X3_FORM_NT2_MT2_S3 3
+#define BBB_C8X3_FORM_NT2_MT2_F32 4
+#define BBB_C8X3_FORM_NT2_MT2_POOL 5
+#define BBB_C8X3_FORM_NT3_MT1_S3 6
+#define BBB_C8X3_FORM_NT3_MT1_F32 7
+#define BBB_C8X3_FORM_NT3_MT1_POOL 8
+#define BBB_C8X3_FORM_NT3_MT2_S3 9
+#define BBB_C8X3_FORM_NT3_MT2_F32 10
+#define BBB_C8X3_FORM_NT3_MT2_POOL 11
+#define BBB_C8X3_FORM_NT4_MT1_S3 12
+#define BBB_C8X3_FORM_NT4_MT1_F32 13
+#define BBB_C8X3_FORM_NT4_MT1_POOL 14
+#define BBB_C8X3_FORM_NT4_MT2_S3 15
+#define BBB_C8X3_FORM_NT4_MT2_F32 16
+#define BBB_C8X3_FORM_NT4_MT2_POOL 17
+#define BBB_C8X3_FORM_LRT_S3 18
+#define BBB_C8X3_FORM_LRT_F32 19
+int bbb_conv2d_c8x3_plan(const bbb_conv_desc_t* d, uint32_t flags, int lrt, int32_t* form, int32_t* nt, int32_t* images_per_wg,
+                         int64_t* items, int64_t* blocks);
 int bbb_maxpool_chwn_s3sq(const void* x, void* y, int64_t slabs, int channels, int h, int w, int batch, int k, int s, void* stream);
 int bbb_s2d_c8s3sq(const float* x, void* y, int64_t blocks, int batch, int channels, int h, int w, int k, int stride, int pad, void* stream);
 /*
@@ -675,6 +711,12 @@ int bbb_input_grad_col2im(const float* dcol, int64_t row_pitch, int64_t set_stri
  * bbb_conv2d_chwn_fwd on the flipped weights: there is one way to compute it). */
 int bbb_conv2d_chwn_dgrad(const bbb_conv_desc_t* d, const float* g_pre, const float* w_flipped, float* dx, int up_h, int up_w,
                           int out_h, int out_w, void* stream);
+/* What that launch takes (host only, no device): *bm images per item (64 | 128), *ilv staging loads interleaved, *items, *blocks --
+ * the tile and interleave choice bbb_conv2d_chwn_fwd makes for a plain launch of the same pixels, channels, images and draws (one
+ * rule, csrc/pconv_plan.h).  Returns 0 or what the launch entry returns for every check that does not involve an operand pointer.
+ * Out-pointers may be NULL.  The sibling of bbb_conv2d_chwn_bf16_dgrad_plan. */
+int bbb_conv2d_chwn_dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, int out_w, int32_t* bm, int32_t* ilv,
+                               int64_t* items, int64_t* blocks);
 
 /* Training extension, the small steps between the gradient GEMMs (ABI 8; deterministic, no atomics):
  * bbb_plane_sum: out[r] = sum over o < outer, j < cols of x[o*outer_stride + r*row_pitch + j] -- bias gradients (the gradient w.r.t.

@@ -69,6 +69,8 @@ _SIGNATURES = {
     "bbb_maxpool_chwn_s3": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bbb_s3_convert": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p]),
     "bbb_conv2d_c8x3_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_u32, c_void_p]),
+    "bbb_conv2d_c8x3_plan": (c_int, [ctypes.POINTER(ConvDesc), c_u32, c_int, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                     ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "bbb_c8s3_convert": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
     "bbb_w_tap_major": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
     "bbb_s2d_c8s3": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
@@ -120,6 +122,8 @@ _SIGNATURES = {
     "bbb_im2col_pbj": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ConvDesc), c_void_p]),
     "bbb_input_grad_col2im": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, ctypes.POINTER(ConvDesc), c_void_p]),
     "bbb_conv2d_chwn_dgrad": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "bbb_conv2d_chwn_dgrad_plan": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, c_int, c_int, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                           ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "bbb_transpose_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_void_p]),
     "bbb_transpose_sum_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64),
                                           ctypes.POINTER(c_i64), c_i64, c_i64, c_int, c_i64, c_i64, c_void_p]),

@@ -777,6 +777,27 @@ def conv2d_c8x3_forward(x, w_tm, bias, kernel_size, stride=1, padding=0, dilatio
     return y
 
 
+# BBB_C8X3_FORM_* (include/bbb_hip.h): 32-channel tiles per workgroup x 32-image fragments per wave x output, then the LRT pair
+C8X3_FORMS = tuple(f"nt{nt}-mt{mt}-{out}" for nt in (2, 3, 4) for mt in (1, 2) for out in ("s3", "f32", "pool")) + ("lrt-s3", "lrt-f32")
+
+
+def c8x3_fwd_plan(x_shape, cout, kernel_size, stride=1, padding=0, dilation=1, draws=None, out_f32=False, tile=None, nt=None, pool=False,
+                  lrt=False, zero_border=(0, 0, 0, 0)):
+    """(form, nt, images per workgroup, items, workgroups) of the launch conv2d_c8x3_forward (lrt=False) or lrt_conv2d_c8x3_forward
+    (lrt=True) makes for x_shape = [*, Cin, H, W, B] (the logical shape, not the c8 S3 one) and `draws` output slabs: form one of
+    C8X3_FORMS (bbb_conv2d_c8x3_plan, the launch entries' own plan, csrc/pconv_c8x3_plan.h; host only: needs no device).  A geometry
+    or a flag combination the launch refuses raises the launch's error."""
+    E = int(draws) if draws is not None else x_shape[0]
+    Cin, H, W, B = x_shape[-4:]
+    d, _, _ = conv_desc(B, Cin, (H, W), cout, _pair(kernel_size), stride, padding, dilation, E, x_planes=6 if lrt else 3,
+                        w_stride=0 if lrt else None, b_stride=0 if lrt else None)
+    flags = c8x3_flags(out_f32, tile, zero_border, nt, bool(pool))
+    fm, ntv, ipw, items, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.lib().bbb_conv2d_c8x3_plan(ctypes.byref(d), flags, 1 if lrt else 0, ctypes.byref(fm), ctypes.byref(ntv), ctypes.byref(ipw),
+                                          ctypes.byref(items), ctypes.byref(blocks)), "bbb_conv2d_c8x3_plan")
+    return C8X3_FORMS[fm.value], ntv.value, ipw.value, items.value, blocks.value
+
+
 def maxpool_c8s3(x, k, s):
     """MaxPool2d(k, s) on a c8 S3 tensor [E, 3, C / 8, H, W, B, 8] (element-wise on the 16-byte channel vectors); six-plane slabs
     (the LRT chain): the maximum of the values, and the squares of the pooled values behind."""
@@ -2120,6 +2141,22 @@ def conv2d_chwn_input_grad(g_pre, w, x_hw, padding, dilation, w_flipped=None, st
         check(_lib.lib().bbb_conv2d_chwn_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
                                                cur_stream(g_pre.device)), "bbb_conv2d_chwn_dgrad")
     return gx
+
+
+def fp32_dgrad_plan(B, cin, cout, kh, kw, x_hw, stride, dilation, draws, padding=None):
+    """(images per item 64 | 128, interleaved staging, items, workgroups) of the launch bbb_conv2d_chwn_dgrad makes for the input
+    gradient of a strided layer with weights (cout, cin, kh, kw), input map x_hw = (H, W), `draws` draws of B images: the launch
+    entry's own plan (bbb_conv2d_chwn_dgrad_plan, csrc/pconv_plan.h: dgrad_plan -- the forward's tile rule; host only).  padding:
+    the layer's (default dilation * (k - 1), whose output map exists for every input map; the choice does not depend on it)."""
+    (sh, sw), (dh, dw) = _pair(stride), _pair(dilation)
+    H, W = int(x_hw[0]), int(x_hw[1])
+    ph, pw = (dh * (kh - 1), dw * (kw - 1)) if padding is None else _pair(padding)
+    g_hw = out_map(H, W, (kh, kw), (sh, sw), (ph, pw), (dh, dw))
+    d, _, _ = conv_desc(B, cout, g_hw, cin, (kh, kw), 1, (dh * (kh - 1) - ph, dw * (kw - 1) - pw), (dh, dw), int(draws))
+    bm, ilv, items, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.lib().bbb_conv2d_chwn_dgrad_plan(ctypes.byref(d), sh, sw, H, W, ctypes.byref(bm), ctypes.byref(ilv), ctypes.byref(items),
+                                                ctypes.byref(blocks)), "bbb_conv2d_chwn_dgrad_plan")
+    return bm.value, bool(ilv.value), items.value, blocks.value
 
 
 def _transpose_batched(src, out, rows, cols, nb1, nb2, ib1, ib2, ir, ob1, ob2, oc):

@@ -25,6 +25,7 @@
 
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
+#include "conv_desc_check.h"
 
 namespace {
 
@@ -295,19 +296,16 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const ConvArgs p) {
 
 int check_desc(const bbb_conv_desc_t* d, ConvArgs& a) {
     if (d == nullptr) return BBB_EINVAL;
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 ||
-        d->draws <= 0 || d->act < 0 || d->act > 2)
-        return BBB_EINVAL;
-    if (d->unit_div > 1 || d->x_unit_mod != 0 || d->b_offset != 0 || d->w_row_pitch != 0 || d->x_unit_div > 1 || d->x_unit_off != 0 || d->pool != 0 || d->w_tap_major != 0) return BBB_EINVAL;   // batch-innermost entries only
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    const int64_t M = (int64_t)d->batch * ho * wo;
-    const int64_t K = (int64_t)d->cin * d->kh * d->kw;
+    using namespace conv_desc_check;
+    if (!positive_geometry(d) || d->act < 0 || d->act > 2) return BBB_EINVAL;
+    if (unit_fields(d, kNothing) != 0 || d->w_row_pitch != 0 || d->pool != 0 || d->w_tap_major != 0) return BBB_EINVAL;   // batch-innermost entries only
+    int32_t ho = 0, wo = 0;
+    if (const int rc = out_map(d, &ho, &wo)) return rc;
+    const int64_t M = mul_cap(d->batch, ho, wo);
+    const int64_t K = mul_cap(d->cin, d->kh, d->kw);
     if (M > 0x7fffffffLL || K > 0x7fffffffLL) return BBB_ESHAPE;
-    if ((int64_t)d->cin * d->h * d->w > 0x7fffffffLL) return BBB_ESHAPE;     // per-image offsets are int32
-    if (d->h + d->pad_h + d->dil_h * d->kh >= 0x7000 || d->w + d->pad_w + d->dil_w * d->kw >= 0x7000) return BBB_ESHAPE;
+    if (mul_cap(d->cin, d->h, d->w) > 0x7fffffffLL) return BBB_ESHAPE;     // per-image offsets are int32
+    if ((int64_t)d->h + d->pad_h + (int64_t)d->dil_h * d->kh >= 0x7000 || (int64_t)d->w + d->pad_w + (int64_t)d->dil_w * d->kw >= 0x7000) return BBB_ESHAPE;
     a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
     a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
     a.Ho = ho; a.Wo = wo; a.M = (int32_t)M; a.K = (int32_t)K; a.HoWo = ho * wo; a.khkw = d->kh * d->kw;

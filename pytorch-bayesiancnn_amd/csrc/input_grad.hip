@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "conv_desc_check.h"
 
 namespace {
 
@@ -80,19 +81,17 @@ __global__ __launch_bounds__(256) void col2im_nchw_kernel(const float* __restric
 
 extern "C" int bbb_input_grad_col2im(const float* dcol, int64_t row_pitch, int64_t set_stride, const float* x, float* dx,
                                      const bbb_conv_desc_t* d, void* stream) {
-    if (dcol == nullptr || dx == nullptr || d == nullptr || d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->kh <= 0 ||
-        d->kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
-        return BBB_EINVAL;
+    using conv_desc_check::mul_cap;
+    if (dcol == nullptr || dx == nullptr || d == nullptr || !conv_desc_check::positive_map(d)) return BBB_EINVAL;
     if ((((uintptr_t)dcol | (uintptr_t)x | (uintptr_t)dx) & 3u) != 0) return BBB_EALIGN;
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    const int64_t J = (int64_t)d->cin * d->kh * d->kw;
-    if (J > 0x7fffffffLL || row_pitch < (int64_t)ho * wo * d->batch) return BBB_ESHAPE;
-    if (x != nullptr && set_stride < J * row_pitch) return BBB_ESHAPE;           // the two sets of an LRT layer must not overlap
-    const int64_t chw = (int64_t)d->cin * d->h * d->w;
+    int32_t ho = 0, wo = 0;
+    if (const int rc = conv_desc_check::out_map(d, &ho, &wo)) return rc;
+    const int64_t J = mul_cap(d->cin, d->kh, d->kw);
+    if (J > 0x7fffffffLL || row_pitch < mul_cap(ho, wo, d->batch)) return BBB_ESHAPE;
+    if (x != nullptr && set_stride < mul_cap(J, row_pitch)) return BBB_ESHAPE;   // the two sets of an LRT layer must not overlap
+    const int64_t chw = mul_cap(d->cin, d->h, d->w);
     const int64_t p_tiles = (chw + kTileP - 1) / kTileP;
-    const int64_t blocks = p_tiles * ((d->batch + kTileB - 1) / kTileB);
+    const int64_t blocks = mul_cap(p_tiles, (d->batch + kTileB - 1) / kTileB);
     if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
     if (x != nullptr)
         hipLaunchKernelGGL(col2im_nchw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dcol, row_pitch, set_stride,

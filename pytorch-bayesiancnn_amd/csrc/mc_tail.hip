@@ -9,6 +9,7 @@
 
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
+#include "conv_desc_check.h"
 
 namespace {
 
@@ -719,15 +720,15 @@ extern "C" int bbb_transpose_sum_batched(const float* in, float* out, int rows, 
 }
 
 extern "C" int bbb_im2col_pbj(const float* x, float* out, const bbb_conv_desc_t* d, void* stream) {
-    if (x == nullptr || out == nullptr || d == nullptr || d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->kh <= 0 ||
-        d->kw <= 0 || d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0)
-        return BBB_EINVAL;
+    using conv_desc_check::mul_cap;
+    if (x == nullptr || out == nullptr || d == nullptr || !conv_desc_check::positive_map(d)) return BBB_EINVAL;
     if ((((uintptr_t)x | (uintptr_t)out) & 3u) != 0) return BBB_EALIGN;
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    const int J = d->cin * d->kh * d->kw, Jp = (J + 3) / 4 * 4;
-    const int64_t total = (int64_t)ho * wo * d->batch * Jp;
+    int32_t ho = 0, wo = 0;
+    if (const int rc = conv_desc_check::out_map(d, &ho, &wo)) return rc;
+    const int64_t J64 = mul_cap(d->cin, d->kh, d->kw);
+    if (J64 > 0x7ffffffcLL) return BBB_ESHAPE;                 // (the row pitch J rounded up to 4 is an int)
+    const int J = (int)J64, Jp = (J + 3) / 4 * 4;
+    const int64_t total = mul_cap(ho, wo, d->batch, Jp);
     const int64_t blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
     hipLaunchKernelGGL(im2col_pbj_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, out, total, d->batch, d->cin,

@@ -1,5 +1,5 @@
-// Kernel-argument block shared by the pixel-major GEMM variants (pconv_gemm.hip, pconv_bf16.hip), and the tap enumeration of their
-// transposed forms (tr_axis).
+// Kernel-argument block shared by the five pixel-major GEMM families (pconv_gemm.hip, pconv_dgrad.hip, pconv_bf16.hip,
+// pconv_bf16_lrt.hip, pconv_c8x3.hip), and the tap enumeration of the transposed forms (tr_axis: pconv_dgrad.hip, pconv_bf16.hip).
 #pragma once
 #include <stdint.h>
 

@@ -554,12 +554,9 @@ extern "C" int bbb_lrt_conv2d_chwn_bf16_fwd(const bbb_conv_desc_t* d, const void
     if ((b_mu == nullptr) != (b_var == nullptr) || (act_mu_out == nullptr) != (act_var_out == nullptr)) return BBB_EINVAL;
     if (y == nullptr && (act_mu_out == nullptr || sample)) return BBB_EINVAL;        // y may be left out of a moments-only launch
     if (d->w_draw_stride != 0 || d->b_draw_stride != 0) return BBB_EINVAL;           // LRT weights are shared by the slabs
-    if (d->unit_div > 1 || d->unit_off != 0 || d->x_unit_mod != 0 || d->w_row_pitch != 0 || d->w_tap_major != 0 || d->pool != 0 ||
+    if (conv_desc_check::unit_fields(d, conv_desc_check::kSteps) != 0 || d->w_row_pitch != 0 || d->w_tap_major != 0 || d->pool != 0 ||
         d->b_offset < 0)
-        return BBB_EINVAL;                                                           // no work units, no pooled form
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && d->x_unit_off >= d->x_unit_div) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
+        return BBB_EINVAL;                                                           // steps per launch, no work units, no pooled form
     if (const int rc = bf16_plan::vector_rows(d, tap_major)) return rc;
     bf16_plan::Geom g;
     if (const int rc = bf16_plan::slab_limits(d, p.ho, p.wo, bf16_plan::kLrtLimits, &g)) return rc;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "conv_desc_check.h"
 
 namespace bf16_plan {
 
@@ -15,9 +16,9 @@ constexpr int LDWB = BK + 8;             // weight row pitch (elements): 144 B
 constexpr int KCH = 256;                 // k entries per decode chunk and k-group
 constexpr int kWinPasses = 13;           // 16-row passes of the window loader: windows of up to 13 * 16 - 1 = 207 image rows (+ the zero row)
 
-// a * b for positive factors, capped far above every limit it is compared with (no signed overflow on absurd descriptors)
-constexpr int64_t kCap = (int64_t)1 << 62;
-inline int64_t mul_cap(int64_t a, int64_t b) { return a > kCap / b ? kCap : a * b; }
+using conv_desc_check::mul_cap;
+using conv_desc_check::out_map;
+using conv_desc_check::positive_geometry;
 inline int64_t cdiv(int64_t n, int64_t t) { return (n + t - 1) / t; }
 
 inline int gcd_i(int a, int b) {
@@ -37,22 +38,9 @@ struct Geom {
 struct Limits { int y_esize; int64_t y_bound; int w_pad_rows; };
 constexpr Limits kFwdLimits = {4, 0xFFFE0000LL, 64}, kDgradLimits = {2, 0xFFFE0000LL, 64}, kLrtLimits = {4, 0x7FFE0000LL, 128};
 
-inline bool positive_geometry(const bbb_conv_desc_t* d) {
-    return d->batch > 0 && d->cin > 0 && d->h > 0 && d->w > 0 && d->cout > 0 && d->kh > 0 && d->kw > 0 && d->pad_h >= 0 &&
-           d->pad_w >= 0 && d->dil_h > 0 && d->dil_w > 0 && d->draws > 0;
-}
-
 inline int vector_rows(const bbb_conv_desc_t* d, bool tap_major) {
     if (d->batch % 8 != 0) return BBB_ESHAPE;               // rows of 16-byte vectors of 8 bf16 images
     if (tap_major && d->cin % 8 != 0) return BBB_ESHAPE;    // a 16-byte weight vector must not straddle two taps
-    return 0;
-}
-
-inline int out_map(const bbb_conv_desc_t* d, int32_t* ho, int32_t* wo) {
-    const int64_t h = ((int64_t)d->h + 2 * (int64_t)d->pad_h - (int64_t)d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int64_t w = ((int64_t)d->w + 2 * (int64_t)d->pad_w - (int64_t)d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (h <= 0 || w <= 0 || h > 0x7fffffffLL || w > 0x7fffffffLL) return BBB_ESHAPE;
-    *ho = (int32_t)h; *wo = (int32_t)w;
     return 0;
 }
 
@@ -117,11 +105,7 @@ inline int tile_grid(int shape, const TileWork& w, TileGrid* t) {
     const int64_t mt = mul_cap(w.pixels, t->nbt);
     if (mt > 0x7fffffffLL) return BBB_ESHAPE;
     t->Mtiles = (int32_t)mt;
-    const int64_t per = (G * mt + 7) / 8;
-    t->blocks = 8 * per;
-    if (t->blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    t->per_xcd = (int32_t)per;
-    return 0;
+    return conv_desc_check::xcd_grid(G * mt, &t->per_xcd, &t->blocks);
 }
 
 // A second k-group (its own stage, its own loads in flight, deterministic LDS reduction) when the launch cannot fill the chip with
@@ -177,20 +161,14 @@ struct FwdPlan {
     int smem_bytes;            // window-resident form: its dynamic LDS
 };
 
-inline int xcd_blocks(int64_t items, FwdPlan* p) {
-    const int64_t per = (items + 7) / 8;
-    if (8 * per > 0x7fffffffLL) return BBB_ESHAPE;
-    p->f.per_xcd = (int32_t)per;
-    p->blocks = 8 * per;
-    return 0;
-}
+inline int xcd_blocks(int64_t items, FwdPlan* p) { return conv_desc_check::xcd_grid(items, &p->f.per_xcd, &p->blocks); }
 
 // ptr_rc: what the entry's pointer-alignment check found (0 | BBB_EALIGN), returned at its place in the order of checks
 inline int fwd_plan(const bbb_conv_desc_t* d, uint32_t flags, int ptr_rc, FwdPlan* p) {
     *p = FwdPlan{};
     const bool out_f32 = (flags & BBB_BF16_OUT_F32) != 0, tap_major = (flags & BBB_BF16_W_TAP_MAJOR) != 0;
     if (d == nullptr) return BBB_EINVAL;
-    if (!positive_geometry(d) || d->stride_h <= 0 || d->stride_w <= 0 || d->act < 0 || d->act > 2) return BBB_EINVAL;
+    if (!positive_geometry(d) || d->act < 0 || d->act > 2) return BBB_EINVAL;
     if (const int rc = vector_rows(d, tap_major)) return rc;
     if ((flags & ~(BBB_BF16_OUT_F32 | BBB_BF16_W_TAP_MAJOR | BBB_BF16_X_C8 | BBB_BF16_OUT_C8)) != 0) return BBB_EINVAL;
     const bool x_c8 = (flags & BBB_BF16_X_C8) != 0, out_c8 = (flags & BBB_BF16_OUT_C8) != 0;
@@ -200,9 +178,8 @@ inline int fwd_plan(const bbb_conv_desc_t* d, uint32_t flags, int ptr_rc, FwdPla
     if (ptr_rc) return ptr_rc;
     if ((d->x_draw_stride & 7) != 0 || (d->w_draw_stride & 7) != 0) return BBB_EALIGN;
     const int64_t K = p->g.K, Kp = p->g.Kp;
-    if (d->unit_div < 0 || d->unit_off < 0 || d->x_unit_mod < 0 || (d->unit_div > 1 && d->unit_off >= d->unit_div) ||
-        (d->x_unit_mod > 0 && d->x_unit_mod != d->unit_div) || d->w_row_pitch != 0 || d->w_tap_major != 0)
-        return BBB_EINVAL;
+    // (the checks from here to the end of the pooled form's admission all return BBB_EINVAL)
+    if (conv_desc_check::unit_fields(d, conv_desc_check::kUnitsAndSteps) != 0 || d->w_row_pitch != 0 || d->w_tap_major != 0) return BBB_EINVAL;
     // pooling in the launch (bbb_conv_desc_t::pool): first layers with a short contraction only (pconv_bf16_smallk_pool_kernel);
     // 1 = MaxPool2d(2, 2), (k << 8) | s otherwise; admitted: 2 / 2 and 3 / 2 (at most one window closes per conv column)
     int pool_k = 0, pool_s = 0;
@@ -213,9 +190,6 @@ inline int fwd_plan(const bbb_conv_desc_t* d, uint32_t flags, int ptr_rc, FwdPla
         if (tap_major || out_f32 || Kp > 128) return BBB_EINVAL;
         if (x_c8 || (out_c8 && d->cout % 8 != 0)) return BBB_EINVAL;
     }
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && (d->unit_div > 1 || d->x_unit_off >= d->x_unit_div)) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
     LaunchFields& f = p->f;
     p->y_ds = (int64_t)d->cout * ho * wo * d->batch;
     // the small-k forms' tiles: weights in registers, 32 * nt channels x 256 images
@@ -354,8 +328,8 @@ inline int dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, i
     // d describes the stride-1 launch on the flipped rows; the layer's stride travels as the upsampling factors
     if (d->stride_h != 1 || d->stride_w != 1) return BBB_EINVAL;
     if (up_h == 1 && up_w == 1) return BBB_EINVAL;          // a stride-1 layer's gradient is bbb_conv2d_chwn_bf16_fwd: one way to compute it
-    if (d->act != 0 || d->pool != 0 || d->w_tap_major != 0 || d->w_row_pitch != 0 || d->unit_div != 0 || d->unit_off != 0 ||
-        d->x_unit_mod != 0 || d->x_unit_div != 0 || d->x_unit_off != 0 || d->b_offset != 0)
+    if (d->act != 0 || d->pool != 0 || d->w_tap_major != 0 || d->w_row_pitch != 0 ||
+        conv_desc_check::unit_fields(d, conv_desc_check::kNothing) != 0)
         return BBB_EINVAL;
     if (d->x_draw_stride < 0 || d->w_draw_stride < 0) return BBB_EINVAL;
     if ((flags & ~BBB_BF16_W_TAP_MAJOR) != 0) return BBB_EINVAL;
@@ -365,8 +339,10 @@ inline int dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, i
     const int64_t rh = (int64_t)d->dil_h * (d->kh - 1), rw = (int64_t)d->dil_w * (d->kw - 1);
     const int64_t fph = rh - d->pad_h, fpw = rw - d->pad_w;
     if (fph < 0 || fpw < 0) return BBB_ESHAPE;
-    const int64_t nh = (int64_t)out_h + 2 * fph - rh - 1, nw = (int64_t)out_w + 2 * fpw - rw - 1;
-    if (nh < 0 || nw < 0 || nh / up_h + 1 != d->h || nw / up_w + 1 != d->w) return BBB_ESHAPE;
+    int32_t gh = 0, gw = 0;
+    if (conv_desc_check::out_axis(out_h, fph, d->dil_h, d->kh, up_h, &gh) != 0 ||
+        conv_desc_check::out_axis(out_w, fpw, d->dil_w, d->kw, up_w, &gw) != 0 || gh != d->h || gw != d->w)
+        return BBB_ESHAPE;
     // per-draw slabs are addressed through 32-bit buffer offsets (as in the forward's checks)
     if (const int rc = slab_limits(d, out_h, out_w, kDgradLimits, &p->g)) return rc;
     if (ptr_rc) return ptr_rc;
@@ -384,7 +360,7 @@ struct LrtPlan { int32_t ho, wo; TileWork work; TileChoice tile; };
 
 inline int lrt_plan(const bbb_conv_desc_t* d, LrtPlan* p) {
     *p = LrtPlan{};
-    if (d == nullptr || !positive_geometry(d) || d->stride_h <= 0 || d->stride_w <= 0) return BBB_EINVAL;
+    if (d == nullptr || !positive_geometry(d)) return BBB_EINVAL;
     if (const int rc = out_map(d, &p->ho, &p->wo)) return rc;
     p->work = {d->cout, d->batch, d->draws, (int64_t)p->ho * p->wo};
     const int64_t t64 = cdiv(mul_cap(mul_cap(d->cin, d->kh), d->kw), BK);

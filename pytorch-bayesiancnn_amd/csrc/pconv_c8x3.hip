@@ -23,6 +23,7 @@
 #include "bbb_common.cuh"
 #include "pconv_args.h"
 #include "pconv_bf16x3.cuh"
+#include "pconv_c8x3_plan.h"
 
 namespace pconv {
 
@@ -615,78 +616,28 @@ __global__ __launch_bounds__(256) void w_s2d_tap_major_kernel(const float* __res
 using namespace pconv;
 
 namespace {
-template <int NT, int MT>
-void launch_c8x3(bool of32, bool poolp, bool lrt, dim3 grid, hipStream_t st, const PConvArgs& a) {
-    const dim3 block(kThreads);
-    if constexpr (NT == 2 && MT == 1) {        // (LRT: two accumulator sets -- 32 images per wave; 64 would spill)
-        if (lrt) {
-            if (of32) hipLaunchKernelGGL((pconv_c8x3_kernel<NT, MT, true, false, true>), grid, block, 0, st, a);
-            else      hipLaunchKernelGGL((pconv_c8x3_kernel<NT, MT, false, false, true>), grid, block, 0, st, a);
-            return;
-        }
-    }
-    if (poolp)     hipLaunchKernelGGL((pconv_c8x3_kernel<NT, MT, false, true>), grid, block, 0, st, a);
-    else if (of32) hipLaunchKernelGGL((pconv_c8x3_kernel<NT, MT, true, false>), grid, block, 0, st, a);
-    else           hipLaunchKernelGGL((pconv_c8x3_kernel<NT, MT, false, false>), grid, block, 0, st, a);
-}
-}  // namespace
-
-namespace {
 struct LrtNoise { const float* w_var; const float* b_var; uint64_t seed; uint32_t call0, stream_id; int sample; const uint32_t* call_dev; };
 
+// What to launch: pconv_c8x3_plan.h decides (the checks, the zero-border window, the slab limits, the tile rule and the form);
+// this function checks the pointers, fills the argument block and starts the instantiation the plan names.
 int c8x3_launch(const bbb_conv_desc_t* d, const void* x, const float* w, const float* bias, void* y, uint32_t flags, const LrtNoise* lrt,
                 void* stream) {
-    constexpr uint32_t kKnown = BBB_C8X3_OUT_F32 | BBB_C8X3_TILE128 | BBB_C8X3_TILE256 | BBB_C8X3_POOL | BBB_C8X3_NT_MASK | BBB_C8X3_ZERO_MASK;
-    if (d == nullptr || x == nullptr || w == nullptr || y == nullptr || (flags & ~kKnown) != 0 ||
-        ((flags & BBB_C8X3_TILE128) && (flags & BBB_C8X3_TILE256)))
-        return BBB_EINVAL;
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride_h <= 0 ||
-        d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 || d->draws <= 0 || d->act < 0 || d->act > 2 ||
-        d->pool != 0 || d->w_row_pitch != 0 || d->w_tap_major != 0)
-        return BBB_EINVAL;
-    const bool of32 = (flags & BBB_C8X3_OUT_F32) != 0;
-    const bool poolp = (flags & BBB_C8X3_POOL) != 0;
-    const int nt_force = (int)((flags & BBB_C8X3_NT_MASK) >> BBB_C8X3_NT_SHIFT);
-    if (nt_force == 1 || nt_force > 4 || (poolp && of32)) return BBB_EINVAL;
-    if (lrt != nullptr) {
-        // LRT: one (mu, sigma^2) weight pair for every slab; 64-channel tiles; pooling is a launch of its own (bbb_maxpool_c8s3_sq)
-        if (lrt->w_var == nullptr || poolp || (nt_force != 0 && nt_force != 2) || d->w_draw_stride != 0 || d->b_draw_stride != 0 ||
-            ((bias == nullptr) != (lrt->b_var == nullptr)))
-            return BBB_EINVAL;
-        if ((((uintptr_t)lrt->w_var) & 15u) != 0 || (((uintptr_t)lrt->b_var) & (of32 ? 3u : 15u)) != 0) return BBB_EALIGN;
-    }
-    const int sets = lrt != nullptr ? 2 : 1;
-    if (d->cin % 16 != 0 || d->batch % 4 != 0 || (!of32 && d->cout % 8 != 0)) return BBB_ESHAPE;
-    const int ho = (d->h + 2 * d->pad_h - d->dil_h * (d->kh - 1) - 1) / d->stride_h + 1;
-    const int wo = (d->w + 2 * d->pad_w - d->dil_w * (d->kw - 1) - 1) / d->stride_w + 1;
-    if (ho <= 0 || wo <= 0) return BBB_ESHAPE;
-    // the pooled form: no padding (the four pixels of a window walk the same taps), even output height and width
-    if (poolp && (d->pad_h != 0 || d->pad_w != 0 || ho % 2 != 0 || wo % 2 != 0)) return BBB_ESHAPE;
-    if ((((uintptr_t)x | (uintptr_t)y) & 15u) != 0 || (((uintptr_t)w) & 15u) != 0 || (((uintptr_t)bias) & (of32 ? 3u : 15u)) != 0) return BBB_EALIGN;
+    if (x == nullptr || w == nullptr || y == nullptr) return BBB_EINVAL;
+    if (lrt != nullptr && (lrt->w_var == nullptr || ((bias == nullptr) != (lrt->b_var == nullptr)))) return BBB_EINVAL;
+    c8x3_plan::Flags f;
+    if (const int rc = c8x3_plan::decode(d, flags, lrt != nullptr, &f)) return rc;
+    if (lrt != nullptr && ((((uintptr_t)lrt->w_var) & 15u) != 0 || (((uintptr_t)lrt->b_var) & (f.of32 ? 3u : 15u)) != 0)) return BBB_EALIGN;
+    const bool aligned = (((uintptr_t)x | (uintptr_t)y) & 15u) == 0 && (((uintptr_t)w) & 15u) == 0 && (((uintptr_t)bias) & (f.of32 ? 3u : 15u)) == 0;
+    c8x3_plan::Plan pl;
+    if (const int rc = c8x3_plan::plan(d, f, aligned ? 0 : BBB_EALIGN, &pl)) return rc;
     PConvArgs a = {};
     a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
     a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = ho; a.Wo = wo; a.K = d->cin * d->kh * d->kw; a.Kp = a.K; a.khkw = d->kh * d->kw; a.act = d->act;
-    a.pool = poolp ? 1 : 0;
-    {   // rows / columns of the input the caller declares all-zero (BBB_C8X3_ZERO_* nibbles of flags)
-        const int lh = (int)((flags >> 8) & 15u), lw = (int)((flags >> 12) & 15u), th = (int)((flags >> 16) & 15u), tw = (int)((flags >> 20) & 15u);
-        if (lh + th >= a.H || lw + tw >= a.W) return BBB_EINVAL;
-        a.vh0 = lh; a.vh1 = a.H - th; a.vw0 = lw; a.vw1 = a.W - tw;
-    }
-    a.x_ps = (int64_t)a.Cin * a.H * a.W * a.B;
-    a.y_ps = (int64_t)a.Cout * ho * wo * a.B / (poolp ? 4 : 1);
-    // slabs are addressed through 32-bit buffer offsets (three -- LRT: six -- planes of 2-byte elements, or fp32 outputs)
-    if (6 * sets * a.x_ps >= 0x3FFF0000LL || 6 * sets * a.y_ps >= 0x3FFF0000LL || ((int64_t)a.Cout + 128) * a.K * 4 >= 0x3FFF0000LL) return BBB_ESHAPE;
-    if (d->x_draw_stride != 0 && d->x_draw_stride < 3 * sets * a.x_ps) return BBB_EINVAL;
-    if (d->w_draw_stride % 4 != 0 || (!of32 && d->b_draw_stride % 4 != 0) || d->x_draw_stride % 8 != 0) return BBB_EALIGN;
-    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride;
-    a.y_ds = of32 ? a.y_ps : 3 * sets * a.y_ps;
-    if (d->unit_div < 0 || d->unit_off < 0 || d->x_unit_mod < 0) return BBB_EINVAL;
-    if (d->unit_div > 1 && d->unit_off >= d->unit_div) return BBB_EINVAL;
-    if (d->x_unit_mod > 0 && d->x_unit_mod != d->unit_div) return BBB_EINVAL;
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && (d->unit_div > 1 || d->x_unit_off >= d->x_unit_div)) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
+    a.Ho = pl.ho; a.Wo = pl.wo; a.K = pl.K; a.Kp = a.K; a.khkw = d->kh * d->kw; a.act = d->act;
+    a.pool = f.pool ? 1 : 0;
+    a.vh0 = pl.vh0; a.vh1 = pl.vh1; a.vw0 = pl.vw0; a.vw1 = pl.vw1;
+    a.x_ps = pl.x_ps; a.y_ps = pl.y_ps;
+    a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride; a.y_ds = pl.y_ds;
     a.unit_div = d->unit_div; a.unit_off = d->unit_div > 1 ? d->unit_off : 0; a.x_mod = d->x_unit_mod;
     a.x_div = d->x_unit_div; a.x_off = d->x_unit_off;
     a.x = static_cast<const float*>(x); a.w = w; a.bias = bias; a.y = static_cast<float*>(y);
@@ -695,48 +646,52 @@ int c8x3_launch(const bbb_conv_desc_t* d, const void* x, const float* w, const f
         a.k0 = (uint32_t)lrt->seed; a.k1 = (uint32_t)(lrt->seed >> 32); a.call0 = lrt->call0; a.stream_id = lrt->stream_id;
         a.sample = lrt->sample ? 1 : 0; a.call_dev = lrt->call_dev; a.b_off = d->b_offset;
     }
-    const int64_t pixels = (int64_t)ho * wo / (poolp ? 4 : 1);
-    // Tile shape (the MFMA sequence per output element, hence every output bit, does not depend on it).  Channels per workgroup
-    // 32 * NT: NT = 2 unless forced -- wider tiles halve the image fragments' trips through the vector memory path per matrix
-    // instruction but hold 96 / 128 accumulation registers (two waves per SIMD instead of three), and measured slower on every
-    // AlexNet layer but conv3 (profiles/r06_notes.md: conv2 504 / 515 / 603 us for NT = 2 / 3 / 4 at 40 slabs).  Images per wave
-    // 32 * MT: 64, or 32 when the launch would otherwise leave the chip less than ~two rounds of workgroups.
-    int nt = 2, mt = 2;
-    {
-        static const int env_nt = [] { const char* s = getenv("BBB_C8X3_NT"); return s ? atoi(s) : 0; }();   // (experiments)
-        if (nt_force) nt = nt_force;
-        else if (env_nt >= 2 && env_nt <= 4) nt = env_nt;
-        const int64_t bm2 = (poolp ? 32 : 128) * 2;
-        const int64_t items2 = (int64_t)d->draws * ((a.Cout + 32 * nt - 1) / (32 * nt)) * pixels * ((a.B + bm2 - 1) / bm2);
-        if (flags & BBB_C8X3_TILE128) mt = 1;
-        else if (flags & BBB_C8X3_TILE256) mt = 2;
-        else if (a.B <= bm2 / 2 || items2 < 1024) mt = 1;
-        if (lrt != nullptr) mt = 1;                                  // two accumulator sets: 32 images per wave
-    }
-    const int bnw = 32 * nt, bm = (poolp ? 32 : 128) * mt;
-    a.Ntiles = (a.Cout + bnw - 1) / bnw;
-    a.G = a.Ntiles * d->draws;
-    a.nbt = (a.B + bm - 1) / bm;
-    const int64_t mtiles = pixels * a.nbt;
-    if (mtiles > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mtiles;
-    const int64_t per = ((int64_t)a.G * mtiles + 7) / 8;
-    if (8 * per > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
-    const dim3 grid((unsigned)(8 * per));
+    a.Ntiles = pl.Ntiles; a.G = pl.G; a.nbt = pl.nbt; a.Mtiles = pl.Mtiles; a.per_xcd = pl.per_xcd;
+    const dim3 grid((unsigned)pl.blocks), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
-    const bool is_lrt = lrt != nullptr;
-    switch (nt * 10 + mt) {
-        case 21: launch_c8x3<2, 1>(of32, poolp, is_lrt, grid, st, a); break;
-        case 22: launch_c8x3<2, 2>(of32, poolp, is_lrt, grid, st, a); break;
-        case 31: launch_c8x3<3, 1>(of32, poolp, false, grid, st, a); break;
-        case 32: launch_c8x3<3, 2>(of32, poolp, false, grid, st, a); break;
-        case 41: launch_c8x3<4, 1>(of32, poolp, false, grid, st, a); break;
-        default: launch_c8x3<4, 2>(of32, poolp, false, grid, st, a); break;
+    // pconv_c8x3_kernel<NT, MT, OF32, POOLP, LRT>, one case per BBB_C8X3_FORM_*
+#define C8X3_FORM(form, ...) case form: hipLaunchKernelGGL((pconv_c8x3_kernel<__VA_ARGS__>), grid, block, 0, st, a); break
+    switch (pl.form) {
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT1_S3, 2, 1, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT1_F32, 2, 1, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT1_POOL, 2, 1, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT2_S3, 2, 2, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT2_F32, 2, 2, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT2_MT2_POOL, 2, 2, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT1_S3, 3, 1, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT1_F32, 3, 1, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT1_POOL, 3, 1, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT2_S3, 3, 2, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT2_F32, 3, 2, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT3_MT2_POOL, 3, 2, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT1_S3, 4, 1, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT1_F32, 4, 1, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT1_POOL, 4, 1, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT2_S3, 4, 2, false, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT2_F32, 4, 2, true, false);
+        C8X3_FORM(BBB_C8X3_FORM_NT4_MT2_POOL, 4, 2, false, true);
+        C8X3_FORM(BBB_C8X3_FORM_LRT_S3, 2, 1, false, false, true);      // (LRT: two accumulator sets -- 32 images per wave; 64 would spill)
+        C8X3_FORM(BBB_C8X3_FORM_LRT_F32, 2, 1, true, false, true);
+        default: return BBB_EINVAL;
     }
+#undef C8X3_FORM
     return (int)hipGetLastError();
 }
 }  // namespace
+
+extern "C" int bbb_conv2d_c8x3_plan(const bbb_conv_desc_t* d, uint32_t flags, int lrt, int32_t* form, int32_t* nt, int32_t* images_per_wg,
+                                    int64_t* items, int64_t* blocks) {
+    c8x3_plan::Flags f;
+    c8x3_plan::Plan pl;
+    if (const int rc = c8x3_plan::decode(d, flags, lrt != 0, &f)) return rc;
+    if (const int rc = c8x3_plan::plan(d, f, 0, &pl)) return rc;
+    if (form) *form = pl.form;
+    if (nt) *nt = pl.nt;
+    if (images_per_wg) *images_per_wg = pl.images_per_wg;
+    if (items) *items = pl.items;
+    if (blocks) *blocks = pl.blocks;
+    return 0;
+}
 
 extern "C" int bbb_conv2d_c8x3_fwd(const bbb_conv_desc_t* d, const void* x, const float* w, const float* bias, void* y, uint32_t flags,
                                    void* stream) {

@@ -344,20 +344,14 @@ extern "C" int bbb_conv2d_chwn_bf16x3_fwd(const bbb_conv_desc_t* d, const void* 
     a.y_ps = (int64_t)a.Cout * a.Ho * a.Wo * a.B;
     if (ys3) a.y_ds = 3 * a.y_ps;
     if (xs3 && (d->x_draw_stride != 0 && d->x_draw_stride < 3 * a.x_ps)) return BBB_EINVAL;
-    a.Ntiles = (a.Cout + BN - 1) / BN;
-    a.G = a.Ntiles * d->draws;
-    const int64_t pixels = (int64_t)a.Ho * a.Wo;
     // 128 images per workgroup (measured: the 256-image form -- 2 workgroups per CU, half the workgroups -- is slower on four of
-    // the six launches of the metric step, profiles/r04_notes.md)
+    // the six launches of the metric step, profiles/r04_notes.md); the grid is the fp32 forward's (pconv_plan.h)
     constexpr int kMT = 1;
-    a.nbt = (a.B + 128 * kMT - 1) / (128 * kMT);
-    const int64_t mtiles = pixels * a.nbt;
-    if (mtiles > 0x7fffffffLL) return BBB_ESHAPE;
-    a.Mtiles = (int)mtiles;
-    const int64_t per = ((int64_t)a.G * mtiles + 7) / 8;
-    if (8 * per > 0x7fffffffLL) return BBB_ESHAPE;
-    a.per_xcd = (int32_t)per;
-    const dim3 grid((unsigned)(8 * per)), block(kThreads);
+    pconv_plan::Plan pl = {};
+    if (const int rc = pconv_plan::channel_groups(a.Cout, d->draws, &pl)) return rc;
+    if (const int rc = pconv_plan::item_grid(a.B, (int64_t)a.Ho * a.Wo, 128 * kMT, &pl)) return rc;
+    a.Ntiles = pl.Ntiles; a.G = pl.G; a.nbt = pl.nbt; a.Mtiles = pl.Mtiles; a.per_xcd = pl.per_xcd;
+    const dim3 grid((unsigned)pl.blocks), block(kThreads);
     hipStream_t st = (hipStream_t)stream;
     if (xs3 && ys3)      hipLaunchKernelGGL((pconv_bf16x3_kernel<kMT, true, true>), grid, block, 0, st, a);
     else if (xs3)        hipLaunchKernelGGL((pconv_bf16x3_kernel<kMT, true, false>), grid, block, 0, st, a);

@@ -1,14 +1,17 @@
 // Host-side launch plan of the batch-innermost fp32 implicit GEMM (csrc/pconv_gemm.hip, csrc/pconv_body.cuh): the descriptor
 // checks, the layer's split of its contraction, and which of the fifteen launch forms a launch takes -- tile width, staging
-// interleaved or not, the split across workgroups or inside one, the pooled forms -- with its item count and grid.  Plain C++17,
-// no HIP headers: launch<LRT>() takes its kernel and grid from here, bbb_conv2d_chwn_plan reports them, and
-// tests/host/pconv_plan_check.cpp walks this file under the sanitizers.
+// interleaved or not, the split across workgroups or inside one, the pooled forms -- with its item count and grid; the same tile
+// rule applied to the transposed launch (dgrad_plan: csrc/pconv_dgrad.hip) and to the grid of bbb_conv2d_chwn_bf16x3_fwd.  What
+// every family checks on a descriptor comes from conv_desc_check.h.  Plain C++17, no HIP headers: launch<LRT>() takes its kernel
+// and grid from here, bbb_conv2d_chwn_plan / bbb_conv2d_chwn_dgrad_plan report them, and tests/host/pconv_plan_check.cpp walks
+// this file under the sanitizers.
 #ifndef BBB_PCONV_PLAN_H
 #define BBB_PCONV_PLAN_H
 
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "conv_desc_check.h"
 
 // launches of more 64-image items than this run the in-workgroup form of a layer's split (measured, profiles/r03_notes.md
 // section 2 and r04_notes.md: above ~400 items the cross-workgroup form only adds partial-tile traffic; LRT items carry two
@@ -21,6 +24,9 @@
 #endif
 
 namespace pconv_plan {
+
+using conv_desc_check::mul_cap;
+using conv_desc_check::xcd_grid;
 
 constexpr int kBN = 64;                           // output channels per item (pconv::BN)
 constexpr int kBK = 32;                           // contraction elements per k tile (pconv::BK)
@@ -68,55 +74,36 @@ struct Plan {
     int64_t blocks;     // workgroups of the launch
 };
 
-// The descriptor checks of every batch-innermost fp32 entry, in the order the entries have always made them.
+// The limits of 32-bit buffer offsets into one draw's slabs, for a launch that writes an ho x wo map; -> PConvArgs::x_inv
+inline int slab_limits(const bbb_conv_desc_t* d, int32_t ho, int32_t wo, uint32_t* x_inv) {
+    if (mul_cap(d->cin, d->h, d->w) > 0x7fffffffLL || mul_cap(d->cin, d->kh, d->kw) > 0x7fffffffLL) return BBB_ESHAPE;
+    // per-draw slabs are addressed through 32-bit buffer offsets
+    const int64_t x_bytes = mul_cap(d->cin, d->h, d->w, (int64_t)d->batch * 4);
+    if (x_bytes > 0xFFFE0000LL || mul_cap(d->cout, ho, wo, (int64_t)d->batch * 4) > 0xFFFE0000LL ||
+        mul_cap((int64_t)d->cout + 64, d->cin, d->kh, (int64_t)d->kw * 4) > 0x3FFFFFFFLL || (int64_t)d->batch * 4 > 0x0FFFFFFFLL)
+        return BBB_ESHAPE;
+    *x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 4u) & ~15u;   /* a ragged last tile reaches < 512 columns past the row */
+    return x_bytes > (int64_t)*x_inv ? BBB_ESHAPE : 0;
+}
+
+// The descriptor checks of every batch-innermost fp32 forward entry, in the order the entries have always made them.
 inline int describe(const bbb_conv_desc_t* d, Geom* g) {
     if (d == nullptr) return BBB_EINVAL;
     *g = Geom{};
-    if (d->batch <= 0 || d->cin <= 0 || d->h <= 0 || d->w <= 0 || d->cout <= 0 || d->kh <= 0 || d->kw <= 0 ||
-        d->stride_h <= 0 || d->stride_w <= 0 || d->pad_h < 0 || d->pad_w < 0 || d->dil_h <= 0 || d->dil_w <= 0 ||
-        d->draws <= 0 || d->act < 0 || d->act > 2)
-        return BBB_EINVAL;
+    if (!conv_desc_check::positive_geometry(d) || d->act < 0 || d->act > 2) return BBB_EINVAL;
     if (d->batch % 4 != 0) return BBB_ESHAPE;        // batch-innermost rows are moved as 16-byte vectors
-    // (64-bit: h + 2 pad and dil * (k - 1) of a hostile descriptor leave the int range.)  A kernel that reaches past the padded image
-    // is refused: C's division rounds a negative numerator towards zero, which for a stride above 1 would name one output row.
-    const int64_t nh = (int64_t)d->h + 2 * (int64_t)d->pad_h - (int64_t)d->dil_h * (d->kh - 1) - 1;
-    const int64_t nw = (int64_t)d->w + 2 * (int64_t)d->pad_w - (int64_t)d->dil_w * (d->kw - 1) - 1;
-    if (nh < 0 || nw < 0) return BBB_ESHAPE;
-    const int64_t ho64 = nh / d->stride_h + 1, wo64 = nw / d->stride_w + 1;
-    if (ho64 > 0x7fffffffLL || wo64 > 0x7fffffffLL) return BBB_ESHAPE;
-    const int ho = (int)ho64, wo = (int)wo64;
-    // products of up to four 31-bit factors: multiply step by step, refusing as soon as a partial product leaves 2^32 bytes
-    auto over = [](int64_t a, int64_t b, int64_t c, int64_t e, int64_t lim) {
-        const int64_t f[3] = {b, c, e};
-        int64_t v = a;
-        if (v > lim) return true;
-        for (int i = 0; i < 3; ++i) {
-            if (v > lim / f[i]) return true;
-            v *= f[i];
-        }
-        return false;
-    };
-    if (over(d->cin, d->h, d->w, 1, 0x7fffffffLL) || over(d->cin, d->kh, d->kw, 1, 0x7fffffffLL)) return BBB_ESHAPE;
-    // per-draw slabs are addressed through 32-bit buffer offsets
-    if (over(d->cin, d->h, d->w, (int64_t)d->batch * 4, 0xFFFE0000LL) || over(d->cout, ho, wo, (int64_t)d->batch * 4, 0xFFFE0000LL) ||
-        over((int64_t)d->cout + 64, d->cin, d->kh, (int64_t)d->kw * 4, 0x3FFFFFFFLL) || (int64_t)d->batch * 4 > 0x0FFFFFFFLL)
-        return BBB_ESHAPE;
-    g->x_inv = (0xFFFFFFF0u - ((uint32_t)d->batch + 512u) * 4u) & ~15u;   /* a ragged last tile reaches < 512 columns past the row */
-    if ((int64_t)d->cin * d->h * d->w * d->batch * 4 > (int64_t)g->x_inv) return BBB_ESHAPE;
+    int32_t ho = 0, wo = 0;
+    if (const int rc = conv_desc_check::out_map(d, &ho, &wo)) return rc;
+    if (const int rc = slab_limits(d, ho, wo, &g->x_inv)) return rc;
     g->B = d->batch; g->Cin = d->cin; g->H = d->h; g->W = d->w; g->Cout = d->cout; g->kh = d->kh; g->kw = d->kw;
     g->sh = d->stride_h; g->sw = d->stride_w; g->ph = d->pad_h; g->pw = d->pad_w; g->dh = d->dil_h; g->dw = d->dil_w;
     g->Ho = ho; g->Wo = wo; g->K = d->cin * d->kh * d->kw; g->khkw = d->kh * d->kw; g->act = d->act;
     if (d->w_row_pitch < 0 || (d->w_row_pitch > 0 && d->w_row_pitch < g->K)) return BBB_EINVAL;
     g->Kp = d->w_row_pitch > 0 ? d->w_row_pitch : g->K;
-    if (over((int64_t)d->cout + 64, g->Kp, 4, 1, 0x3FFFFFFFLL)) return BBB_ESHAPE;
+    if (mul_cap((int64_t)d->cout + 64, g->Kp, 4) > 0x3FFFFFFFLL) return BBB_ESHAPE;
     g->x_ds = d->x_draw_stride; g->w_ds = d->w_draw_stride; g->b_ds = d->b_draw_stride;
     g->y_ds = (int64_t)d->cout * ho * wo * d->batch;
-    if (d->unit_div < 0 || d->unit_off < 0 || d->x_unit_mod < 0 || d->b_offset < 0) return BBB_EINVAL;
-    if (d->unit_div > 1 && d->unit_off >= d->unit_div) return BBB_EINVAL;          // passed reduced modulo S
-    if (d->x_unit_mod > 0 && d->x_unit_mod != d->unit_div) return BBB_EINVAL;
-    if (d->x_unit_div < 0 || d->x_unit_off < 0 || (d->x_unit_div > 1 && (d->unit_div > 1 || d->x_unit_off >= d->x_unit_div)) ||
-        (d->x_unit_div <= 1 && d->x_unit_off != 0))
-        return BBB_EINVAL;
+    if (d->b_offset < 0 || conv_desc_check::unit_fields(d, conv_desc_check::kUnitsAndSteps) != 0) return BBB_EINVAL;
     g->unit_div = d->unit_div; g->unit_off = d->unit_div > 1 ? d->unit_off : 0; g->x_mod = d->x_unit_mod; g->b_off = d->b_offset;
     g->x_div = d->x_unit_div; g->x_off = d->x_unit_off;
     if (d->pool != 0 && d->pool != 1) return BBB_EINVAL;
@@ -163,6 +150,44 @@ inline int64_t split_scratch_bytes(const Geom& a, int draws, bool lrt, int s) {
     return kTicketBytes + items * s * (lrt ? 2 : 1) * 64 * 64 * 4;
 }
 
+// ---- the pieces the forward's plain branch, the transposed launch (dgrad_plan) and bbb_conv2d_chwn_bf16x3_fwd share ----
+// channel tiles and (draw, channel tile) groups
+inline int channel_groups(int cout, int draws, Plan* p) {
+    p->Ntiles = (cout + kBN - 1) / kBN;
+    const int64_t G = (int64_t)p->Ntiles * draws;
+    if (G > 0x7fffffffLL) return BBB_ESHAPE;
+    p->G = (int32_t)G;
+    return 0;
+}
+
+// tile choice: 128 images per workgroup (two accumulator chains per wave) unless that leaves fewer than 3
+// workgroups per CU, then 64.  A 256-image tile (64x64 per wave) exists but measured 5-10 % slower on every
+// AlexNet layer (3 instead of 4 workgroups per CU); the launcher never selects it.
+// LRT stages two weight tiles and keeps two accumulator sets: 64-wide only.
+inline int image_tile(int B, int64_t pixels, int64_t G, bool lrt) {
+    // (the slab limits hold Ho * Wo * B below 2^30 and G is below 2^31: the item counts stay inside 64 bits)
+    const int64_t nb128 = pixels * ((B + 127) / 128) * G;
+    if (lrt || nb128 < 768) return 64;               // (round 3 re-measured 600 / 300: conv4 +10 %, conv5 +25 % slower with 128)
+    // an image axis that 128-wide tiles would pad by >= 25 % and 64-wide ones by less (192 = the input channels of conv3's
+    // role-swapped weight gradient: 256 against 192): 64.  Same sums per element either way.
+    const int64_t pad128 = ((int64_t)B + 127) / 128 * 128, pad64 = ((int64_t)B + 63) / 64 * 64;
+    return (pad128 * 4 >= (int64_t)B * 5 && pad64 < pad128) ? 64 : 128;
+}
+
+// nbt, Mtiles, items, the grid and the interleave choice of a launch of bm-image items (p->G set by channel_groups)
+inline int item_grid(int B, int64_t pixels, int bm, Plan* p) {
+    p->bm = bm;
+    p->nbt = (B + bm - 1) / bm;
+    const int64_t mt = pixels * p->nbt;
+    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
+    p->Mtiles = (int32_t)mt;
+    p->items = (int64_t)p->G * mt;
+    // staging loads interleaved with the MFMAs (ILV): round 1 measured it a loss beyond ~1.5 rounds of workgroups; re-measured in
+    // round 3 on the current kernel (profiles/r03_notes.md section 3) it is a 1-2 % gain up to ~12k items, one or three steps in flight
+    p->ilv = p->items <= PCONV_ILV_MAX;
+    return xcd_grid(p->items, &p->per_xcd, &p->blocks);
+}
+
 // The form of one launch.  k_split: what the caller passed (<= 1: no split; otherwise it must be the layer's plan);
 // has_scratch: the caller gave scratch for the cross-workgroup form (it is used only when split_scratch_bytes() is not 0).
 inline int plan(const Geom& a, int draws, bool lrt, int k_split, bool has_scratch, Plan* p) {
@@ -173,15 +198,9 @@ inline int plan(const Geom& a, int draws, bool lrt, int k_split, bool has_scratc
         ksplit = k_split;
     }
     const bool part = ksplit > 1 && has_scratch && split_scratch_bytes(a, draws, lrt, ksplit) > 0;
-    p->Ntiles = (a.Cout + kBN - 1) / kBN;
-    const int64_t G = (int64_t)p->Ntiles * draws;
-    if (G > 0x7fffffffLL) return BBB_ESHAPE;
-    p->G = (int32_t)G;
+    if (const int rc = channel_groups(a.Cout, draws, p)) return rc;
+    const int64_t G = p->G;
     const int64_t pixels = (int64_t)a.Ho * a.Wo;
-    // tile choice: 128 images per workgroup (two accumulator chains per wave) unless that leaves fewer than 3
-    // workgroups per CU, then 64.  A 256-image tile (64x64 per wave) exists but measured 5-10 % slower on every
-    // AlexNet layer (3 instead of 4 workgroups per CU); the launcher never selects it.
-    // LRT stages two weight tiles and keeps two accumulator sets: 64-wide only.
     if (a.pool) {
         // one item per POOLED pixel, 128-image tiles (LRT: 64) (the callers fuse large launches only)
         if (ksplit > 1) return BBB_EINVAL;
@@ -191,53 +210,27 @@ inline int plan(const Geom& a, int draws, bool lrt, int k_split, bool has_scratc
         const int64_t itp = G * mtp;
         if (mtp > 0x7fffffffLL || itp > 0x7fffffffLL - 8) return BBB_ESHAPE;
         p->Mtiles = (int32_t)mtp;
-        const int64_t perp = (itp + 7) / 8;
-        p->per_xcd = (int32_t)perp;
         // staging loads up front (ILV = false): with the running maximum in 32 more accumulation registers this form fits four
         // workgroups per CU (60 + 64 registers) and the interleaved one does not (82 + 64: three; measured 492-494 us against 480-482
         // for conv1 of the metric step, profiles/r04_notes.md section 7)
         p->ilv = 0;
         p->form = lrt ? kLrtPool : kBbbPool;
         p->items = itp;
-        p->blocks = 8 * perp;
-        return 0;
+        return xcd_grid(itp, &p->per_xcd, &p->blocks);
     }
-    // (describe() holds Ho * Wo * B below 2^30 and G is below 2^31: the item counts below stay inside 64 bits)
-    const int64_t nb128 = pixels * ((a.B + 127) / 128) * G;
-    int bm = (lrt || nb128 < 768) ? 64 : 128;        // (round 3 re-measured 600 / 300: conv4 +10 %, conv5 +25 % slower with 128)
-    // an image axis that 128-wide tiles would pad by >= 25 % and 64-wide ones by less (192 = the input channels of conv3's
-    // role-swapped weight gradient: 256 against 192): 64.  Same sums per element either way.
-    const int64_t pad128 = ((int64_t)a.B + 127) / 128 * 128, pad64 = ((int64_t)a.B + 63) / 64 * 64;
-    if (bm == 128 && pad128 * 4 >= (int64_t)a.B * 5 && pad64 < pad128) bm = 64;
     const int64_t items64 = pixels * ((a.B + 63) / 64) * G;
     const bool cross = part && items64 <= split_max_items(lrt);
-    if (cross) bm = 64;
-    p->bm = bm;
-    p->nbt = (a.B + bm - 1) / bm;
-    const int64_t mt = pixels * p->nbt;
-    if (mt > 0x7fffffffLL) return BBB_ESHAPE;
-    p->Mtiles = (int32_t)mt;
-    const int64_t items = G * mt;
+    const int bm = cross ? 64 : image_tile(a.B, pixels, G, lrt);
+    if (const int rc = item_grid(a.B, pixels, bm, p)) return rc;
+    const int64_t items = p->items;
     if (cross) {
         // the layer's split contraction ACROSS workgroups: a launch this small cannot fill the chip otherwise
         if (items * ksplit > 0x7fffffffLL) return BBB_EINVAL;
-        const int64_t perb = (items * ksplit + 7) / 8;
-        p->per_xcd = (int32_t)perb;
         p->ilv = 1;
         p->form = lrt ? kLrtCross : kBbbCross;
-        p->items = items;
-        p->blocks = 8 * perb;
-        return 0;
+        return xcd_grid(items * ksplit, &p->per_xcd, &p->blocks);
     }
-    const int64_t per = (items + 7) / 8;
-    const int64_t blocks = 8 * per;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    p->per_xcd = (int32_t)per;
-    p->items = items;
-    p->blocks = blocks;
-    // staging loads interleaved with the MFMAs (ILV): round 1 measured it a loss beyond ~1.5 rounds of workgroups; re-measured in
-    // round 3 on the current kernel (profiles/r03_notes.md section 3) it is a 1-2 % gain up to ~12k items, one or three steps in flight
-    const bool ilv = items <= PCONV_ILV_MAX;
+    const bool ilv = p->ilv != 0;
     if (ksplit > 1) {
         // the same summation order inside ONE workgroup per item (pconv_body.cuh, SEQ): no scratch, no extra traffic
         if (!lrt && bm == 128) {
@@ -257,6 +250,37 @@ inline int plan(const Geom& a, int draws, bool lrt, int k_split, bool has_scratc
     else if (bm == 128) p->form = ilv ? kBbb128Ilv : kBbb128;
     else p->form = ilv ? kBbb64Ilv : kBbb64;
     return 0;
+}
+
+// ---- bbb_conv2d_chwn_dgrad: the transposed launch (csrc/pconv_dgrad.hip) ----
+// d describes the stride-1 launch on the flipped weights (its h x w is g's map); the layer's stride travels as the upsampling
+// factors and out_h x out_w is dx's map.  The entry's checks in the order it has always made them, then the forward's own tile
+// rule: image_tile() and item_grid() of the plain form, never LRT, never a split contraction (p->form stays 0: the entry picks
+// pconv_dgrad_kernel<bm, ilv>).  ptr_rc: what the entry's operand-pointer checks found (0 | BBB_EINVAL | BBB_EALIGN), returned at
+// their place in the order.
+inline int dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, int out_w, int ptr_rc, uint32_t* x_inv, Plan* p) {
+    *p = Plan{};
+    if (d == nullptr) return BBB_EINVAL;
+    if (!conv_desc_check::positive_geometry(d) || up_h <= 0 || up_w <= 0 || out_h <= 0 || out_w <= 0) return BBB_EINVAL;
+    if (d->stride_h != 1 || d->stride_w != 1) return BBB_EINVAL;
+    if (up_h == 1 && up_w == 1) return BBB_EINVAL;          // a stride-1 layer's gradient is bbb_conv2d_chwn_fwd: one way to compute it
+    if (d->act != 0 || d->pool != 0 || d->w_tap_major != 0 || d->w_row_pitch != 0 ||
+        conv_desc_check::unit_fields(d, conv_desc_check::kNothing) != 0)
+        return BBB_EINVAL;
+    if (d->x_draw_stride < 0 || d->w_draw_stride < 0) return BBB_EINVAL;
+    if (d->batch % 4 != 0) return BBB_ESHAPE;
+    // (out_h, out_w) must be a map whose forward (padding p = d (k - 1) - q >= 0, stride up) gives exactly the g map of d
+    const int64_t fph = (int64_t)d->dil_h * (d->kh - 1) - d->pad_h, fpw = (int64_t)d->dil_w * (d->kw - 1) - d->pad_w;
+    if (fph < 0 || fpw < 0) return BBB_ESHAPE;
+    int32_t gh = 0, gw = 0;
+    if (conv_desc_check::out_axis(out_h, fph, d->dil_h, d->kh, up_h, &gh) != 0 ||
+        conv_desc_check::out_axis(out_w, fpw, d->dil_w, d->kw, up_w, &gw) != 0 || gh != d->h || gw != d->w)
+        return BBB_ESHAPE;
+    if (const int rc = slab_limits(d, out_h, out_w, x_inv)) return rc;
+    if (ptr_rc != 0) return ptr_rc;
+    if (const int rc = channel_groups(d->cout, d->draws, p)) return rc;
+    const int64_t pixels = (int64_t)out_h * out_w;
+    return item_grid(d->batch, pixels, image_tile(d->batch, pixels, p->G, false), p);
 }
 
 }  // namespace pconv_plan

@@ -1,6 +1,8 @@
 // Host-only walk of the bf16 launch plans (csrc/pconv_bf16_plan.h) for tests/test_bf16_plan_cpu.py, which builds this file with
 // -fsanitize=undefined: the three plans over a seeded sweep of ordinary geometries and over descriptors whose dimensions sit near
 // INT32_MAX / 2 (every product inside the plans must be guarded, not overflow).  Prints a checksum of everything the plans return.
+// `bf16_plan_check dump` prints one line per walk() instead -- whether the kernel reaches past the padded input, then each plan's
+// return code and fields -- so that two builds of this file against two versions of the header can be compared line by line.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -18,6 +20,8 @@ int pick(const int* v, int n) { return v[rnd() % (uint32_t)n]; }
 void mix(int64_t v) { sum = (sum ^ (uint64_t)v) * 0x100000001b3ull; }
 
 long counts[4];   // ok / EINVAL / EALIGN / ESHAPE over all plan calls
+bool dump = false;
+long walks = 0;
 
 void tally(int rc) {
     mix(rc);
@@ -28,6 +32,12 @@ void walk(const bbb_conv_desc_t& d, uint32_t flags, int up_h, int up_w, int out_
     bf16_plan::FwdPlan f;
     int rc = bf16_plan::fwd_plan(&d, flags, 0, &f);
     tally(rc);
+    if (dump) {
+        const bool reach = (int64_t)d.h + 2 * (int64_t)d.pad_h < (int64_t)d.dil_h * (d.kh - 1) + 1 ||
+                           (int64_t)d.w + 2 * (int64_t)d.pad_w < (int64_t)d.dil_w * (d.kw - 1) + 1;
+        printf("%ld reach %d fwd %d form %d shape %d kgs %d ws %d blocks %lld", walks++, reach, rc, rc ? -1 : f.form, rc ? 0 : f.tile.shape,
+               rc ? 0 : f.tile.kgs, rc ? 0 : (int)f.tile.ws, rc ? 0LL : (long long)f.blocks);
+    }
     if (rc == 0) {
         mix(f.form); mix(f.tile.shape); mix(f.tile.kgs); mix(f.tile.ws); mix(f.blocks); mix(f.smem_bytes); mix(f.y_ds); mix(f.nt); mix(f.ks);
         mix(f.f.Ntiles); mix(f.f.G); mix(f.f.nbt); mix(f.f.Mtiles); mix(f.f.per_xcd); mix(f.f.px_run); mix(f.f.pool); mix(f.f.y_c8);
@@ -36,6 +46,7 @@ void walk(const bbb_conv_desc_t& d, uint32_t flags, int up_h, int up_w, int out_
     bf16_plan::DgradPlan g;
     rc = bf16_plan::dgrad_plan(&d, up_h, up_w, out_h, out_w, flags & BBB_BF16_W_TAP_MAJOR, 0, &g);
     tally(rc);
+    if (dump) printf(" dgrad %d shape %d kgs %d ws %d blocks %lld", rc, rc ? 0 : g.tile.shape, rc ? 0 : g.tile.kgs, rc ? 0 : (int)g.tile.ws, rc ? 0LL : (long long)g.grid.blocks);
     if (rc == 0) {
         mix(g.tile.shape); mix(g.tile.kgs); mix(g.tile.ws); mix(g.tstep_h); mix(g.tstep_w); mix(g.grid.blocks); mix(g.grid.Mtiles);
         mix(g.grid.G); mix(g.grid.per_xcd);
@@ -43,6 +54,7 @@ void walk(const bbb_conv_desc_t& d, uint32_t flags, int up_h, int up_w, int out_
     bf16_plan::LrtPlan l;
     rc = bf16_plan::lrt_plan(&d, &l);
     tally(rc);
+    if (dump) printf(" lrt %d shape %d kgs %d ws %d\n", rc, rc ? 0 : l.tile.shape, rc ? 0 : l.tile.kgs, rc ? 0 : (int)l.tile.ws);
     if (rc == 0) {
         mix(l.tile.shape); mix(l.tile.kgs); mix(l.tile.ws);
         bf16_plan::Geom geom;
@@ -56,7 +68,8 @@ void walk(const bbb_conv_desc_t& d, uint32_t flags, int up_h, int up_w, int out_
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    dump = argc > 1 && argv[1][0] == 'd';
     static const int batches[] = {8, 16, 24, 64, 128, 136, 200, 256, 264, 512}, taps[] = {1, 3, 5, 11}, strides[] = {1, 1, 2, 4};
     static const int pools[] = {0, 0, 0, 1, (3 << 8) | 2, (2 << 8) | 2, (3 << 8) | 3};
     static const uint32_t flagset[] = {0, 1, 2, 3, 2 | 4, 2 | 4 | 8, 8, 4};
@@ -108,6 +121,7 @@ int main() {
         d.pool = i % 2 ? 1 : (3 << 8) | 2;
         walk(d, 0, 2, 2, 4, 4);
     }
+    if (dump) return 0;
     printf("cases %ld ok %ld einval %ld ealign %ld eshape %ld checksum %016llx\n", cases, counts[0], counts[1], counts[2], counts[3],
            (unsigned long long)sum);
     return 0;
