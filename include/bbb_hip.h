@@ -461,6 +461,49 @@ int bbb_lrt_pool_act_bwd_chwn(const float* g_out, const float* y, const float* a
                               int64_t out_plane_pitch, const float* g_out2, const float* x_out, int64_t x_planes, void* stream);
 
 /*
+ * Average pooling on batch-innermost planes (additive to ABI 13): nn.AvgPool2d(kernel_size, stride, padding, ceil_mode=False,
+ * count_include_pad, divisor_override=None) -- and nn.AdaptiveAvgPool2d on a map its output size divides, which is the window
+ * (h / oh, w / ow) at the same stride without padding -- for models built from the layers package beyond the three of the zoo
+ * (LeNet-style stacks, global-average-pool heads).  The output map is floor mode's, ho = (h + 2 pad_h - kh) / stride_h + 1.
+ */
+#define BBB_POOL_AVG 1        /* bbb_pool_desc_t::kind (0 is not a kind; 2 is kept for a maximum kind) */
+typedef struct bbb_pool_desc {
+    int32_t kind;              /* BBB_POOL_AVG */
+    int32_t h, w, batch;       /* the input map and the images per plane (batch % 4 == 0) */
+    int32_t kh, kw;            /* window */
+    int32_t stride_h, stride_w;
+    int32_t pad_h, pad_w;      /* zero padding, 2 * pad <= k on each axis (torch's rule: every window then holds a valid tap) */
+    int32_t count_include_pad; /* 1: the divisor is kh * kw; 0: the number of taps inside the map */
+} bbb_pool_desc_t;
+
+/* What the three launches below do for this descriptor (host only, needs no device): the output map and the workgroups (256
+ * threads, one per 16-byte group of 4 images) of the forward and of the backward, or the code all of them refuse it with BEFORE
+ * anything is launched: BBB_EINVAL for a null descriptor, an unknown kind, a non-positive size, a negative padding or a
+ * count_include_pad other than 0 / 1; BBB_ESHAPE for batch % 4 != 0, 2 * pad > k on an axis, a window larger than the padded map,
+ * or a grid that does not fit an int; BBB_EINVAL for an out_plane_pitch (the backward's, 0 = dense) that is below h * w * batch or
+ * not a multiple of 4.  Out-pointers may be NULL. */
+int bbb_avgpool_plan(const bbb_pool_desc_t* d, int64_t planes, int64_t out_plane_pitch, int32_t* ho, int32_t* wo, int64_t* fwd_blocks,
+                     int64_t* bwd_blocks);
+
+/* x [planes][h][w][B] -> y [planes][ho][wo][B]: the taps of a window that lie inside the map are added in scan order (rows, then
+ * columns) by plain fp32 adds, then divided ONCE (IEEE division) by the divisor.  The order depends on the window alone, so a
+ * plane computed alone or among others is the same bits.  x, y 16-byte aligned. */
+int bbb_avgpool_chwn(const bbb_pool_desc_t* d, const float* x, float* y, int64_t planes, void* stream);
+
+/* Training extension: bbb_pool_act_bwd_chwn with the average pool's routing.  y [planes][h][w][B] the layer's ACTIVATED output,
+ * g_out [planes][ho][wo][B]; g_pre(h, w) = act'(.) * sum of g_out(oh, ow) / divisor(oh, ow) over the windows that contain (h, w), in
+ * ascending (oh, ow) order; elements no window covers receive 0.  Gather form: no atomics, deterministic.  act, out_plane_pitch and
+ * the activation arithmetic as there. */
+int bbb_avgpool_act_bwd_chwn(const bbb_pool_desc_t* d, const float* g_out, const float* y, float* g_pre, int64_t planes, int act,
+                             int64_t out_plane_pitch, void* stream);
+
+/* ... and bbb_lrt_pool_act_bwd_chwn with it, argument for argument: act_mu / act_var over moment_planes planes, g_var = g_mu *
+ * (v - act_mu) / (2 act_var), the g_out2 / x_out combine of the incoming gradient. */
+int bbb_lrt_avgpool_act_bwd_chwn(const bbb_pool_desc_t* d, const float* g_out, const float* y, const float* act_mu, const float* act_var,
+                                 float* g_mu, float* g_var, int64_t planes, int64_t moment_planes, int act, int64_t out_plane_pitch,
+                                 const float* g_out2, const float* x_out, int64_t x_planes, void* stream);
+
+/*
  * E noise draws from ONE pair of LRT moments, batch-innermost: y[e] = act(act_mu + sqrt(act_var) * eps[e]) with eps exactly
  * as bbb_lrt_conv2d_chwn_fwd would have drawn it for draw e (layers/BBB_LRT/BBBConv.py:78-81).  For an LRT layer whose input
  * is the same for every draw (the first layer of a model) this replaces E identical pairs of contractions by one.

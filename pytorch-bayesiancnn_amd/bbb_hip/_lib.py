@@ -51,6 +51,14 @@ class ConvDesc(ctypes.Structure):
                 ("x_unit_div", c_i32), ("x_unit_off", c_i32), ("pool", c_i32), ("w_tap_major", c_i32)]
 
 
+POOL_AVG = 1
+
+
+class PoolDesc(ctypes.Structure):
+    _fields_ = [("kind", c_i32), ("h", c_i32), ("w", c_i32), ("batch", c_i32), ("kh", c_i32), ("kw", c_i32), ("stride_h", c_i32),
+                ("stride_w", c_i32), ("pad_h", c_i32), ("pad_w", c_i32), ("count_include_pad", c_i32)]
+
+
 _SIGNATURES = {
     "bbb_reparam_kl_fwd": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_float, c_float, c_u64, c_u32, c_u32,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -88,6 +96,12 @@ _SIGNATURES = {
     "bbb_pool_act_bwd_chwn": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_void_p]),
     "bbb_lrt_pool_act_bwd_chwn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
+    "bbb_avgpool_plan": (c_int, [ctypes.POINTER(PoolDesc), c_i64, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                 ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "bbb_avgpool_chwn": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_i64, c_void_p]),
+    "bbb_avgpool_act_bwd_chwn": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p]),
+    "bbb_lrt_avgpool_act_bwd_chwn": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                             c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
     "bbb_conv2d_chwn_bf16_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_u32, c_void_p]),
     "bbb_conv2d_chwn_bf16_plan": (c_int, [ctypes.POINTER(ConvDesc), c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
                                           ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),

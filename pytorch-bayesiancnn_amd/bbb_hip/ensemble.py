@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, rng, _lib
+from . import ops, pool_desc, rng, _lib
 from .infer_walk import (BAYES_FORMS, ChwnPartition, ChwnPlan, ChwnStep, chwn_partition, conv_flops,  # noqa: F401
                          _act_name, _chwn_steps, _chwn_walk, _run)
 
@@ -138,11 +138,13 @@ def flat_children(net):
 def output_rows(net, x_shape):
     """Rows of the model's output for an input of shape x_shape (B, except where FlattenLayer cuts a larger feature map into
     several rows per image: the reference's view(-1, num_features), layers/misc.py:35)."""
-    cache = _structure(net)["rows"]
+    st_ = _structure(net)
+    cache = st_["rows"]
     if x_shape in cache:
         return cache[x_shape]
     B, C, H, W = x_shape
     rows = B
+    avg_ok = True                        # every average pool met a map it is admitted on (pool_desc.avgpool_of): _avgpools_ok
     for m in flat_children(net) or []:
         if isinstance(m, (_BBBConv, _LRTConv)):
             (sh, sw), (ph, pw), (dh, dw) = ops._pair(m.stride), ops._pair(m.padding), ops._pair(m.dilation)
@@ -153,11 +155,26 @@ def output_rows(net, x_shape):
         elif isinstance(m, nn.MaxPool2d):
             k, st = m.kernel_size, m.stride
             H, W = (H - k) // st + 1, (W - k) // st + 1
+        elif pool_desc.is_avgpool(m):
+            spec = pool_desc.avgpool_of(m, H, W)
+            if spec is None:             # (a pool the fast paths do not take: the caller is on the module-by-module loop)
+                avg_ok = False
+            else:
+                H, W = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
         elif isinstance(m, FlattenLayer):
             rows = rows * C * H * W // m.num_features
             C, H, W = m.num_features, 1, 1
     cache[tuple(x_shape)] = rows
+    st_.setdefault("avg_ok", {})[tuple(x_shape)] = avg_ok
     return rows
+
+
+def _avgpools_ok(net, x_shape):
+    """Every nn.AvgPool2d / nn.AdaptiveAvgPool2d of the model is one the batch-innermost paths admit on the map it meets for an input
+    of x_shape (pool_desc.avgpool_of); True for a model without one.  Decided by output_rows' shape walk, remembered with it."""
+    x_shape = tuple(x_shape)
+    output_rows(net, x_shape)
+    return _structure(net)["avg_ok"][x_shape]
 
 
 class Timers:
@@ -295,7 +312,8 @@ def _variances_all(layers, timers=None):
 
 def _chwn_ok(net, x, any_batch=True):
     """The batch-innermost fast path handles: 4-d input, no autograd, and only module kinds it knows how to run in that layout
-    (Bayesian layers, ReLU/Softplus, MaxPool2d without padding, FlattenLayer that flattens whole images).  Batch sizes that are
+    (Bayesian layers, ReLU/Softplus, MaxPool2d without padding, the average pools of pool_desc.avgpool_of on the maps they meet,
+    FlattenLayer that flattens whole images).  Batch sizes that are
     not a multiple of 4 (image rows move as 16-byte vectors) run PADDED with zero images whose rows are dropped again
     (_mc_logits_chwn); any_batch=False: only batches that need no padding (work units, several steps per launch)."""
     if torch.is_grad_enabled() and any_requires_grad(net):
@@ -305,7 +323,8 @@ def _chwn_ok(net, x, any_batch=True):
     st = _structure(net)
     if "chwn_mods" not in st:
         st["chwn_mods"] = _chwn_mods_ok(flat_children(net))
-    return st["chwn_mods"]
+        st["has_avg"] = st["chwn_mods"] and _has_avgpool(net)
+    return st["chwn_mods"] and (not st["has_avg"] or _avgpools_ok(net, tuple(x.shape)))
 
 
 def _chwn_mods_ok(mods):
@@ -320,8 +339,14 @@ def _chwn_mods_ok(mods):
             k, s = m.kernel_size, m.stride
             if isinstance(k, int) and isinstance(s, int) and m.padding == 0 and m.dilation == 1 and not m.ceil_mode:
                 continue
+        if pool_desc.is_avgpool(m):
+            continue                     # (which of them the walk takes depends on the map: pool_desc.avgpool_of, asked by the planner)
         return False
     return True
+
+
+def _has_avgpool(net):
+    return any(pool_desc.is_avgpool(m) for m in flat_children(net) or [])
 
 
 _BF16_LRT_HINT = ("LRT models run in bf16 only under LaunchConfig.bf16_lrt (ops.use_config(bf16_lrt=True) or launch_config= on the "
@@ -347,6 +372,9 @@ def _check_precision(precision, net, x, fast_path_allowed, dropin=False):
         return
     if precision != "bf16":
         raise _lib.BBBHipError(f"precision must be 'fp32', 'bf16x3' or 'bf16', got {precision!r}")
+    if _has_avgpool(net):
+        raise _lib.BBBHipError("bf16 storage has no average pooling (nn.AvgPool2d / nn.AdaptiveAvgPool2d run in precision='fp32' or "
+                               "'bf16x3'; nothing of the bf16 path falls back to fp32)")
     if not fast_path_allowed or not _chwn_ok(net, x, any_batch=False):
         raise _lib.BBBHipError("bf16 runs on the batch-innermost inference path only (no autograd, no external eps, "
                                "4-d input with B % 8 == 0, BBB layers + ReLU/Softplus/MaxPool2d/FlattenLayer)")

@@ -29,7 +29,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, pool_desc
+from .conv_desc import out_map as _out_map
 
 
 def _layers():
@@ -42,7 +43,8 @@ def _layers():
 def train_path_ok(net, x):
     """The fast autograd path covers: a 4-d CUDA fp32 batch with B % 4 == 0; a flat model (ensemble.flat_children) of Bayesian
     conv / linear layers of ONE kind (all BBB or all BBB_LRT) sharing one prior, each optionally followed by ReLU /
-    Softplus(1, 20) and then MaxPool2d (no padding, floor), and a FlattenLayer that keeps one row per image; convolutions of any
+    Softplus(1, 20) and then MaxPool2d (no padding, floor) or an average pool pool_desc.avgpool_of admits (nn.AvgPool2d, a dividing
+    nn.AdaptiveAvgPool2d), and a FlattenLayer that keeps one row per image; convolutions of any
     positive stride in any layer (a strided layer behind the first takes its input gradient on the transposed launch,
     ops.conv2d_chwn_input_grad(stride=)), padding within the kernel reach (p <= d (k - 1)) and channel counts that are multiples
     of 4 everywhere except the first layer; the model ends in a Bayesian linear layer; no eps replay.  Returns "bbb", "lrt" or
@@ -77,6 +79,7 @@ def _train_path_static(net, x):
     kinds = set()
     i = 0
     after_layer = False                  # the previous module was a Bayesian layer (+ its fused activation): a pool may follow
+    H, W = int(x.shape[2]), int(x.shape[3])                # the map, followed for the average pools (pool_desc.avgpool_of asks about it)
     while i < len(mods):
         m = mods[i]
         poolable, after_layer = after_layer, False
@@ -91,6 +94,7 @@ def _train_path_static(net, x):
                 (ph, pw), (dh, dw) = ops._pair(m.padding), ops._pair(m.dilation)
                 if dh * (m.kernel_size[0] - 1) < ph or dw * (m.kernel_size[1] - 1) < pw:
                     return None
+                H, W = _out_map(H, W, m.kernel_size, m.stride, m.padding, m.dilation)
             elif m.in_features % 4 != 0:
                 return None              # (a first linear layer too: its weight gradient takes the 4-aligned channel path)
             first = False
@@ -103,8 +107,14 @@ def _train_path_static(net, x):
                 return None
             if not poolable:
                 return None              # a leading pool, or a pool after a pool / flatten: the node's backward pairs pools with layers
+            H, W = (H - k) // s + 1, (W - k) // s + 1
+        elif pool_desc.is_avgpool(m):          # an average pool stands where a max pool may
+            spec = pool_desc.avgpool_of(m, H, W) if (poolable and H > 0 and W > 0) else None
+            if spec is None:
+                return None
+            H, W = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
         elif isinstance(m, FlattenLayer):
-            pass
+            H = W = 1
         else:
             return None                      # a stand-alone activation or anything else: not on this path
         i += 1
@@ -179,14 +189,15 @@ def _param_lists(layers, leaf):
     return mus, rhos, ids
 
 
-def _walk(mods, h, is_layer, run_layer, pool):
+def _walk(mods, h, is_layer, run_layer, pool, avgpool=None):
     """The forward walk over a flat model (ensemble.flat_children), one copy for the three nodes: -> (tape, final h).
     h: the batch-innermost input [1, C, H, W, B].  is_layer(m): m is a Bayesian layer of the node's kind.
     run_layer(m, li, x_in, is_conv, geom, act, pooled) -> a record holding at least `y`, the activated output [E', Cout, Ho, Wo, B]
     (x_in: h, for a linear layer reshaped to [*, in_features, 1, 1, B]; geom: (stride, padding, dilation); act: the activation
-    module behind the layer, fused and skipped; pooled: a MaxPool2d follows that).  pool(y, kernel, stride): the node's pooling.
-    The walk completes the record -- layer, x, act, geom, pool (kernel, stride) or None, first, out_shape (of what the next layer
-    reads) -- and appends it to the tape."""
+    module behind the layer, fused and skipped; pooled: a pool follows that).  pool(y, kernel, stride): the node's max pooling;
+    avgpool(y, kernel, stride, padding, count_include_pad): its average pooling (None: the node has none).
+    The walk completes the record -- layer, x, act, geom, pool (kernel, stride) or None, avg (pool_desc.avgpool_of's tuple: the pool
+    behind the layer is that average pool) or None, first, out_shape (of what the next layer reads) -- and appends it to the tape."""
     from . import ensemble
     from layers.lrt import BBBConv2d as LRTConv2d
     _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
@@ -202,17 +213,26 @@ def _walk(mods, h, is_layer, run_layer, pool):
             act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
             if act is not None:
                 i += 1
-            pool_mod = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.MaxPool2d) else None
-            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None)
-            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, first=not tape)
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            pool_mod = nxt if isinstance(nxt, nn.MaxPool2d) else None
+            avg_mod = nxt if pool_desc.is_avgpool(nxt) else None
+            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None or avg_mod is not None)
+            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, avg=None, first=not tape)
             h = rec["y"]
             if pool_mod is not None:
                 h = pool(h, pool_mod.kernel_size, pool_mod.stride)
                 rec["pool"] = (pool_mod.kernel_size, pool_mod.stride)
                 i += 1
+            elif avg_mod is not None:
+                spec = pool_desc.avgpool_of(avg_mod, h.shape[-3], h.shape[-2])
+                if spec is None or avgpool is None:
+                    raise _lib.BBBHipError("fast_train: an average pool this path does not take (train_path_ok refuses it)")
+                h = avgpool(h, *spec)
+                rec["avg"] = spec
+                i += 1
             rec["out_shape"] = tuple(h.shape)
             tape.append(rec)
-        elif isinstance(m, nn.MaxPool2d):                                  # a pool that does not follow a Bayesian layer: on the input
+        elif isinstance(m, nn.MaxPool2d) or pool_desc.is_avgpool(m):             # a pool that does not follow a Bayesian layer: on the input
             raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
         elif isinstance(m, FlattenLayer):
             h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
@@ -303,7 +323,7 @@ class _MCForward(torch.autograd.Function):
             return dict(w=w5, y=ops.conv2d_chwn_forward(x_in, w5, b, *geom, act=act))
 
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)               # [1, C, H, W, B]
-        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn)
+        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn, ops.avgpool_chwn)
         _carry(ctx, cfg, params)
         ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
         ctx.x_nchw = x.detach()
@@ -348,7 +368,9 @@ class _MCForward(torch.autograd.Function):
                 break
             g = g.reshape(rec["out_shape"])
             pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
-            if rec["pool"] is not None:
+            if rec["avg"] is not None:
+                g_pre = ops.avgpool_act_backward_chwn(g, y, *rec["avg"], act, pad_planes=pad)
+            elif rec["pool"] is not None:
                 g_pre = ops.pool_act_backward_chwn(g, y, rec["pool"][0], rec["pool"][1], act, pad_planes=pad)
             elif act is not None:
                 g_pre = ops.pool_act_backward_chwn(g, y, 0, 1, act, pad_planes=pad)
@@ -528,7 +550,8 @@ class _MCForwardLRT(torch.autograd.Function):
             return dict(w_mu=w_mu, w_var=w_var, y=y, am=am, av=av)
 
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)
-        tape, h = _walk(ensemble.flat_children(cfg["net"]), h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn)
+        tape, h = _walk(ensemble.flat_children(cfg["net"]), h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn,
+                        ops.avgpool_chwn)
         _carry(ctx, cfg, params)
         ctx.tape = tape
         ctx.x_nchw = x.detach()
@@ -571,11 +594,17 @@ class _MCForwardLRT(torch.autograd.Function):
             # below the first layer the pair (d/d act_mu, d/d act_var) stays ONE buffer: its two weight gradients (with x, x^2) and,
             # for a single draw, its two input gradients (with W_mu, W_var) run as the draws of one launch each
             g_pair = None
+            if rec["avg"] is not None:                                   # (an average pool behind the layer: the same pass, its routing)
+                def pool_pass(**kw):
+                    return ops.lrt_avgpool_act_backward_chwn(g, y, am, av, *rec["avg"], act, **kw)
+            else:
+                def pool_pass(**kw):
+                    return ops.lrt_pool_act_backward_chwn(g, y, am, av, k, s, act, **kw)
             if pair_lrt_backward[0] and not rec["first"]:
-                g_pair = ops.lrt_pool_act_backward_chwn(g, y, am, av, k, s, act, stacked=True, combine=comb)        # [2, E, Cout, Ho, Wo, B]
+                g_pair = pool_pass(stacked=True, combine=comb)                                 # [2, E, Cout, Ho, Wo, B]
                 g_mu, g_var = g_pair[0], g_pair[1]
             else:
-                g_mu, g_var = ops.lrt_pool_act_backward_chwn(g, y, am, av, k, s, act, pad_planes=pad, combine=comb)
+                g_mu, g_var = pool_pass(pad_planes=pad, combine=comb)
             if am.shape[0] == 1 and g_mu.shape[0] > 1:      # first layer: one pair of moments feeds every draw
                 # (the two sums one set apart in one buffer: the input gradient reads them as the two draws of one launch)
                 both = torch.empty((2, 1) + tuple(g_mu.shape[1:]), dtype=torch.float32, device=g_mu.device)
@@ -648,6 +677,8 @@ def bf16_train_refusal(net, x):
     if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
         return "no eps replay"
     kind = train_path_ok(net, x)
+    if kind is not None and ensemble._has_avgpool(net):
+        return "models without average pooling (nn.AvgPool2d / nn.AdaptiveAvgPool2d have no bf16 kernels; precision='fp32' trains such a model)"
     if kind == "lrt":
         return "BBB (weight-space) layers; local-reparameterisation layers have no bf16 mode"
     if kind is None:

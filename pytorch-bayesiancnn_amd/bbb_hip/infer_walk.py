@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, _lib
+from . import ops, pool_desc, _lib
 from layers.bbb import _BBBLayer, BBBConv2d as _BBBConv
 from layers.lrt import _LRTLayer, BBBConv2d as _LRTConv
 from layers.misc import FlattenLayer
@@ -102,9 +102,10 @@ BAYES_FORMS = ("s2d_lrt", "s2d_bbb", "bf16_bbb", "c8x3_lrt", "c8x3_bbb", "fp32_b
 
 
 class ChwnStep:
-    """One step of the walk: a launch (one of BAYES_FORMS, "pool", "to_c8s3"), a torch op ("relu", "softplus", "to_f32") or a view
-    ("flatten").  i / mod: the module (a conversion: the module it prepares for, None at the end); act: the activation fused into the
-    launch; pool: the MaxPool2d fused into it (True, or (k, s) where the launch takes any window); logits: the launch writes the
+    """One step of the walk: a launch (one of BAYES_FORMS, "pool", "avgpool", "to_c8s3"), a torch op ("relu", "softplus", "to_f32") or
+    a view ("flatten").  i / mod: the module (a conversion: the module it prepares for, None at the end); act: the activation fused into
+    the launch; pool: the MaxPool2d fused into it (True, or (k, s) where the launch takes any window) -- an "avgpool" step: its
+    (kernel, stride, padding, count_include_pad), pool_desc.avgpool_of; logits: the launch writes the
     logits buffer; first: the first Bayesian layer (it reads the caller's input blocks); rows: a flatten that cuts every image
     into that many rows; in_layout / layout: how h enters / leaves (f32 | s3 | c8s3 | bf16 | bf16c8); in_shape / out_shape:
     (C, H, W, B); n_mods: modules consumed; a Bayesian layer's is_conv, geom = (stride, padding, dilation), ckk = (Cin, kh, kw) and
@@ -305,6 +306,19 @@ class _Planner:
                                           (hw[0], hw[1], B), self.Es)
         return dict(pool=pool_ks, out_c8=out_c8)
 
+    def avgpool(self, i, mod):
+        """nn.AvgPool2d / nn.AdaptiveAvgPool2d as a launch of its own (ops.avgpool_chwn; never fused into a conv launch), on fp32
+        planes: the split layouts are converted in front of it, as in front of a stand-alone activation.  No plan where
+        pool_desc.avgpool_of does not admit the module on this map, or on bf16 storage (which has no average pooling)."""
+        C, H, W = self.chw
+        spec = None if self.bf16 else pool_desc.avgpool_of(mod, H, W)
+        if spec is None:
+            raise _NoPlan
+        if self.lay in ("s3", "c8s3"):
+            self.to_f32(i, mod)
+        ho, wo = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
+        return self.emit("avgpool", i, mod, self.lay, (C, ho, wo, self.B), 1, pool=spec)
+
     def flatten(self, i, mod):
         F_, (C, H, W) = mod.num_features, self.chw
         if self.lay == "c8s3" and not (H * W == 1 and C == F_):  # ([E, 3, F / 8, 1, 1, B, 8] already is the flattened feature order)
@@ -342,6 +356,8 @@ def _chwn_steps(children, x_shape, part, precision, cfg, draws, n_slabs=None):
                 elif isinstance(mod, nn.MaxPool2d):
                     k, s = mod.kernel_size, mod.stride
                     i += p.emit("pool", i, mod, p.lay, (p.chw[0], (p.chw[1] - k) // s + 1, (p.chw[2] - k) // s + 1, p.B), 1)
+                elif pool_desc.is_avgpool(mod):
+                    i += p.avgpool(i, mod)
                 else:
                     if p.lay in ("s3", "c8s3"):
                         p.to_f32(i, mod)
@@ -499,6 +515,8 @@ def _chwn_walk(c, steps, e0, e1):
             pool = ops.maxpool_c8s3 if st.in_layout == "c8s3" else ops.maxpool_chwn_s3 if st.in_layout == "s3" else \
                 (ops.maxpool_chwn_bf16 if c.bf16 else ops.maxpool_chwn)
             h = _run(timers, "maxpool", None, lambda h=h, mod=mod, pool=pool: pool(h, mod.kernel_size, mod.stride))
+        elif form == "avgpool":
+            h = _run(timers, "avgpool", None, lambda h=h, st=st: ops.avgpool_chwn(h, *st.pool))
         elif form == "relu":
             h = torch.relu(h)
         elif form == "softplus":

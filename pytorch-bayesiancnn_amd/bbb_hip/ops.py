@@ -20,6 +20,7 @@ import torch
 
 from . import _lib, rng
 from ._lib import Segment, check, ptr, require_device, cur_stream, on_device
+from .pool_desc import avgpool_of, avgpool_plan, is_avgpool, pool_desc as _pool_desc  # noqa: F401  (ops.avgpool_of, ...)
 from .conv_desc import ACT_CODE, _pair, bf16_flags, c8x3_flags, conv_desc, out_map, pool_code, pooled_map, slab_rule  # noqa: F401  (ops.ACT_CODE)
 
 _scratch = {}
@@ -952,6 +953,31 @@ def maxpool_chwn(x, k, s):
     with on_device(x.device):
         check(_lib.lib().bbb_maxpool_chwn(x.data_ptr(), y.data_ptr(), planes, H, W, B, int(k), int(s), cur_stream(x.device)),
               "bbb_maxpool_chwn")
+    return y
+
+
+# ---- average pooling (csrc/pool2d.hip; what a launch checks: csrc/pool_plan.h; what is admitted: bbb_hip/pool_desc.py) ----
+def _avgpool_grad_shape(g_out, planes, H, W, B, avg):
+    """The backward kernels index g_out by the pooled map: refuse a gradient of any other size before the launch."""
+    ho, wo, _, _ = avgpool_plan(H, W, B, *avg, planes=planes)
+    if g_out.numel() != planes * ho * wo * B:
+        raise _lib.BBBHipError("average-pool backward: g_out must hold %d planes of the pooled map %d x %d x %d" % (planes, ho, wo, B))
+
+
+def avgpool_chwn(x, kernel, stride, padding=0, count_include_pad=True):
+    """AvgPool2d(kernel, stride, padding, count_include_pad=) in floor mode on [..., H, W, B] (B innermost, B % 4 == 0): the taps
+    inside the map added in scan order, one IEEE division (bbb_avgpool_chwn)."""
+    require_device(x)
+    x = x.contiguous()
+    *lead, H, W, B = x.shape
+    planes = 1
+    for v in lead:
+        planes *= v
+    d = _pool_desc(H, W, B, kernel, stride, padding, count_include_pad)
+    ho, wo, _, _ = avgpool_plan(H, W, B, kernel, stride, padding, count_include_pad, planes=max(planes, 1))
+    y = torch.empty((*lead, ho, wo, B), dtype=torch.float32, device=x.device)
+    with on_device(x.device):
+        check(_lib.lib().bbb_avgpool_chwn(ctypes.byref(d), x.data_ptr(), y.data_ptr(), planes, cur_stream(x.device)), "bbb_avgpool_chwn")
     return y
 
 
@@ -1902,10 +1928,11 @@ def padded_plane_pitch(K):
     return K + 32 if K % 1024 == 0 else K
 
 
-def pool_act_backward_chwn(g_out, y, k, s, act, pad_planes=False):
+def pool_act_backward_chwn(g_out, y, k, s, act, pad_planes=False, avg=None):
     """Backward of [fused activation -> MaxPool2d(k, s)] (k = 0: activation only) on [..., H, W, B] planes: gradient w.r.t.
     the layer's pre-activation from the gradient w.r.t. the (pooled) output and the ACTIVATED output y (bbb_pool_act_bwd_chwn).
-    pad_planes: return a view of y's shape into a [planes, padded_plane_pitch(H*W*B)] buffer (see there)."""
+    pad_planes: return a view of y's shape into a [planes, padded_plane_pitch(H*W*B)] buffer (see there).
+    avg = (kernel, stride, padding, count_include_pad): the pool is that average pool instead (avgpool_act_backward_chwn)."""
     require_device(g_out, y)
     g_out, y = g_out.contiguous(), y.contiguous()
     *lead, H, W, B = y.shape
@@ -1919,10 +1946,23 @@ def pool_act_backward_chwn(g_out, y, k, s, act, pad_planes=False):
         g_pre = buf[:, :K].view(*lead, H, W, B)
     else:
         buf = g_pre = torch.empty_like(y)
+    if avg is not None:
+        _avgpool_grad_shape(g_out, planes, H, W, B, avg)
     with on_device(y.device):
-        check(_lib.lib().bbb_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), buf.data_ptr(), planes, H, W, B, int(k), int(s),
-                                               ACT_CODE[act], pitch if pitch != K else 0, cur_stream(y.device)), "bbb_pool_act_bwd_chwn")
+        if avg is not None:
+            check(_lib.lib().bbb_avgpool_act_bwd_chwn(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(), buf.data_ptr(),
+                                                      planes, ACT_CODE[act], pitch if pitch != K else 0, cur_stream(y.device)),
+                  "bbb_avgpool_act_bwd_chwn")
+        else:
+            check(_lib.lib().bbb_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), buf.data_ptr(), planes, H, W, B, int(k), int(s),
+                                                   ACT_CODE[act], pitch if pitch != K else 0, cur_stream(y.device)), "bbb_pool_act_bwd_chwn")
     return g_pre
+
+
+def avgpool_act_backward_chwn(g_out, y, kernel, stride, padding, count_include_pad, act, pad_planes=False):
+    """Backward of [fused activation -> AvgPool2d(kernel, stride, padding, count_include_pad=)] on [..., H, W, B] planes
+    (bbb_avgpool_act_bwd_chwn): pool_act_backward_chwn with every tap of a window receiving that window's gradient over its divisor."""
+    return pool_act_backward_chwn(g_out, y, 0, 1, act, pad_planes=pad_planes, avg=(kernel, stride, padding, count_include_pad))
 
 
 def plane_sums(g, over_draws=False):
@@ -1987,13 +2027,14 @@ def lrt_input_grad_combine(g1, x, g2):
     return out
 
 
-def lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, k, s, act, pad_planes=False, stacked=False, combine=None):
+def lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, k, s, act, pad_planes=False, stacked=False, combine=None, avg=None):
     """pool_act_backward_chwn for a local-reparameterisation layer: -> (g_mu, g_var), the gradients w.r.t. act_mu and act_var
     (bbb_lrt_pool_act_bwd_chwn).  act_mu / act_var: y's shape, or one draw's worth ([1, C, H, W, B]) when every draw was sampled
     from the same pair of moments.  stacked (without pad_planes): the two land in ONE buffer [2, *y.shape], returned as such --
     the weight-side and input-side contractions of the pair then run as the draws of one launch.
     combine = (x_out, g_out2): the incoming gradient is g_out + 2 * x_out * g_out2 (lrt_input_grad_combine of the layer above,
-    formed on the fly: g_out / g_out2 = its two input gradients, x_out = this layer's output, [E|1, ...] of g_out's trailing shape)."""
+    formed on the fly: g_out / g_out2 = its two input gradients, x_out = this layer's output, [E|1, ...] of g_out's trailing shape).
+    avg = (kernel, stride, padding, count_include_pad): the pool is that average pool instead (lrt_avgpool_act_backward_chwn)."""
     require_device(g_out, y, act_mu, act_var)
     g_out, y, act_mu, act_var = g_out.contiguous(), y.contiguous(), act_mu.contiguous(), act_var.contiguous()
     g2p, xcp, x_planes = 0, 0, 0
@@ -2020,16 +2061,33 @@ def lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, k, s, act, pad_planes=
     else:
         both = torch.empty((2,) + tuple(y.shape), dtype=torch.float32, device=y.device)
         bufs = outs = [both[0], both[1]]
+    x_planes = (planes * xc.numel() // g_out.numel()) if combine is not None else 0
+    if avg is not None:
+        _avgpool_grad_shape(g_out, planes, H, W, B, avg)
     with on_device(y.device):
-        check(_lib.lib().bbb_lrt_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), act_mu.data_ptr(), act_var.data_ptr(),
-                                                   bufs[0].data_ptr(), bufs[1].data_ptr(), planes, mom_planes, H, W, B, int(k), int(s),
-                                                   ACT_CODE[act], pitch if pitch != K else 0, g2p, xcp,
-                                                   (planes * xc.numel() // g_out.numel()) if combine is not None else 0,
-                                                   cur_stream(y.device)),
-              "bbb_lrt_pool_act_bwd_chwn")
+        if avg is not None:
+            check(_lib.lib().bbb_lrt_avgpool_act_bwd_chwn(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(),
+                                                          act_mu.data_ptr(), act_var.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                                          planes, mom_planes, ACT_CODE[act], pitch if pitch != K else 0, g2p, xcp,
+                                                          x_planes, cur_stream(y.device)),
+                  "bbb_lrt_avgpool_act_bwd_chwn")
+        else:
+            check(_lib.lib().bbb_lrt_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), act_mu.data_ptr(), act_var.data_ptr(),
+                                                       bufs[0].data_ptr(), bufs[1].data_ptr(), planes, mom_planes, H, W, B, int(k), int(s),
+                                                       ACT_CODE[act], pitch if pitch != K else 0, g2p, xcp, x_planes,
+                                                       cur_stream(y.device)),
+                  "bbb_lrt_pool_act_bwd_chwn")
     if stacked and pitch == K:
         return both
     return outs[0], outs[1]
+
+
+def lrt_avgpool_act_backward_chwn(g_out, y, act_mu, act_var, kernel, stride, padding, count_include_pad, act, pad_planes=False,
+                                  stacked=False, combine=None):
+    """lrt_pool_act_backward_chwn behind an AvgPool2d(kernel, stride, padding, count_include_pad=) (bbb_lrt_avgpool_act_bwd_chwn):
+    the same arguments and results, the average pool's routing."""
+    return lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, 0, 1, act, pad_planes=pad_planes, stacked=stacked, combine=combine,
+                                      avg=(kernel, stride, padding, count_include_pad))
 
 
 def flip_transpose_w(w):

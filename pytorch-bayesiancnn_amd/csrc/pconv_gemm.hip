@@ -29,6 +29,7 @@
 #include "pconv_body.cuh"
 #include "pconv_bf16x3.cuh"
 #include "pconv_plan.h"
+#include "pool_act_bwd.cuh"
 
 namespace {
 
@@ -125,17 +126,8 @@ __global__ __launch_bounds__(256) void pool_act_bwd_chwn_kernel(const float* __r
                                                                 int64_t xc_total4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total4) return;
-    // g2 != NULL (an LRT layer below another one): the incoming gradient is g_out + 2 * xc * g2 -- the two input gradients of the
-    // layer above combined on the fly (bbb_lrt_glue mode 1's fmaf, bit for bit) instead of by a launch of its own
-    auto incoming = [&](int64_t idx) {
-        f32x4 gv = reinterpret_cast<const f32x4*>(g_out)[idx];
-        if (g2 != nullptr) {
-            const f32x4 b4v = reinterpret_cast<const f32x4*>(g2)[idx], x4v = reinterpret_cast<const f32x4*>(xc)[idx % xc_total4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) gv[u] = fmaf(2.0f * x4v[u], b4v[u], gv[u]);
-        }
-        return gv;
-    };
+    // (the incoming gradient and everything behind the routed gradient: pool_act_bwd.cuh, shared with the average-pool routing)
+    auto incoming = [&](int64_t idx) { return pool_bwd::incoming(g_out, g2, xc, xc_total4, idx); };
     const int b4 = (int)(i % B4);
     int64_t t = i / B4;
     const int w = (int)(t % W);
@@ -170,32 +162,7 @@ __global__ __launch_bounds__(256) void pool_act_bwd_chwn_kernel(const float* __r
                 for (int u = 0; u < 4; ++u) g[u] += first[u] ? go[u] : 0.0f;
             }
     }
-    f32x4 o;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        float d = 1.0f;
-        if (act == 1) d = me[u] > 0.0f ? 1.0f : 0.0f;
-        else if (act == 2) d = me[u] > 20.0f ? 1.0f : -expm1f(-me[u]);      // y = softplus(v) -> sigmoid(v) = 1 - exp(-y)
-        o[u] = g[u] * d;
-    }
-    // out_pitch4 != 0: planes are written at that pitch (in 16-byte units) instead of densely -- see bbb_pool_act_bwd_chwn
-    const int64_t oi = out_pitch4 ? pl * out_pitch4 + (i - pl * (int64_t)H * W * B4) : i;
-    reinterpret_cast<f32x4*>(g_pre)[oi] = o;
-    if (am != nullptr) {
-        const int64_t in_plane = i - pl * (int64_t)H * W * B4;
-        const int64_t mi = (pl % mom_planes) * ((int64_t)H * W * B4) + in_plane;
-        const f32x4 a4 = reinterpret_cast<const f32x4*>(am)[mi];
-        const f32x4 v4 = reinterpret_cast<const f32x4*>(av)[mi];
-        f32x4 gv;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float v = me[u];
-            if (act == 2 && !(v > 20.0f)) v = v + logf(-expm1f(-v));
-            const float t = (act != 0 && !(me[u] > 0.0f)) ? 0.0f : v - a4[u];        // sqrt(act_var) * eps
-            gv[u] = (o[u] * t) / (2.0f * v4[u]);
-        }
-        reinterpret_cast<f32x4*>(g_var)[oi] = gv;
-    }
+    pool_bwd::act_epilogue(g, me, act, i, pl, (int64_t)H * W * B4, out_pitch4, g_pre, am, av, g_var, mom_planes);
 }
 
 // the descriptor checks (pconv_plan.h, describe) -> the kernel-argument block

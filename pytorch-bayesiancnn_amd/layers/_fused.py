@@ -149,14 +149,34 @@ def _hooks_present(wrapper, mods):
 hooked_chain_enabled = [True]
 
 
+def loop_child(child, x):
+    """child(x) in the module-by-module loop.  An average pool the batched paths admit (ops.avgpool_of) computes on the HIP kernel
+    those paths run (ops.avgpool_chwn, between two layout transposes) where it can -- a 4-d fp32 GPU batch with B % 4 == 0 and no
+    autograd -- so that the loop, hooked_chain and the whole-model forward are the same bits (torch's own average pools add in
+    another order and divide twice); the module is still CALLED, its hooks fire as ever.  Everything else: child(x)."""
+    from bbb_hip import ops
+    if not (ops.is_avgpool(child) and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and
+            x.shape[0] > 0 and x.shape[0] % 4 == 0 and not (torch.is_grad_enabled() and x.requires_grad) and
+            "forward" not in child.__dict__):
+        return child(x)
+    spec = ops.avgpool_of(child, x.shape[2], x.shape[3])
+    if spec is None:
+        return child(x)
+    child.__dict__["forward"] = lambda t: ops.from_batch_innermost(ops.avgpool_chwn(ops.to_batch_innermost(t), *spec))
+    try:
+        return child(x)
+    finally:
+        del child.__dict__["forward"]
+
+
 def hooked_chain(wrapper, x, scope):
     """The per-layer forward of a model whose children carry forward (pre-)hooks, WITHOUT leaving the batch-innermost layout between
     the layers: the children run in definition order on the kernels the per-layer path uses anyway (ops.conv2d_layer /
     lrt_conv2d_layer: batch-innermost GEMM, plain fmaf chain; torch activations; HIP pooling) -- bit for bit that path's results --
     but the layout transposes around every layer are gone: only a module that carries a hook gets its input and output as the
     NCHW tensors the hook expects (and may replace).  ~19 launches per forward instead of ~35 (the path is host-bound).
-    Applies to: a flat wrapper of Bayesian conv / linear layers, ReLU / Softplus(1, 20), MaxPool2d (no padding, floor) and a
-    FlattenLayer that keeps one row per image; a 4-d fp32 GPU batch with B % 4 == 0; no autograd; plain hooks (no kwargs hooks, no
+    Applies to: a flat wrapper of Bayesian conv / linear layers, ReLU / Softplus(1, 20), MaxPool2d (no padding, floor), the average
+    pools of ops.avgpool_of and a FlattenLayer that keeps one row per image; a 4-d fp32 GPU batch with B % 4 == 0; no autograd; plain hooks (no kwargs hooks, no
     global hooks); every layer's weights presampled by enter().  Returns the output, or None (-> the module-by-module loop)."""
     import torch.nn as nn
     import torch.nn.functional as F
@@ -245,6 +265,12 @@ def hooked_chain(wrapper, x, scope):
                 put(chwn_t=r) if st["chwn"] is not None else put(nchw_t=r)
             elif isinstance(m, nn.MaxPool2d):
                 put(chwn_t=ops.maxpool_chwn(chwn(), m.kernel_size, m.stride if m.stride is not None else m.kernel_size))
+            elif ops.is_avgpool(m):
+                h = chwn()
+                spec = ops.avgpool_of(m, h.shape[2], h.shape[3])
+                if spec is None:
+                    raise RuntimeError("hooked_chain: an average pool the batched path does not take slipped through the checks")
+                put(chwn_t=ops.avgpool_chwn(h, *spec))
             elif isinstance(m, FlattenLayer):
                 h = chwn()
                 if h.shape[1] * h.shape[2] * h.shape[3] != m.num_features:

@@ -58,7 +58,7 @@ class ModuleWrapper(nn.Module):
                 x = y
             else:
                 for child in self.children():   # launch) for every Bayesian layer below this wrapper
-                    x = child(x)
+                    x = _fused.loop_child(child, x)
             if scope is not None and scope.kl is not None:
                 return x, scope.kl          # KL of all layers, already reduced on the device
             kl = 0.0
