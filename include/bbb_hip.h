@@ -469,7 +469,7 @@ int bbb_lrt_pool_act_bwd_chwn(const float* g_out, const float* y, const float* a
 #define BBB_POOL_AVG 1        /* bbb_pool_desc_t::kind (0 is not a kind; 2 is kept for a maximum kind) */
 typedef struct bbb_pool_desc {
     int32_t kind;              /* BBB_POOL_AVG */
-    int32_t h, w, batch;       /* the input map and the images per plane (batch % 4 == 0) */
+    int32_t h, w, batch;       /* the input map and the images per plane (batch % 4 == 0; % 8 on bf16 planes) */
     int32_t kh, kw;            /* window */
     int32_t stride_h, stride_w;
     int32_t pad_h, pad_w;      /* zero padding, 2 * pad <= k on each axis (torch's rule: every window then holds a valid tap) */
@@ -502,6 +502,31 @@ int bbb_avgpool_act_bwd_chwn(const bbb_pool_desc_t* d, const float* g_out, const
 int bbb_lrt_avgpool_act_bwd_chwn(const bbb_pool_desc_t* d, const float* g_out, const float* y, const float* act_mu, const float* act_var,
                                  float* g_mu, float* g_var, int64_t planes, int64_t moment_planes, int act, int64_t out_plane_pitch,
                                  const float* g_out2, const float* x_out, int64_t x_planes, void* stream);
+
+/*
+ * Average pooling on bf16 planes (csrc/pool2d_bf16.hip; additive to ABI 13): the pool of the bf16 storage mode, opt-in from Python
+ * (LaunchConfig.bf16_avgpool).  The descriptor is the one above with batch % 8 == 0: a thread moves a 16-byte group of 8 images.
+ *
+ * bbb_avgpool_bf16_plan: bbb_avgpool_plan at that group width -- the same checks in the same order, BBB_ESHAPE for batch % 8 != 0,
+ *   BBB_EINVAL for an out_plane_pitch that is not a multiple of 8 (csrc/pool_plan.h: plan_bf16).
+ * bbb_avgpool_chwn_bf16: x [planes][h][w][B] bf16 -> y [planes][ho][wo][B] bf16.  The valid taps of a window are converted to fp32
+ *   (exact), added in scan order (rows, then columns) by plain fp32 adds, divided ONCE (IEEE division) by bbb_avgpool_chwn's divisor,
+ *   and the quotient is rounded ONCE to bf16, nearest-even.  The order depends on the window alone: a plane computed alone or among
+ *   others is the same bits.
+ * bbb_avgpool_act_bwd_chwn_bf16: bbb_avgpool_act_bwd_chwn's routing on bbb_pool_act_bwd_chwn_bf16's storage rules.  y
+ *   [planes][h][w][B] the stored bf16 ACTIVATED output, g_out [planes][ho][wo][B] bf16 or, with BBB_BF16_BWD_G_F32, fp32;
+ *   g_act(h, w) = the fp32 sum of g_out(oh, ow) / divisor(oh, ow) (each an IEEE division) over the windows that contain (h, w), in
+ *   ascending (oh, ow); elements no window covers receive 0.  g_pre = g_act * act'(y) (ReLU [y > 0]; Softplus 1 - exp(-y), 1 above
+ *   20), rounded once to bf16; with BBB_BF16_BWD_OUT_F32 written as the fp32 values of that rounding.  out_plane_pitch: 0 = dense,
+ *   else elements (% 8 == 0).  Gather form: no atomics, deterministic.  There is no LRT form.
+ * Both launches check, in this order: null pointers (BBB_EINVAL), the plan, 16-byte alignment of every pointer (BBB_EALIGN), then
+ * act outside 0..2 or unknown flag bits (BBB_EINVAL).
+ */
+int bbb_avgpool_bf16_plan(const bbb_pool_desc_t* d, int64_t planes, int64_t out_plane_pitch, int32_t* ho, int32_t* wo,
+                          int64_t* fwd_blocks, int64_t* bwd_blocks);
+int bbb_avgpool_chwn_bf16(const bbb_pool_desc_t* d, const void* x, void* y, int64_t planes, void* stream);
+int bbb_avgpool_act_bwd_chwn_bf16(const bbb_pool_desc_t* d, const void* g_out, const void* y, void* g_pre, int64_t planes, int act,
+                                  int64_t out_plane_pitch, uint32_t flags, void* stream);
 
 /*
  * E noise draws from ONE pair of LRT moments, batch-innermost: y[e] = act(act_mu + sqrt(act_var) * eps[e]) with eps exactly

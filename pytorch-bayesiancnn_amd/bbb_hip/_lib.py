@@ -102,6 +102,11 @@ _SIGNATURES = {
     "bbb_avgpool_act_bwd_chwn": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p]),
     "bbb_lrt_avgpool_act_bwd_chwn": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
                                              c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_void_p]),
+    "bbb_avgpool_bf16_plan": (c_int, [ctypes.POINTER(PoolDesc), c_i64, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "bbb_avgpool_chwn_bf16": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_i64, c_void_p]),
+    "bbb_avgpool_act_bwd_chwn_bf16": (c_int, [ctypes.POINTER(PoolDesc), c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_u32,
+                                              c_void_p]),
     "bbb_conv2d_chwn_bf16_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_u32, c_void_p]),
     "bbb_conv2d_chwn_bf16_plan": (c_int, [ctypes.POINTER(ConvDesc), c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
                                           ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),

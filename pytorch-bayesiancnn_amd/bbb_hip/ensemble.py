@@ -353,6 +353,12 @@ _BF16_LRT_HINT = ("LRT models run in bf16 only under LaunchConfig.bf16_lrt (ops.
                   "graphed classes): all-LRT models on mc_logits / mc_forward / GraphedMC / GraphedPipeline")
 
 
+_BF16_AVGPOOL_REFUSAL = ("bf16 storage has no average pooling (nn.AvgPool2d / nn.AdaptiveAvgPool2d run in precision='fp32' or "
+                         "'bf16x3'; nothing of the bf16 path falls back to fp32) unless LaunchConfig.bf16_avgpool is set "
+                         "(ops.use_config(bf16_avgpool=True) or launch_config= on the graphed classes: the average pool on bf16 "
+                         "planes, one more rounding per pool, opt-in)")
+
+
 def _has_lrt(net):
     return any(isinstance(l, _LRTLayer) for l in bayesian_layers(net))
 
@@ -372,9 +378,8 @@ def _check_precision(precision, net, x, fast_path_allowed, dropin=False):
         return
     if precision != "bf16":
         raise _lib.BBBHipError(f"precision must be 'fp32', 'bf16x3' or 'bf16', got {precision!r}")
-    if _has_avgpool(net):
-        raise _lib.BBBHipError("bf16 storage has no average pooling (nn.AvgPool2d / nn.AdaptiveAvgPool2d run in precision='fp32' or "
-                               "'bf16x3'; nothing of the bf16 path falls back to fp32)")
+    if _has_avgpool(net) and not ops.current_config().bf16_avgpool:
+        raise _lib.BBBHipError(_BF16_AVGPOOL_REFUSAL)
     if not fast_path_allowed or not _chwn_ok(net, x, any_batch=False):
         raise _lib.BBBHipError("bf16 runs on the batch-innermost inference path only (no autograd, no external eps, "
                                "4-d input with B % 8 == 0, BBB layers + ReLU/Softplus/MaxPool2d/FlattenLayer)")

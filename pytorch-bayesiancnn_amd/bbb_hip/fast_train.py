@@ -412,6 +412,8 @@ class _MCForwardBF16(torch.autograd.Function):
     each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the walk of _MCForward._backward on the same
     _Schedule with
       * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
+      * ops.avgpool_act_backward_chwn_bf16   the same behind an average pool (LaunchConfig.bf16_avgpool): every window's gradient over
+        its divisor to each of its taps,
       * ops.plane_sums_bf16               bias gradients, the fp32 sum of that bf16 g_pre,
       * ops.conv2d_chwn_input_grad_bf16   dgrad on the bf16 GEMM over the flipped bf16 weight rows -> bf16 (a strided layer, admitted
         under LaunchConfig.bf16_strided_train: the transposed launch on the same rows),
@@ -442,7 +444,7 @@ class _MCForwardBF16(torch.autograd.Function):
             return dict(w=w, wshape=wshape, y=y)
 
         h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
-        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn_bf16)
+        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn_bf16, ops.avgpool_chwn_bf16)
         _carry(ctx, cfg, params)
         ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
         # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted)
@@ -482,8 +484,10 @@ class _MCForwardBF16(torch.autograd.Function):
             g = g.reshape(rec["out_shape"])
             shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
             k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
-            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
+            if rec["pool"] is None and rec["avg"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
                 g_pre = g                                                 # already the bf16 output gradient
+            elif rec["avg"] is not None:
+                g_pre = ops.avgpool_act_backward_chwn_bf16(g, y, *rec["avg"], act, out_f32=shared, pad_planes=shared)
             else:
                 g_pre = ops.pool_act_backward_chwn_bf16(g, y if y.dtype == torch.bfloat16 else None, k, s, act, out_f32=shared,
                                                         pad_planes=shared)
@@ -667,8 +671,9 @@ def _strided_later_conv(net):
 
 def bf16_train_refusal(net, x):
     """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0 --
-    with stride-1 convolutions behind the first layer, or any stride there under LaunchConfig.bf16_strided_train (read from the
-    configuration that is current: the caller's use_config, or what GraphedTrainStep snapshotted)."""
+    with stride-1 convolutions behind the first layer, or any stride there under LaunchConfig.bf16_strided_train, and without average
+    pools, or with them under LaunchConfig.bf16_avgpool (both read from the configuration that is current: the caller's use_config,
+    or what GraphedTrainStep snapshotted)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return "a 4-d fp32 CUDA batch"
     if x.requires_grad and torch.is_grad_enabled():
@@ -677,8 +682,9 @@ def bf16_train_refusal(net, x):
     if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
         return "no eps replay"
     kind = train_path_ok(net, x)
-    if kind is not None and ensemble._has_avgpool(net):
-        return "models without average pooling (nn.AvgPool2d / nn.AdaptiveAvgPool2d have no bf16 kernels; precision='fp32' trains such a model)"
+    if kind is not None and ensemble._has_avgpool(net) and not ops.current_config().bf16_avgpool:
+        return ("models without average pooling (precision='fp32' trains such a model) unless LaunchConfig.bf16_avgpool is set "
+                "(ops.use_config(bf16_avgpool=True) or launch_config= on GraphedTrainStep: the average pool on bf16 planes, opt-in)")
     if kind == "lrt":
         return "BBB (weight-space) layers; local-reparameterisation layers have no bf16 mode"
     if kind is None:

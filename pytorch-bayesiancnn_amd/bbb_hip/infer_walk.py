@@ -196,7 +196,7 @@ class _Planner:
     the first Bayesian layer: its slab e reads block (e + x_off) // x_div)."""
 
     def __init__(self, children, x_shape, part, precision, cfg, draws, Es):
-        self.children, self.Es, self.bf16 = children, Es, precision == "bf16"
+        self.children, self.Es, self.bf16, self.cfg = children, Es, precision == "bf16", cfg
         self.tm, self.s2d_first, self.lrt_mode, split_mode = _chwn_modes(children, x_shape, draws, precision, cfg)
         self.bayes = [i for i, m in enumerate(children) if isinstance(m, (_BBBLayer, _LRTLayer))]
         self.last_bayes = self.bayes[-1] if self.bayes else -1
@@ -308,15 +308,22 @@ class _Planner:
 
     def avgpool(self, i, mod):
         """nn.AvgPool2d / nn.AdaptiveAvgPool2d as a launch of its own (ops.avgpool_chwn; never fused into a conv launch), on fp32
-        planes: the split layouts are converted in front of it, as in front of a stand-alone activation.  No plan where
-        pool_desc.avgpool_of does not admit the module on this map, or on bf16 storage (which has no average pooling)."""
+        planes: the split layouts are converted in front of it, as in front of a stand-alone activation.  bf16 storage, under
+        LaunchConfig.bf16_avgpool: the same step on planar bf16 planes (ops.avgpool_chwn_bf16, the map asked of the 8-wide plan).
+        No plan where pool_desc.avgpool_of does not admit the module on this map; on bf16 storage without the switch; on bf16 storage
+        in any layout but "bf16" (the planner chooses the channel-interleaved one only in front of a conv; the logits are fp32)."""
         C, H, W = self.chw
-        spec = None if self.bf16 else pool_desc.avgpool_of(mod, H, W)
+        if self.bf16 and not (self.cfg.bf16_avgpool and self.lay == "bf16"):
+            raise _NoPlan
+        spec = pool_desc.avgpool_of(mod, H, W)
         if spec is None:
             raise _NoPlan
         if self.lay in ("s3", "c8s3"):
             self.to_f32(i, mod)
-        ho, wo = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
+        try:
+            ho, wo = (pool_desc.avgpool_bf16_plan(H, W, self.B, *spec) if self.bf16 else pool_desc.avgpool_plan(H, W, 4, *spec))[:2]
+        except _lib.BBBHipError:
+            raise _NoPlan from None                              # (B % 8 != 0: bf16 storage does not take this batch at all)
         return self.emit("avgpool", i, mod, self.lay, (C, ho, wo, self.B), 1, pool=spec)
 
     def flatten(self, i, mod):
@@ -516,7 +523,8 @@ def _chwn_walk(c, steps, e0, e1):
                 (ops.maxpool_chwn_bf16 if c.bf16 else ops.maxpool_chwn)
             h = _run(timers, "maxpool", None, lambda h=h, mod=mod, pool=pool: pool(h, mod.kernel_size, mod.stride))
         elif form == "avgpool":
-            h = _run(timers, "avgpool", None, lambda h=h, st=st: ops.avgpool_chwn(h, *st.pool))
+            avg = ops.avgpool_chwn_bf16 if st.in_layout == "bf16" else ops.avgpool_chwn
+            h = _run(timers, "avgpool", None, lambda h=h, st=st, avg=avg: avg(h, *st.pool))
         elif form == "relu":
             h = torch.relu(h)
         elif form == "softplus":

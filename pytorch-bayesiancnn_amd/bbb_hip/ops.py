@@ -20,7 +20,7 @@ import torch
 
 from . import _lib, rng
 from ._lib import Segment, check, ptr, require_device, cur_stream, on_device
-from .pool_desc import avgpool_of, avgpool_plan, is_avgpool, pool_desc as _pool_desc  # noqa: F401  (ops.avgpool_of, ...)
+from .pool_desc import avgpool_bf16_plan, avgpool_of, avgpool_plan, is_avgpool, pool_desc as _pool_desc  # noqa: F401  (ops.avgpool_of, ...)
 from .conv_desc import ACT_CODE, _pair, bf16_flags, c8x3_flags, conv_desc, out_map, pool_code, pooled_map, slab_rule  # noqa: F401  (ops.ACT_CODE)
 
 _scratch = {}
@@ -345,11 +345,17 @@ class LaunchConfig:
     bf16_strided_train   False | True: train_step / forward_loss / GraphedTrainStep(precision="bf16") admit BBB models with STRIDED
                 convolutions behind the first layer: their input gradient runs on the transposed form of the general bf16 GEMM
                 (conv2d_chwn_input_grad_bf16(stride=...), bbb_conv2d_chwn_bf16_dgrad; bf16 in, fp32 accumulation, one rounding).
-                Opt-in: under the default such a model is refused, as it always was (precision="fp32" trains it)"""
+                Opt-in: under the default such a model is refused, as it always was (precision="fp32" trains it)
+    bf16_avgpool   False | True: precision="bf16" admits models with nn.AvgPool2d / a dividing nn.AdaptiveAvgPool2d (pool_desc.avgpool_of)
+                on avgpool_chwn_bf16 / avgpool_act_backward_chwn_bf16 (csrc/pool2d_bf16.hip: bf16 planes, fp32 sums in scan order, one
+                IEEE division, ONE rounding to bf16; the backward in gather form with act' from the stored bf16 output).  Inference
+                (mc_logits / mc_forward / the Graphed* objects / the drop-in loop; LRT models together with bf16_lrt) and BBB
+                training (train_step / forward_loss / GraphedTrainStep), B % 8 == 0.  Opt-in: under the default bf16 on a model
+                with an average pool raises, naming this switch, as it always did"""
     FIELDS = ("gemm_mode", "bf16x3_min_workgroups", "s3_min_images", "split_k", "pool_fusion", "pool_fuse_min_items",
               "pool_fuse_imbalance", "launches_overlap", "pool_fuse_min_items_overlapped", "pool_fuse_weight_budget",
               "bf16_pool_fuse_min_rows", "bf16_pool_fuse_min_rows_overlapped", "bf16_c8", "bf16_c8_min_items", "c8x3", "c8x3_s2d",
-              "dropin_precision", "bf16_lrt", "bf16_strided_train")
+              "dropin_precision", "bf16_lrt", "bf16_strided_train", "bf16_avgpool")
     __slots__ = FIELDS
 
     def __init__(self, **kw):
@@ -372,6 +378,7 @@ class LaunchConfig:
         self.dropin_precision = "fp32"
         self.bf16_lrt = False                          # precision="bf16" on all-LRT models (lrt_conv2d_chwn_bf16_forward); opt-in
         self.bf16_strided_train = False                # bf16 training of models with strided later layers (bbb_conv2d_chwn_bf16_dgrad); opt-in
+        self.bf16_avgpool = False                      # precision="bf16" on models with average pools (csrc/pool2d_bf16.hip); opt-in
         self.c8x3 = True                               # split-bf16 mode: layers (behind the first) with Cin % 32 == 0 run on the
                                                        # MFMA-ready-operand kernel (conv2d_c8x3_forward: channel-interleaved split
                                                        # activations + tap-major weights from the parameter pass); False: round 4's
@@ -1336,6 +1343,24 @@ def maxpool_chwn_bf16(x, k, s):
     with on_device(x.device):
         check(_lib.lib().bbb_maxpool_chwn_bf16(x.data_ptr(), y.data_ptr(), planes, H, W, B, int(k), int(s), cur_stream(x.device)),
               "bbb_maxpool_chwn_bf16")
+    return y
+
+
+def avgpool_chwn_bf16(x, kernel, stride, padding=0, count_include_pad=True):
+    """avgpool_chwn on bf16 [..., H, W, B] (B % 8 == 0): the taps inside the map added in scan order in fp32, one IEEE division, one
+    rounding to bf16 (bbb_avgpool_chwn_bf16)."""
+    require_device(x, dtype=torch.bfloat16)
+    x = x.contiguous()
+    *lead, H, W, B = x.shape
+    planes = 1
+    for v in lead:
+        planes *= v
+    d = _pool_desc(H, W, B, kernel, stride, padding, count_include_pad)
+    ho, wo, _, _ = avgpool_bf16_plan(H, W, B, kernel, stride, padding, count_include_pad, planes=max(planes, 1))
+    y = torch.empty((*lead, ho, wo, B), dtype=torch.bfloat16, device=x.device)
+    with on_device(x.device):
+        check(_lib.lib().bbb_avgpool_chwn_bf16(ctypes.byref(d), x.data_ptr(), y.data_ptr(), planes, cur_stream(x.device)),
+              "bbb_avgpool_chwn_bf16")
     return y
 
 
@@ -2520,6 +2545,40 @@ def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=F
         check(_lib.lib().bbb_pool_act_bwd_chwn_bf16(g_out.data_ptr(), ptr(y), buf.data_ptr(), planes, H, W, B, int(k), int(s),
                                                     ACT_CODE[act], pitch if pitch != K else 0, flags, cur_stream(g_out.device)),
               "bbb_pool_act_bwd_chwn_bf16")
+    return g_pre
+
+
+def avgpool_act_backward_chwn_bf16(g_out, y, kernel, stride, padding, count_include_pad, act, out_f32=False, pad_planes=False):
+    """pool_act_backward_chwn_bf16 behind an AvgPool2d(kernel, stride, padding, count_include_pad=) (bbb_avgpool_act_bwd_chwn_bf16):
+    every tap of a window receives that window's gradient over its divisor (fp32, windows in ascending order), times act'(y) from the
+    stored bf16 y [..., H, W, B], rounded once to bf16.  g_out bf16 or fp32, of the pooled size; out_f32 / pad_planes as there."""
+    if g_out.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BBBHipError("avgpool_act_backward_chwn_bf16: g_out must be bf16 or fp32")
+    require_device(g_out, dtype=g_out.dtype)
+    require_device(y, dtype=torch.bfloat16)
+    y, g_out = y.contiguous(), g_out.contiguous()
+    *lead, H, W, B = y.shape
+    planes = 1
+    for v in lead:
+        planes *= v
+    avg = (kernel, stride, padding, count_include_pad)
+    ho, wo, _, _ = avgpool_bf16_plan(H, W, B, *avg, planes=max(planes, 1))
+    if g_out.numel() != planes * ho * wo * B:
+        raise _lib.BBBHipError("average-pool backward: g_out must hold %d planes of the pooled map %d x %d x %d" % (planes, ho, wo, B))
+    K = H * W * B
+    pitch = padded_plane_pitch(K) if pad_planes else K
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if pitch != K:
+        buf = torch.empty((planes, pitch), dtype=dt, device=g_out.device)
+        g_pre = buf[:, :K].view(*lead, H, W, B)
+    else:
+        buf = g_pre = torch.empty(tuple(y.shape), dtype=dt, device=g_out.device)
+    flags = (1 if g_out.dtype == torch.float32 else 0) | (2 if out_f32 else 0)
+    with on_device(g_out.device):
+        check(_lib.lib().bbb_avgpool_act_bwd_chwn_bf16(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(),
+                                                       buf.data_ptr(), planes, ACT_CODE[act], pitch if pitch != K else 0, flags,
+                                                       cur_stream(g_out.device)),
+              "bbb_avgpool_act_bwd_chwn_bf16")
     return g_pre
 
 

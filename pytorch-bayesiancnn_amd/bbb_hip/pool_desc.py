@@ -22,10 +22,19 @@ def pool_desc(H, W, B, kernel, stride, padding, count_include_pad):
 def avgpool_plan(H, W, B, kernel, stride, padding=0, count_include_pad=True, planes=1, out_plane_pitch=0):
     """(ho, wo, forward workgroups, backward workgroups) of the average-pool launches on `planes` planes [H, W, B]
     (bbb_avgpool_plan, the launch entries' own plan; host only: needs no device).  A geometry the launches refuse raises their error."""
-    d = pool_desc(H, W, B, kernel, stride, padding, count_include_pad)
+    return _plan("bbb_avgpool_plan", pool_desc(H, W, B, kernel, stride, padding, count_include_pad), planes, out_plane_pitch)
+
+
+def avgpool_bf16_plan(H, W, B, kernel, stride, padding=0, count_include_pad=True, planes=1, out_plane_pitch=0):
+    """avgpool_plan of the launches on bf16 planes (bbb_avgpool_bf16_plan: 16-byte groups of 8 images, so B % 8 == 0 and a pitch
+    that is a multiple of 8; every other check shared with avgpool_plan).  Host only."""
+    return _plan("bbb_avgpool_bf16_plan", pool_desc(H, W, B, kernel, stride, padding, count_include_pad), planes, out_plane_pitch)
+
+
+def _plan(entry, d, planes, out_plane_pitch):
     ho, wo, fb, bb = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    check(_lib.lib().bbb_avgpool_plan(ctypes.byref(d), int(planes), int(out_plane_pitch), ctypes.byref(ho), ctypes.byref(wo),
-                                      ctypes.byref(fb), ctypes.byref(bb)), "bbb_avgpool_plan")
+    check(getattr(_lib.lib(), entry)(ctypes.byref(d), int(planes), int(out_plane_pitch), ctypes.byref(ho), ctypes.byref(wo),
+                                     ctypes.byref(fb), ctypes.byref(bb)), entry)
     return ho.value, wo.value, fb.value, bb.value
 
 

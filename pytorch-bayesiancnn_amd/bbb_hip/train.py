@@ -254,6 +254,7 @@ def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
             int(num_ens), float(train_size), net.training,
             ensemble._epoch[0], groups, rng.next_calls(0)[0],               # the noise seed is a constant of the captured kernels
             ops.current_config().bf16_strided_train,                        # (what bf16_train_refusal admits: switched off, it must refuse again)
+            ops.current_config().bf16_avgpool,                              # (likewise)
             precision)
 
 

@@ -2,7 +2,7 @@
 // floor mode (any window, stride and padding with 2 * pad <= k, either divisor rule) and, as the window H/oh x W/ow with the same
 // stride, nn.AdaptiveAvgPool2d on a map its output size divides -- the forward, and the backward of [activation -> pool] for the
 // training nodes (BBB and LRT forms, the arithmetic behind the routing shared with the max-pool backward: pool_act_bwd.cuh).
-// What every entry checks before it launches is pool_plan.h.
+// What every entry checks before it launches is pool_plan.h.  The same pool on bf16 planes (8 images per 16-byte group): pool2d_bf16.hip.
 //
 // Both kernels are bound by memory traffic (one pass over the larger of the two maps), one thread per 16-byte group of 4 images,
 // rows of images read and written as whole vectors: fully coalesced on both sides.  The order of every sum depends on the window
