@@ -427,8 +427,54 @@ int bbb_lrt_conv2d_chwn_splitk_fwd(const bbb_conv_desc_t* d, const float* x, con
 int bbb_conv2d_chwn_plan(const bbb_conv_desc_t* d, int lrt, int k_split, int has_scratch, int32_t* form, int32_t* bm, int32_t* ilv,
                          int64_t* items, int64_t* blocks);
 
-/* nn.MaxPool2d(kernel_size=k, stride=s) (no padding, floor mode; models/BayesianModels/BayesianAlexNet.py:37)
- * on batch-innermost planes: x [planes][h][w][B] -> y [planes][(h-k)/s+1][(w-k)/s+1][B]. */
+/*
+ * Pooling on batch-innermost planes x [planes][h][w][B] -> y [planes][ho][wo][B] (csrc/pool2d.hip; bf16 planes: csrc/pool2d_bf16.hip),
+ * one descriptor and one plan (csrc/pool_plan.h) for both kinds.  The output map is floor mode's, ho = (h + 2 pad_h - kh) / stride_h + 1.
+ *   BBB_POOL_MAX  nn.MaxPool2d(kernel_size=k, stride=s) (no padding, floor mode; models/BayesianModels/BayesianAlexNet.py:37): a square
+ *                 window, one stride, no padding, count_include_pad 0 -- what the maximum kernels implement.  Its launch entries take
+ *                 scalars (bbb_maxpool_chwn, bbb_pool_act_bwd_chwn, bbb_lrt_pool_act_bwd_chwn, and on bf16 planes bbb_maxpool_chwn_bf16,
+ *                 bbb_pool_act_bwd_chwn_bf16) and build this descriptor themselves; a backward's k = 0 (the activation alone) is
+ *                 planned as the 1 x 1 window at stride 1.
+ *   BBB_POOL_AVG  (additive to ABI 13) nn.AvgPool2d(kernel_size, stride, padding, ceil_mode=False, count_include_pad,
+ *                 divisor_override=None) -- and nn.AdaptiveAvgPool2d on a map its output size divides, which is the window
+ *                 (h / oh, w / ow) at the same stride without padding -- for models built from the layers package beyond the three
+ *                 of the zoo (LeNet-style stacks, global-average-pool heads).  Its launch entries take the descriptor
+ *                 (bbb_avgpool_*) and refuse any other kind as an unknown one (BBB_EINVAL).
+ * What an entry checks, in order, by family (the plan: in the order bbb_avgpool_plan documents):
+ *   forwards (bbb_maxpool_chwn, bbb_avgpool_chwn, and their _bf16 twins): null x / y (BBB_EINVAL); the plan; 16-byte alignment (BBB_EALIGN).
+ *   fp32 backwards (bbb_pool_act_bwd_chwn, bbb_avgpool_act_bwd_chwn): null g_out / y / g_pre or an activation outside 0..2
+ *     (BBB_EINVAL); the plan; alignment of the three (BBB_EALIGN).
+ *   LRT backwards (bbb_lrt_pool_act_bwd_chwn, bbb_lrt_avgpool_act_bwd_chwn): FIRST null act_mu / act_var / g_var, then moment_planes
+ *     (positive, dividing planes; both BBB_EINVAL), then the alignment of those three (BBB_EALIGN); then everything of the fp32
+ *     backwards; last the g_out2 / x_out pair: both or neither, x_planes positive and dividing planes (BBB_EINVAL), their alignment.
+ *   bf16 backwards (bbb_pool_act_bwd_chwn_bf16, bbb_avgpool_act_bwd_chwn_bf16): null g_out / g_pre, null y (the max entry: unless k = 0
+ *     and act = 0) (BBB_EINVAL); the plan; alignment (BBB_EALIGN); then an activation outside 0..2 or unknown flag bits (BBB_EINVAL).
+ * For the scalar entries every single violation is the code it always was, with one exception no memory reaches: the plan bounds the
+ * forward AND the backward grid, so a max forward whose own grid fits an int while planes * h * w * B / group threads do not (over 8 TB
+ * of input) is BBB_ESHAPE where it used to launch.  Where two violations coincide, the order above decides.
+ */
+#define BBB_POOL_AVG 1        /* bbb_pool_desc_t::kind (0 is not a kind) */
+#define BBB_POOL_MAX 2
+typedef struct bbb_pool_desc {
+    int32_t kind;              /* BBB_POOL_AVG | BBB_POOL_MAX */
+    int32_t h, w, batch;       /* the input map and the images per plane (batch % 4 == 0; % 8 on bf16 planes) */
+    int32_t kh, kw;            /* window (BBB_POOL_MAX: kh == kw) */
+    int32_t stride_h, stride_w;   /* (BBB_POOL_MAX: equal) */
+    int32_t pad_h, pad_w;      /* zero padding, 2 * pad <= k on each axis (torch's rule: every window then holds a valid tap); BBB_POOL_MAX: 0 */
+    int32_t count_include_pad; /* 1: the divisor is kh * kw; 0: the number of taps inside the map (BBB_POOL_MAX: 0) */
+} bbb_pool_desc_t;
+
+/* What the launches of this section do for a descriptor of either kind (host only, needs no device; the name dates from the average
+ * pool, which it answered for first): the output map and the workgroups (256 threads, one per 16-byte group of 4 images) of the
+ * forward and of the backward, or the code all of them refuse it with BEFORE anything is launched: BBB_EINVAL for a null descriptor,
+ * an unknown kind, a non-positive size, a negative padding, a count_include_pad other than 0 / 1, or a BBB_POOL_MAX descriptor with
+ * a rectangular window, two strides, a padding or count_include_pad 1; BBB_ESHAPE for batch % 4 != 0, 2 * pad > k on an axis, a
+ * window larger than the padded map, or a grid that does not fit an int; BBB_EINVAL for an out_plane_pitch (the backward's, 0 =
+ * dense) that is below h * w * batch or not a multiple of 4.  Out-pointers may be NULL. */
+int bbb_avgpool_plan(const bbb_pool_desc_t* d, int64_t planes, int64_t out_plane_pitch, int32_t* ho, int32_t* wo, int64_t* fwd_blocks,
+                     int64_t* bwd_blocks);
+
+/* BBB_POOL_MAX forward: y [planes][(h-k)/s+1][(w-k)/s+1][B]. */
 int bbb_maxpool_chwn(const float* x, float* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream);
 
 /*
@@ -460,31 +506,6 @@ int bbb_lrt_pool_act_bwd_chwn(const float* g_out, const float* y, const float* a
                               float* g_var, int64_t planes, int64_t moment_planes, int h, int w, int batch, int k, int s, int act,
                               int64_t out_plane_pitch, const float* g_out2, const float* x_out, int64_t x_planes, void* stream);
 
-/*
- * Average pooling on batch-innermost planes (additive to ABI 13): nn.AvgPool2d(kernel_size, stride, padding, ceil_mode=False,
- * count_include_pad, divisor_override=None) -- and nn.AdaptiveAvgPool2d on a map its output size divides, which is the window
- * (h / oh, w / ow) at the same stride without padding -- for models built from the layers package beyond the three of the zoo
- * (LeNet-style stacks, global-average-pool heads).  The output map is floor mode's, ho = (h + 2 pad_h - kh) / stride_h + 1.
- */
-#define BBB_POOL_AVG 1        /* bbb_pool_desc_t::kind (0 is not a kind; 2 is kept for a maximum kind) */
-typedef struct bbb_pool_desc {
-    int32_t kind;              /* BBB_POOL_AVG */
-    int32_t h, w, batch;       /* the input map and the images per plane (batch % 4 == 0; % 8 on bf16 planes) */
-    int32_t kh, kw;            /* window */
-    int32_t stride_h, stride_w;
-    int32_t pad_h, pad_w;      /* zero padding, 2 * pad <= k on each axis (torch's rule: every window then holds a valid tap) */
-    int32_t count_include_pad; /* 1: the divisor is kh * kw; 0: the number of taps inside the map */
-} bbb_pool_desc_t;
-
-/* What the three launches below do for this descriptor (host only, needs no device): the output map and the workgroups (256
- * threads, one per 16-byte group of 4 images) of the forward and of the backward, or the code all of them refuse it with BEFORE
- * anything is launched: BBB_EINVAL for a null descriptor, an unknown kind, a non-positive size, a negative padding or a
- * count_include_pad other than 0 / 1; BBB_ESHAPE for batch % 4 != 0, 2 * pad > k on an axis, a window larger than the padded map,
- * or a grid that does not fit an int; BBB_EINVAL for an out_plane_pitch (the backward's, 0 = dense) that is below h * w * batch or
- * not a multiple of 4.  Out-pointers may be NULL. */
-int bbb_avgpool_plan(const bbb_pool_desc_t* d, int64_t planes, int64_t out_plane_pitch, int32_t* ho, int32_t* wo, int64_t* fwd_blocks,
-                     int64_t* bwd_blocks);
-
 /* x [planes][h][w][B] -> y [planes][ho][wo][B]: the taps of a window that lie inside the map are added in scan order (rows, then
  * columns) by plain fp32 adds, then divided ONCE (IEEE division) by the divisor.  The order depends on the window alone, so a
  * plane computed alone or among others is the same bits.  x, y 16-byte aligned. */
@@ -504,10 +525,11 @@ int bbb_lrt_avgpool_act_bwd_chwn(const bbb_pool_desc_t* d, const float* g_out, c
                                  const float* g_out2, const float* x_out, int64_t x_planes, void* stream);
 
 /*
- * Average pooling on bf16 planes (csrc/pool2d_bf16.hip; additive to ABI 13): the pool of the bf16 storage mode, opt-in from Python
+ * Average pooling on bf16 planes (csrc/pool2d_bf16.hip, beside the maximum pool of that mode: bbb_maxpool_chwn_bf16,
+ * bbb_pool_act_bwd_chwn_bf16; additive to ABI 13): the average pool of the bf16 storage mode, opt-in from Python
  * (LaunchConfig.bf16_avgpool).  The descriptor is the one above with batch % 8 == 0: a thread moves a 16-byte group of 8 images.
  *
- * bbb_avgpool_bf16_plan: bbb_avgpool_plan at that group width -- the same checks in the same order, BBB_ESHAPE for batch % 8 != 0,
+ * bbb_avgpool_bf16_plan: bbb_avgpool_plan at that group width, for both kinds like it -- the same checks in the same order, BBB_ESHAPE for batch % 8 != 0,
  *   BBB_EINVAL for an out_plane_pitch that is not a multiple of 8 (csrc/pool_plan.h: plan_bf16).
  * bbb_avgpool_chwn_bf16: x [planes][h][w][B] bf16 -> y [planes][ho][wo][B] bf16.  The valid taps of a window are converted to fp32
  *   (exact), added in scan order (rows, then columns) by plain fp32 adds, divided ONCE (IEEE division) by bbb_avgpool_chwn's divisor,

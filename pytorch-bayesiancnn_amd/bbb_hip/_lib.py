@@ -51,7 +51,7 @@ class ConvDesc(ctypes.Structure):
                 ("x_unit_div", c_i32), ("x_unit_off", c_i32), ("pool", c_i32), ("w_tap_major", c_i32)]
 
 
-POOL_AVG = 1
+POOL_AVG, POOL_MAX = 1, 2
 
 
 class PoolDesc(ctypes.Structure):

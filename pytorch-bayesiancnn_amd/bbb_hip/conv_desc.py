@@ -102,5 +102,11 @@ def pool_code(pool):
 
 
 def pooled_map(ho, wo, pool):
-    k, s = int(pool[0]), int(pool[1])
-    return (ho - k) // s + 1, (wo - k) // s + 1
+    """The map behind MaxPool2d(*pool) without padding in floor mode, pool = (k, s), ints or pairs: THE statement of that arithmetic
+    for every max pool of the batch-innermost paths (a pooled conv form, a launch of its own).  Stated for any map: where the window
+    does not fit, the result is empty or negative and the launch entry is what refuses it."""
+    k, s = pool
+    if isinstance(k, int) and isinstance(s, int):
+        return (ho - k) // s + 1, (wo - k) // s + 1
+    (kh, kw), (sh, sw) = (_pair(v) if isinstance(v, (tuple, list)) else (int(v), int(v)) for v in pool)
+    return (ho - kh) // sh + 1, (wo - kw) // sw + 1

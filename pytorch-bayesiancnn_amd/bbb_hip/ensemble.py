@@ -144,7 +144,7 @@ def output_rows(net, x_shape):
         return cache[x_shape]
     B, C, H, W = x_shape
     rows = B
-    avg_ok = True                        # every average pool met a map it is admitted on (pool_desc.avgpool_of): _avgpools_ok
+    pools_ok = True                      # every pool is admitted on the map it meets (pool_desc.pool_of): _pools_ok
     for m in flat_children(net) or []:
         if isinstance(m, (_BBBConv, _LRTConv)):
             (sh, sw), (ph, pw), (dh, dw) = ops._pair(m.stride), ops._pair(m.padding), ops._pair(m.dilation)
@@ -152,29 +152,26 @@ def output_rows(net, x_shape):
             H = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
             W = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
             C = m.out_channels
-        elif isinstance(m, nn.MaxPool2d):
-            k, st = m.kernel_size, m.stride
-            H, W = (H - k) // st + 1, (W - k) // st + 1
-        elif pool_desc.is_avgpool(m):
-            spec = pool_desc.avgpool_of(m, H, W)
+        elif pool_desc.is_pool(m):
+            spec = pool_desc.pool_of(m, H, W)
             if spec is None:             # (a pool the fast paths do not take: the caller is on the module-by-module loop)
-                avg_ok = False
+                pools_ok = False
             else:
-                H, W = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
+                H, W = spec.out
         elif isinstance(m, FlattenLayer):
             rows = rows * C * H * W // m.num_features
             C, H, W = m.num_features, 1, 1
     cache[tuple(x_shape)] = rows
-    st_.setdefault("avg_ok", {})[tuple(x_shape)] = avg_ok
+    st_.setdefault("pools_ok", {})[tuple(x_shape)] = pools_ok
     return rows
 
 
-def _avgpools_ok(net, x_shape):
-    """Every nn.AvgPool2d / nn.AdaptiveAvgPool2d of the model is one the batch-innermost paths admit on the map it meets for an input
-    of x_shape (pool_desc.avgpool_of); True for a model without one.  Decided by output_rows' shape walk, remembered with it."""
+def _pools_ok(net, x_shape):
+    """Every pooling module of the model is one the batch-innermost paths admit on the map it meets for an input of x_shape
+    (pool_desc.pool_of); True for a model without one.  Decided by output_rows' shape walk, remembered with it."""
     x_shape = tuple(x_shape)
     output_rows(net, x_shape)
-    return _structure(net)["avg_ok"][x_shape]
+    return _structure(net)["pools_ok"][x_shape]
 
 
 class Timers:
@@ -312,7 +309,7 @@ def _variances_all(layers, timers=None):
 
 def _chwn_ok(net, x, any_batch=True):
     """The batch-innermost fast path handles: 4-d input, no autograd, and only module kinds it knows how to run in that layout
-    (Bayesian layers, ReLU/Softplus, MaxPool2d without padding, the average pools of pool_desc.avgpool_of on the maps they meet,
+    (Bayesian layers, ReLU/Softplus, the pools of pool_desc.pool_of -- MaxPool2d without padding, the average pools on the maps they meet --
     FlattenLayer that flattens whole images).  Batch sizes that are
     not a multiple of 4 (image rows move as 16-byte vectors) run PADDED with zero images whose rows are dropped again
     (_mc_logits_chwn); any_batch=False: only batches that need no padding (work units, several steps per launch)."""
@@ -324,7 +321,7 @@ def _chwn_ok(net, x, any_batch=True):
     if "chwn_mods" not in st:
         st["chwn_mods"] = _chwn_mods_ok(flat_children(net))
         st["has_avg"] = st["chwn_mods"] and _has_avgpool(net)
-    return st["chwn_mods"] and (not st["has_avg"] or _avgpools_ok(net, tuple(x.shape)))
+    return st["chwn_mods"] and (not st["has_avg"] or _pools_ok(net, tuple(x.shape)))
 
 
 def _chwn_mods_ok(mods):
@@ -335,12 +332,10 @@ def _chwn_mods_ok(mods):
             continue
         if isinstance(m, nn.Softplus) and m.beta == 1 and m.threshold == 20:
             continue
-        if isinstance(m, nn.MaxPool2d):
-            k, s = m.kernel_size, m.stride
-            if isinstance(k, int) and isinstance(s, int) and m.padding == 0 and m.dilation == 1 and not m.ceil_mode:
-                continue
+        if pool_desc.is_maxpool(m) and pool_desc.max_args_of(m) is not None:
+            continue                     # (pool_desc.pool_of's rule for a max pool: its arguments alone)
         if pool_desc.is_avgpool(m):
-            continue                     # (which of them the walk takes depends on the map: pool_desc.avgpool_of, asked by the planner)
+            continue                     # (which of them the walk takes depends on the map: pool_desc.pool_of, asked by the planner)
         return False
     return True
 

@@ -27,7 +27,6 @@ backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weig
 import os
 
 import torch
-import torch.nn as nn
 
 from . import _lib, ops, pool_desc
 from .conv_desc import out_map as _out_map
@@ -43,7 +42,7 @@ def _layers():
 def train_path_ok(net, x):
     """The fast autograd path covers: a 4-d CUDA fp32 batch with B % 4 == 0; a flat model (ensemble.flat_children) of Bayesian
     conv / linear layers of ONE kind (all BBB or all BBB_LRT) sharing one prior, each optionally followed by ReLU /
-    Softplus(1, 20) and then MaxPool2d (no padding, floor) or an average pool pool_desc.avgpool_of admits (nn.AvgPool2d, a dividing
+    Softplus(1, 20) and then a pool pool_desc.pool_of admits (MaxPool2d without padding in floor mode, nn.AvgPool2d, a dividing
     nn.AdaptiveAvgPool2d), and a FlattenLayer that keeps one row per image; convolutions of any
     positive stride in any layer (a strided layer behind the first takes its input gradient on the transposed launch,
     ops.conv2d_chwn_input_grad(stride=)), padding within the kernel reach (p <= d (k - 1)) and channel counts that are multiples
@@ -79,7 +78,7 @@ def _train_path_static(net, x):
     kinds = set()
     i = 0
     after_layer = False                  # the previous module was a Bayesian layer (+ its fused activation): a pool may follow
-    H, W = int(x.shape[2]), int(x.shape[3])                # the map, followed for the average pools (pool_desc.avgpool_of asks about it)
+    H, W = int(x.shape[2]), int(x.shape[3])                # the map, followed for the pools (pool_desc.pool_of asks about it)
     while i < len(mods):
         m = mods[i]
         poolable, after_layer = after_layer, False
@@ -101,18 +100,12 @@ def _train_path_static(net, x):
             after_layer = True
             if i + 1 < len(mods) and ensemble._act_name(mods[i + 1]) is not None:
                 i += 1
-        elif isinstance(m, nn.MaxPool2d):
-            k, s = m.kernel_size, m.stride
-            if not (isinstance(k, int) and isinstance(s, int) and m.padding == 0 and m.dilation == 1 and not m.ceil_mode):
-                return None
-            if not poolable:
-                return None              # a leading pool, or a pool after a pool / flatten: the node's backward pairs pools with layers
-            H, W = (H - k) // s + 1, (W - k) // s + 1
-        elif pool_desc.is_avgpool(m):          # an average pool stands where a max pool may
-            spec = pool_desc.avgpool_of(m, H, W) if (poolable and H > 0 and W > 0) else None
+        elif pool_desc.is_pool(m):
+            # (not poolable: a leading pool, or a pool after a pool / flatten -- the node's backward pairs pools with layers)
+            spec = pool_desc.pool_of(m, H, W) if poolable else None
             if spec is None:
                 return None
-            H, W = pool_desc.avgpool_plan(H, W, 4, *spec)[:2]
+            H, W = spec.out
         elif isinstance(m, FlattenLayer):
             H = W = 1
         else:
@@ -195,9 +188,10 @@ def _walk(mods, h, is_layer, run_layer, pool, avgpool=None):
     run_layer(m, li, x_in, is_conv, geom, act, pooled) -> a record holding at least `y`, the activated output [E', Cout, Ho, Wo, B]
     (x_in: h, for a linear layer reshaped to [*, in_features, 1, 1, B]; geom: (stride, padding, dilation); act: the activation
     module behind the layer, fused and skipped; pooled: a pool follows that).  pool(y, kernel, stride): the node's max pooling;
-    avgpool(y, kernel, stride, padding, count_include_pad): its average pooling (None: the node has none).
-    The walk completes the record -- layer, x, act, geom, pool (kernel, stride) or None, avg (pool_desc.avgpool_of's tuple: the pool
-    behind the layer is that average pool) or None, first, out_shape (of what the next layer reads) -- and appends it to the tape."""
+    avgpool(y, kernel, stride, padding, count_include_pad): its average pooling (None: the node has none) -- each called with the
+    spec of the pool behind the layer (pool_desc.pool_of) unpacked.
+    The walk completes the record -- layer, x, act, geom, pool (that spec: its kind, and as a tuple the arguments above; None without
+    a pool), first, out_shape (of what the next layer reads) -- and appends it to the tape."""
     from . import ensemble
     from layers.lrt import BBBConv2d as LRTConv2d
     _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
@@ -214,30 +208,36 @@ def _walk(mods, h, is_layer, run_layer, pool, avgpool=None):
             if act is not None:
                 i += 1
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            pool_mod = nxt if isinstance(nxt, nn.MaxPool2d) else None
-            avg_mod = nxt if pool_desc.is_avgpool(nxt) else None
-            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None or avg_mod is not None)
-            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, avg=None, first=not tape)
+            pool_mod = nxt if pool_desc.is_pool(nxt) else None
+            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None)
+            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, first=not tape)
             h = rec["y"]
             if pool_mod is not None:
-                h = pool(h, pool_mod.kernel_size, pool_mod.stride)
-                rec["pool"] = (pool_mod.kernel_size, pool_mod.stride)
-                i += 1
-            elif avg_mod is not None:
-                spec = pool_desc.avgpool_of(avg_mod, h.shape[-3], h.shape[-2])
-                if spec is None or avgpool is None:
-                    raise _lib.BBBHipError("fast_train: an average pool this path does not take (train_path_ok refuses it)")
-                h = avgpool(h, *spec)
-                rec["avg"] = spec
+                spec = pool_desc.pool_of(pool_mod, h.shape[-3], h.shape[-2])
+                run_pool = None if spec is None else pool if spec.kind == "max" else avgpool
+                if run_pool is None:
+                    raise _lib.BBBHipError("fast_train: a pool this path does not take (train_path_ok refuses it)")
+                h = run_pool(h, *spec)
+                rec["pool"] = spec
                 i += 1
             rec["out_shape"] = tuple(h.shape)
             tape.append(rec)
-        elif isinstance(m, nn.MaxPool2d) or pool_desc.is_avgpool(m):             # a pool that does not follow a Bayesian layer: on the input
+        elif pool_desc.is_pool(m):                                                 # a pool that does not follow a Bayesian layer: on the input
             raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
         elif isinstance(m, FlattenLayer):
             h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
         i += 1
     return tape, h
+
+
+def _pool_pass(rec, max_pass, avg_pass, *tensors, **kw):
+    """The pooling / activation backward of a record, one place for the three nodes: the node's wrapper of the record's pool on
+    `tensors` -- max_pass(*tensors, k, s, act, **kw) behind a max pool or, as k = 0, behind the activation alone;
+    avg_pass(*tensors, kernel, stride, padding, count_include_pad, act, **kw) behind an average pool."""
+    spec = rec["pool"]
+    if spec is None:
+        return max_pass(*tensors, 0, 1, rec["act"], **kw)
+    return (max_pass if spec.kind == "max" else avg_pass)(*tensors, *spec, rec["act"], **kw)
 
 
 def _carry(ctx, cfg, params):
@@ -368,14 +368,10 @@ class _MCForward(torch.autograd.Function):
                 break
             g = g.reshape(rec["out_shape"])
             pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
-            if rec["avg"] is not None:
-                g_pre = ops.avgpool_act_backward_chwn(g, y, *rec["avg"], act, pad_planes=pad)
-            elif rec["pool"] is not None:
-                g_pre = ops.pool_act_backward_chwn(g, y, rec["pool"][0], rec["pool"][1], act, pad_planes=pad)
-            elif act is not None:
-                g_pre = ops.pool_act_backward_chwn(g, y, 0, 1, act, pad_planes=pad)
-            else:
+            if rec["pool"] is None and act is None:
                 g_pre = g
+            else:
+                g_pre = _pool_pass(rec, ops.pool_act_backward_chwn, ops.avgpool_act_backward_chwn, g, y, pad_planes=pad)
 
             def weight_side():
                 gws[2 * li + 1] = ops.plane_sums(g_pre)                   # bias gradient [E, Cout]
@@ -483,14 +479,11 @@ class _MCForwardBF16(torch.autograd.Function):
             stride, padding, dilation = rec["geom"]
             g = g.reshape(rec["out_shape"])
             shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
-            k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
-            if rec["pool"] is None and rec["avg"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
+            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
                 g_pre = g                                                 # already the bf16 output gradient
-            elif rec["avg"] is not None:
-                g_pre = ops.avgpool_act_backward_chwn_bf16(g, y, *rec["avg"], act, out_f32=shared, pad_planes=shared)
-            else:
-                g_pre = ops.pool_act_backward_chwn_bf16(g, y if y.dtype == torch.bfloat16 else None, k, s, act, out_f32=shared,
-                                                        pad_planes=shared)
+            else:                                                         # (the logits layer's fp32 y: no pool, no activation -- a rounding)
+                g_pre = _pool_pass(rec, ops.pool_act_backward_chwn_bf16, ops.avgpool_act_backward_chwn_bf16,
+                                   g, y if y.dtype == torch.bfloat16 else None, out_f32=shared, pad_planes=shared)
 
             def weight_side():
                 wsh = (E,) + wshape
@@ -593,17 +586,12 @@ class _MCForwardLRT(torch.autograd.Function):
             else:
                 g = g.reshape(rec["out_shape"])
             # one pass: pooling / activation backward AND the split into d/d act_mu, d/d act_var (was ~10 ATen kernels per layer)
-            k, s = rec["pool"] if rec["pool"] is not None else (0, 1)
             pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
             # below the first layer the pair (d/d act_mu, d/d act_var) stays ONE buffer: its two weight gradients (with x, x^2) and,
             # for a single draw, its two input gradients (with W_mu, W_var) run as the draws of one launch each
             g_pair = None
-            if rec["avg"] is not None:                                   # (an average pool behind the layer: the same pass, its routing)
-                def pool_pass(**kw):
-                    return ops.lrt_avgpool_act_backward_chwn(g, y, am, av, *rec["avg"], act, **kw)
-            else:
-                def pool_pass(**kw):
-                    return ops.lrt_pool_act_backward_chwn(g, y, am, av, k, s, act, **kw)
+            def pool_pass(**kw):
+                return _pool_pass(rec, ops.lrt_pool_act_backward_chwn, ops.lrt_avgpool_act_backward_chwn, g, y, am, av, **kw)
             if pair_lrt_backward[0] and not rec["first"]:
                 g_pair = pool_pass(stacked=True, combine=comb)                                 # [2, E, Cout, Ho, Wo, B]
                 g_mu, g_var = g_pair[0], g_pair[1]

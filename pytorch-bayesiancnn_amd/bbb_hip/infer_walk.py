@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, pool_desc, _lib
+from .conv_desc import pooled_map          # (a query, not a launch: asked directly, as pool_desc is)
 from layers.bbb import _BBBLayer, BBBConv2d as _BBBConv
 from layers.lrt import _LRTLayer, BBBConv2d as _LRTConv
 from layers.misc import FlattenLayer
@@ -221,7 +222,7 @@ class _Planner:
 
     def pool_behind(self, i, act):
         at = i + (2 if act is not None else 1)
-        return at, (self.children[at] if at < len(self.children) and isinstance(self.children[at], nn.MaxPool2d) else None)
+        return at, (self.children[at] if at < len(self.children) and pool_desc.is_maxpool(self.children[at]) else None)
 
     def layer(self, i, mod, act):
         """A Bayesian layer with what its launch fuses -> modules consumed."""
@@ -258,7 +259,7 @@ class _Planner:
             kw.update(self.bf16_bbb(i, mod, act, kw))
             form, out_lay = "bf16_bbb", ("bf16c8" if kw["out_c8"] else "f32" if kw["out_f32"] else "bf16")
             if kw["pool"]:
-                ho, wo = ((v - ops._pair(kw["pool"][0])[a]) // ops._pair(kw["pool"][1])[a] + 1 for a, v in enumerate((ho, wo)))
+                ho, wo = pooled_map(ho, wo, kw["pool"])
         elif use_c8:
             form, out_lay = ("c8x3_lrt" if self.lrt_mode else "c8x3_bbb"), ("f32" if last else "c8s3")
         elif isinstance(mod, _BBBLayer):
@@ -299,29 +300,33 @@ class _Planner:
         out_c8 = False
         nb = self.children[at + 1] if (fuse and at + 1 < len(self.children)) else None
         if isinstance(nb, _BBBConv) and (mod.out_channels if is_conv else mod.out_features) % 8 == 0 and not kw["logits"]:
-            hw = _out_hw(H, W, ckk, geom)
-            hw = [(v - ops._pair(pool_ks[0])[a]) // ops._pair(pool_ks[1])[a] + 1 for a, v in enumerate(hw)]
+            hw = pooled_map(*_out_hw(H, W, ckk, geom), pool_ks)
             out_c8 = ops.bf16_c8_input_ok((nb.in_channels, *nb.kernel_size), (nb.stride, nb.padding, nb.dilation),
                                           ops.bf16_tap_major(tuple(nb.W_mu.shape)), at + 1 == self.last_bayes and self.tail_is_last,
                                           (hw[0], hw[1], B), self.Es)
         return dict(pool=pool_ks, out_c8=out_c8)
 
-    def avgpool(self, i, mod):
-        """nn.AvgPool2d / nn.AdaptiveAvgPool2d as a launch of its own (ops.avgpool_chwn; never fused into a conv launch), on fp32
-        planes: the split layouts are converted in front of it, as in front of a stand-alone activation.  bf16 storage, under
-        LaunchConfig.bf16_avgpool: the same step on planar bf16 planes (ops.avgpool_chwn_bf16, the map asked of the 8-wide plan).
-        No plan where pool_desc.avgpool_of does not admit the module on this map; on bf16 storage without the switch; on bf16 storage
-        in any layout but "bf16" (the planner chooses the channel-interleaved one only in front of a conv; the logits are fp32)."""
+    def pool(self, i, mod):
+        """A pooling module as a launch of its own -> a "pool" step (nn.MaxPool2d: the launch reads kernel and stride off the module)
+        or an "avgpool" step (its `pool`: pool_desc.pool_of's spec, the wrappers' arguments), on the map pool_of states.  No plan
+        where pool_of does not admit the module on this map.  A max pool runs in whatever layout it meets
+        (ops.maxpool_chwn / _bf16 / _s3 / maxpool_c8s3).  An average pool (nn.AvgPool2d / nn.AdaptiveAvgPool2d; ops.avgpool_chwn, never
+        fused into a conv launch) runs on fp32 planes: the split layouts are converted in front of it, as in front of a stand-alone
+        activation.  bf16 storage, under LaunchConfig.bf16_avgpool: the same step on planar bf16 planes (ops.avgpool_chwn_bf16, the map
+        asked of the 8-wide plan); no plan on bf16 storage without the switch, or in any layout but "bf16" (the planner chooses the
+        channel-interleaved one only in front of a conv; the logits are fp32)."""
         C, H, W = self.chw
-        if self.bf16 and not (self.cfg.bf16_avgpool and self.lay == "bf16"):
-            raise _NoPlan
-        spec = pool_desc.avgpool_of(mod, H, W)
+        spec = pool_desc.pool_of(mod, H, W)
         if spec is None:
+            raise _NoPlan
+        if spec.kind == "max":
+            return self.emit("pool", i, mod, self.lay, (C, *spec.out, self.B), 1)
+        if self.bf16 and not (self.cfg.bf16_avgpool and self.lay == "bf16"):
             raise _NoPlan
         if self.lay in ("s3", "c8s3"):
             self.to_f32(i, mod)
         try:
-            ho, wo = (pool_desc.avgpool_bf16_plan(H, W, self.B, *spec) if self.bf16 else pool_desc.avgpool_plan(H, W, 4, *spec))[:2]
+            ho, wo = pool_desc.pool_plan("avg", H, W, self.B if self.bf16 else 4, *spec, bf16=self.bf16)[:2]
         except _lib.BBBHipError:
             raise _NoPlan from None                              # (B % 8 != 0: bf16 storage does not take this batch at all)
         return self.emit("avgpool", i, mod, self.lay, (C, ho, wo, self.B), 1, pool=spec)
@@ -360,11 +365,8 @@ def _chwn_steps(children, x_shape, part, precision, cfg, draws, n_slabs=None):
                     p.lead, p.x_div = p.Es, 1
                 elif isinstance(mod, FlattenLayer):
                     i += p.flatten(i, mod)
-                elif isinstance(mod, nn.MaxPool2d):
-                    k, s = mod.kernel_size, mod.stride
-                    i += p.emit("pool", i, mod, p.lay, (p.chw[0], (p.chw[1] - k) // s + 1, (p.chw[2] - k) // s + 1, p.B), 1)
-                elif pool_desc.is_avgpool(mod):
-                    i += p.avgpool(i, mod)
+                elif pool_desc.is_pool(mod):
+                    i += p.pool(i, mod)
                 else:
                     if p.lay in ("s3", "c8s3"):
                         p.to_f32(i, mod)

@@ -20,7 +20,8 @@ import torch
 
 from . import _lib, rng
 from ._lib import Segment, check, ptr, require_device, cur_stream, on_device
-from .pool_desc import avgpool_bf16_plan, avgpool_of, avgpool_plan, is_avgpool, pool_desc as _pool_desc  # noqa: F401  (ops.avgpool_of, ...)
+from .pool_desc import (avgpool_bf16_plan, avgpool_of, avgpool_plan, is_avgpool, is_maxpool, is_pool, pool_of,  # noqa: F401
+                        pool_plan, pool_desc as _pool_desc)                                    # (ops.pool_of, ops.avgpool_of, ...)
 from .conv_desc import ACT_CODE, _pair, bf16_flags, c8x3_flags, conv_desc, out_map, pool_code, pooled_map, slab_rule  # noqa: F401  (ops.ACT_CODE)
 
 _scratch = {}
@@ -620,7 +621,7 @@ def maxpool_chwn_s3(x, k, s):
     require_device(x, dtype=torch.bfloat16)
     x = x.contiguous()
     E, three, C, H, W, B = x.shape
-    ho, wo = (H - k) // s + 1, (W - k) // s + 1
+    ho, wo = pooled_map(H, W, (k, s))
     y = torch.empty((E, 3, C, ho, wo, B), dtype=torch.bfloat16, device=x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_maxpool_chwn_s3(x.data_ptr(), y.data_ptr(), E, C, H, W, B, int(k), int(s), cur_stream(x.device)),
@@ -813,7 +814,7 @@ def maxpool_c8s3(x, k, s):
     x = x.contiguous()
     E, planes, CG, H, W, B, eight = x.shape
     if planes == 6:
-        ho, wo = (H - k) // s + 1, (W - k) // s + 1
+        ho, wo = pooled_map(H, W, (k, s))
         y = torch.empty((E, 6, CG, ho, wo, B, 8), dtype=torch.bfloat16, device=x.device)
         with on_device(x.device):
             check(_lib.lib().bbb_maxpool_chwn_s3sq(x.data_ptr(), y.data_ptr(), E, CG, H, W, B * 8, int(k), int(s), cur_stream(x.device)),
@@ -947,28 +948,54 @@ def lrt_sample_chwn(act_mu, act_var, draws, seed, call0, stream_id, act=None, b_
     return y
 
 
+# ---- pooling (csrc/pool2d.hip, pool2d_bf16.hip; what a launch checks: csrc/pool_plan.h; what is admitted: bbb_hip/pool_desc.py) ----
+def _planes_of(shape):
+    """(leading dims, H, W, B, planes) of planes [..., H, W, B]: planes = the product of the leading dims."""
+    *lead, H, W, B = shape
+    planes = 1
+    for v in lead:
+        planes *= v
+    return lead, H, W, B, planes
+
+
+def _grad_buffers(like, planes, dtype, pad_planes, pair=False):
+    """The output of a pooling / activation backward over the `planes` planes [*lead, H, W, B] of the contiguous tensor `like`, in
+    `dtype` (None: like's): dense, or (pad_planes) every plane at padded_plane_pitch(H * W * B) -> (buf, out, pitch): what the launch writes, the
+    same as a tensor of like's shape, and the entry's out_plane_pitch (0 = dense).  pair (the LRT forms): two of them one allocation
+    apart -- buf and out carry a leading 2."""
+    shape = like.shape
+    K = shape[-3] * shape[-2] * shape[-1]
+    pitch = padded_plane_pitch(K) if pad_planes else K
+    if pitch == K and not pair:
+        buf = torch.empty_like(like) if dtype is None else torch.empty_like(like, dtype=dtype)
+        return buf, buf, 0
+    dtype = like.dtype if dtype is None else dtype
+    if pair:
+        shape = (2,) + tuple(shape)
+    if pitch == K:
+        buf = torch.empty(shape, dtype=dtype, device=like.device)
+        return buf, buf, 0
+    buf = torch.empty(((2, planes, pitch) if pair else (planes, pitch)), dtype=dtype, device=like.device)
+    return buf, buf[..., :K].view(shape), pitch
+
+
+def _pooled_grad_shape(g_out, planes, H, W, B, avg, bf16=False):
+    """The average-pool backward kernels index g_out by the pooled map: refuse a gradient of any other size before the launch."""
+    ho, wo, _, _ = pool_plan("avg", H, W, B, *avg, planes=max(planes, 1) if bf16 else planes, bf16=bf16)     # (no planes: the fp32 plan refuses)
+    if g_out.numel() != planes * ho * wo * B:
+        raise _lib.BBBHipError("average-pool backward: g_out must hold %d planes of the pooled map %d x %d x %d" % (planes, ho, wo, B))
+
+
 def maxpool_chwn(x, k, s):
     """MaxPool2d(k, s) on [..., H, W, B] (B innermost, B % 4 == 0)."""
     require_device(x)
     x = x.contiguous()
-    *lead, H, W, B = x.shape
-    planes = 1
-    for v in lead:
-        planes *= v
-    ho, wo = (H - k) // s + 1, (W - k) // s + 1
-    y = torch.empty((*lead, ho, wo, B), dtype=torch.float32, device=x.device)
+    lead, H, W, B, planes = _planes_of(x.shape)
+    y = torch.empty((*lead, *pooled_map(H, W, (k, s)), B), dtype=torch.float32, device=x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_maxpool_chwn(x.data_ptr(), y.data_ptr(), planes, H, W, B, int(k), int(s), cur_stream(x.device)),
               "bbb_maxpool_chwn")
     return y
-
-
-# ---- average pooling (csrc/pool2d.hip; what a launch checks: csrc/pool_plan.h; what is admitted: bbb_hip/pool_desc.py) ----
-def _avgpool_grad_shape(g_out, planes, H, W, B, avg):
-    """The backward kernels index g_out by the pooled map: refuse a gradient of any other size before the launch."""
-    ho, wo, _, _ = avgpool_plan(H, W, B, *avg, planes=planes)
-    if g_out.numel() != planes * ho * wo * B:
-        raise _lib.BBBHipError("average-pool backward: g_out must hold %d planes of the pooled map %d x %d x %d" % (planes, ho, wo, B))
 
 
 def avgpool_chwn(x, kernel, stride, padding=0, count_include_pad=True):
@@ -976,10 +1003,7 @@ def avgpool_chwn(x, kernel, stride, padding=0, count_include_pad=True):
     inside the map added in scan order, one IEEE division (bbb_avgpool_chwn)."""
     require_device(x)
     x = x.contiguous()
-    *lead, H, W, B = x.shape
-    planes = 1
-    for v in lead:
-        planes *= v
+    lead, H, W, B, planes = _planes_of(x.shape)
     d = _pool_desc(H, W, B, kernel, stride, padding, count_include_pad)
     ho, wo, _, _ = avgpool_plan(H, W, B, kernel, stride, padding, count_include_pad, planes=max(planes, 1))
     y = torch.empty((*lead, ho, wo, B), dtype=torch.float32, device=x.device)
@@ -1127,7 +1151,7 @@ def bf16_pool_fusion_ok(cin_khkw, tap_major, out_f32, pool_module, x_shape=None,
     pk, pst = ks[0][0], ks[1][0]
     if ho < pk or wo < pk:
         return False
-    rows = int(draws) * -(-B // 256) * ((ho - pk) // pst + 1)
+    rows = int(draws) * -(-B // 256) * pooled_map(ho, wo, (pk, pst))[0]
     cfg = current_config()
     return rows >= (cfg.bf16_pool_fuse_min_rows_overlapped if cfg.launches_overlap else cfg.bf16_pool_fuse_min_rows)
 
@@ -1334,12 +1358,8 @@ def maxpool_chwn_bf16(x, k, s):
     """MaxPool2d(k, s) on bf16 [..., H, W, B] (B % 8 == 0)."""
     require_device(x, dtype=torch.bfloat16)
     x = x.contiguous()
-    *lead, H, W, B = x.shape
-    planes = 1
-    for v in lead:
-        planes *= v
-    ho, wo = (H - k) // s + 1, (W - k) // s + 1
-    y = torch.empty((*lead, ho, wo, B), dtype=torch.bfloat16, device=x.device)
+    lead, H, W, B, planes = _planes_of(x.shape)
+    y = torch.empty((*lead, *pooled_map(H, W, (k, s)), B), dtype=torch.bfloat16, device=x.device)
     with on_device(x.device):
         check(_lib.lib().bbb_maxpool_chwn_bf16(x.data_ptr(), y.data_ptr(), planes, H, W, B, int(k), int(s), cur_stream(x.device)),
               "bbb_maxpool_chwn_bf16")
@@ -1351,10 +1371,7 @@ def avgpool_chwn_bf16(x, kernel, stride, padding=0, count_include_pad=True):
     rounding to bf16 (bbb_avgpool_chwn_bf16)."""
     require_device(x, dtype=torch.bfloat16)
     x = x.contiguous()
-    *lead, H, W, B = x.shape
-    planes = 1
-    for v in lead:
-        planes *= v
+    lead, H, W, B, planes = _planes_of(x.shape)
     d = _pool_desc(H, W, B, kernel, stride, padding, count_include_pad)
     ho, wo, _, _ = avgpool_bf16_plan(H, W, B, kernel, stride, padding, count_include_pad, planes=max(planes, 1))
     y = torch.empty((*lead, ho, wo, B), dtype=torch.bfloat16, device=x.device)
@@ -1960,27 +1977,17 @@ def pool_act_backward_chwn(g_out, y, k, s, act, pad_planes=False, avg=None):
     avg = (kernel, stride, padding, count_include_pad): the pool is that average pool instead (avgpool_act_backward_chwn)."""
     require_device(g_out, y)
     g_out, y = g_out.contiguous(), y.contiguous()
-    *lead, H, W, B = y.shape
-    planes = 1
-    for v in lead:
-        planes *= v
-    K = H * W * B
-    pitch = padded_plane_pitch(K) if pad_planes else K
-    if pitch != K:
-        buf = torch.empty((planes, pitch), dtype=torch.float32, device=y.device)
-        g_pre = buf[:, :K].view(*lead, H, W, B)
-    else:
-        buf = g_pre = torch.empty_like(y)
+    _, H, W, B, planes = _planes_of(y.shape)
+    buf, g_pre, pitch = _grad_buffers(y, planes, None, pad_planes)
     if avg is not None:
-        _avgpool_grad_shape(g_out, planes, H, W, B, avg)
+        _pooled_grad_shape(g_out, planes, H, W, B, avg)
     with on_device(y.device):
         if avg is not None:
             check(_lib.lib().bbb_avgpool_act_bwd_chwn(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(), buf.data_ptr(),
-                                                      planes, ACT_CODE[act], pitch if pitch != K else 0, cur_stream(y.device)),
-                  "bbb_avgpool_act_bwd_chwn")
+                                                      planes, ACT_CODE[act], pitch, cur_stream(y.device)), "bbb_avgpool_act_bwd_chwn")
         else:
             check(_lib.lib().bbb_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), buf.data_ptr(), planes, H, W, B, int(k), int(s),
-                                                   ACT_CODE[act], pitch if pitch != K else 0, cur_stream(y.device)), "bbb_pool_act_bwd_chwn")
+                                                   ACT_CODE[act], pitch, cur_stream(y.device)), "bbb_pool_act_bwd_chwn")
     return g_pre
 
 
@@ -2069,41 +2076,30 @@ def lrt_pool_act_backward_chwn(g_out, y, act_mu, act_var, k, s, act, pad_planes=
         if g2.numel() != g_out.numel() or g_out.numel() % xc.numel() != 0:
             raise _lib.BBBHipError("lrt_pool_act_backward_chwn: combine = (x_out, g_out2) of g_out's shape (x_out may hold one draw)")
         g2p, xcp = g2.data_ptr(), xc.data_ptr()
-    *lead, H, W, B = y.shape
-    planes = 1
-    for v in lead:
-        planes *= v
+    _, H, W, B, planes = _planes_of(y.shape)
     mom_planes = act_mu.numel() // (H * W * B)
     if act_mu.shape != act_var.shape or act_mu.numel() != mom_planes * H * W * B or planes % max(mom_planes, 1) != 0:
         raise _lib.BBBHipError("lrt_pool_act_backward_chwn: act_mu / act_var must hold y's planes, or one draw's worth of them")
-    K = H * W * B
-    pitch = padded_plane_pitch(K) if pad_planes else K
     # the two outputs one allocation apart in every form: a first layer's input gradient reads them as the two draws of one launch
-    if pitch != K:
-        pair = torch.empty((2, planes, pitch), dtype=torch.float32, device=y.device)
-        bufs = [pair[0], pair[1]]
-        outs = [b[:, :K].view(*lead, H, W, B) for b in bufs]
-    else:
-        both = torch.empty((2,) + tuple(y.shape), dtype=torch.float32, device=y.device)
-        bufs = outs = [both[0], both[1]]
+    bufs, outs, pitch = _grad_buffers(y, planes, None, pad_planes, pair=True)
     x_planes = (planes * xc.numel() // g_out.numel()) if combine is not None else 0
     if avg is not None:
-        _avgpool_grad_shape(g_out, planes, H, W, B, avg)
+        _pooled_grad_shape(g_out, planes, H, W, B, avg)
     with on_device(y.device):
         if avg is not None:
             check(_lib.lib().bbb_lrt_avgpool_act_bwd_chwn(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(),
                                                           act_mu.data_ptr(), act_var.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(),
-                                                          planes, mom_planes, ACT_CODE[act], pitch if pitch != K else 0, g2p, xcp,
+                                                          planes, mom_planes, ACT_CODE[act], pitch, g2p, xcp,
                                                           x_planes, cur_stream(y.device)),
                   "bbb_lrt_avgpool_act_bwd_chwn")
         else:
             check(_lib.lib().bbb_lrt_pool_act_bwd_chwn(g_out.data_ptr(), y.data_ptr(), act_mu.data_ptr(), act_var.data_ptr(),
                                                        bufs[0].data_ptr(), bufs[1].data_ptr(), planes, mom_planes, H, W, B, int(k), int(s),
-                                                       ACT_CODE[act], pitch if pitch != K else 0, g2p, xcp, x_planes,
+                                                       ACT_CODE[act], pitch, g2p, xcp, x_planes,
                                                        cur_stream(y.device)),
                   "bbb_lrt_pool_act_bwd_chwn")
-    if stacked and pitch == K:
-        return both
+    if stacked and pitch == 0:
+        return outs
     return outs[0], outs[1]
 
 
@@ -2512,15 +2508,17 @@ def first_layer_input_grad(g_pre, w, x_hw, stride, padding, dilation, x_lrt=None
 
 # ---- bf16 training backward (fast_train._MCForwardBF16._backward on fast_train._Schedule) ---------------
 
-def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=False):
+def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=False, avg=None):
     """pool_act_backward_chwn on bf16 storage (bbb_pool_act_bwd_chwn_bf16): y = the stored bf16 activated output [..., H, W, B],
     g_out the bf16 (or, the logits layer's, fp32) gradient w.r.t. the (pooled) output -> g_pre = act'(y) * route(g_out) in fp32,
     rounded once to bf16.  out_f32: the rounded values as fp32 (the first layer's fp32 weight gradient), pad_planes as there.
-    y = None (k = 0, no activation): the rounding of g_out alone (the logits layer, whose output is fp32)."""
+    y = None (k = 0, no activation): the rounding of g_out alone (the logits layer, whose output is fp32).
+    avg = (kernel, stride, padding, count_include_pad): the pool is that average pool instead (avgpool_act_backward_chwn_bf16)."""
+    name = "pool_act_backward_chwn_bf16" if avg is None else "avgpool_act_backward_chwn_bf16"
     if g_out.dtype not in (torch.float32, torch.bfloat16):
-        raise _lib.BBBHipError("pool_act_backward_chwn_bf16: g_out must be bf16 or fp32")
+        raise _lib.BBBHipError(name + ": g_out must be bf16 or fp32")
     require_device(g_out, dtype=g_out.dtype)
-    if y is None:
+    if y is None and avg is None:
         if int(k) != 0 or act is not None:
             raise _lib.BBBHipError("pool_act_backward_chwn_bf16: pooling / activation backward needs the stored output y")
     else:
@@ -2528,23 +2526,20 @@ def pool_act_backward_chwn_bf16(g_out, y, k, s, act, out_f32=False, pad_planes=F
         y = y.contiguous()
     g_out = g_out.contiguous()
     shape = tuple(g_out.shape) if y is None else tuple(y.shape)
-    *lead, H, W, B = shape
-    planes = 1
-    for v in lead:
-        planes *= v
-    K = H * W * B
-    pitch = padded_plane_pitch(K) if pad_planes else K
-    dt = torch.float32 if out_f32 else torch.bfloat16
-    if pitch != K:
-        buf = torch.empty((planes, pitch), dtype=dt, device=g_out.device)
-        g_pre = buf[:, :K].view(*lead, H, W, B)
-    else:
-        buf = g_pre = torch.empty(shape, dtype=dt, device=g_out.device)
+    _, H, W, B, planes = _planes_of(shape)
+    if avg is not None:
+        _pooled_grad_shape(g_out, planes, H, W, B, avg, bf16=True)
+    buf, g_pre, pitch = _grad_buffers(g_out if y is None else y, planes, torch.float32 if out_f32 else torch.bfloat16, pad_planes)
     flags = (1 if g_out.dtype == torch.float32 else 0) | (2 if out_f32 else 0)
     with on_device(g_out.device):
-        check(_lib.lib().bbb_pool_act_bwd_chwn_bf16(g_out.data_ptr(), ptr(y), buf.data_ptr(), planes, H, W, B, int(k), int(s),
-                                                    ACT_CODE[act], pitch if pitch != K else 0, flags, cur_stream(g_out.device)),
-              "bbb_pool_act_bwd_chwn_bf16")
+        if avg is not None:
+            check(_lib.lib().bbb_avgpool_act_bwd_chwn_bf16(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(),
+                                                           buf.data_ptr(), planes, ACT_CODE[act], pitch, flags, cur_stream(g_out.device)),
+                  "bbb_avgpool_act_bwd_chwn_bf16")
+        else:
+            check(_lib.lib().bbb_pool_act_bwd_chwn_bf16(g_out.data_ptr(), ptr(y), buf.data_ptr(), planes, H, W, B, int(k), int(s),
+                                                        ACT_CODE[act], pitch, flags, cur_stream(g_out.device)),
+                  "bbb_pool_act_bwd_chwn_bf16")
     return g_pre
 
 
@@ -2552,34 +2547,8 @@ def avgpool_act_backward_chwn_bf16(g_out, y, kernel, stride, padding, count_incl
     """pool_act_backward_chwn_bf16 behind an AvgPool2d(kernel, stride, padding, count_include_pad=) (bbb_avgpool_act_bwd_chwn_bf16):
     every tap of a window receives that window's gradient over its divisor (fp32, windows in ascending order), times act'(y) from the
     stored bf16 y [..., H, W, B], rounded once to bf16.  g_out bf16 or fp32, of the pooled size; out_f32 / pad_planes as there."""
-    if g_out.dtype not in (torch.float32, torch.bfloat16):
-        raise _lib.BBBHipError("avgpool_act_backward_chwn_bf16: g_out must be bf16 or fp32")
-    require_device(g_out, dtype=g_out.dtype)
-    require_device(y, dtype=torch.bfloat16)
-    y, g_out = y.contiguous(), g_out.contiguous()
-    *lead, H, W, B = y.shape
-    planes = 1
-    for v in lead:
-        planes *= v
-    avg = (kernel, stride, padding, count_include_pad)
-    ho, wo, _, _ = avgpool_bf16_plan(H, W, B, *avg, planes=max(planes, 1))
-    if g_out.numel() != planes * ho * wo * B:
-        raise _lib.BBBHipError("average-pool backward: g_out must hold %d planes of the pooled map %d x %d x %d" % (planes, ho, wo, B))
-    K = H * W * B
-    pitch = padded_plane_pitch(K) if pad_planes else K
-    dt = torch.float32 if out_f32 else torch.bfloat16
-    if pitch != K:
-        buf = torch.empty((planes, pitch), dtype=dt, device=g_out.device)
-        g_pre = buf[:, :K].view(*lead, H, W, B)
-    else:
-        buf = g_pre = torch.empty(tuple(y.shape), dtype=dt, device=g_out.device)
-    flags = (1 if g_out.dtype == torch.float32 else 0) | (2 if out_f32 else 0)
-    with on_device(g_out.device):
-        check(_lib.lib().bbb_avgpool_act_bwd_chwn_bf16(ctypes.byref(_pool_desc(H, W, B, *avg)), g_out.data_ptr(), y.data_ptr(),
-                                                       buf.data_ptr(), planes, ACT_CODE[act], pitch if pitch != K else 0, flags,
-                                                       cur_stream(g_out.device)),
-              "bbb_avgpool_act_bwd_chwn_bf16")
-    return g_pre
+    return pool_act_backward_chwn_bf16(g_out, y, 0, 1, act, out_f32=out_f32, pad_planes=pad_planes,
+                                       avg=(kernel, stride, padding, count_include_pad))
 
 
 def plane_sums_bf16(g):

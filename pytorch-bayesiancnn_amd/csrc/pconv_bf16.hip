@@ -1483,43 +1483,6 @@ int launch_dgrad_shape(const PConvArgs& a, int shape, int kgs, bool ws, int64_t 
     return kgs == 2 ? launch_tr<1, 2, 2, false>(a, blocks, st) : launch_tr<1, 2, 1, false>(a, blocks, st);
 }
 
-// maxpool over [planes][H][W][B] bf16, 8 images per thread (bf16 order = fp32 order of the widened values: exact)
-__global__ __launch_bounds__(256) void maxpool_chwn_bf16_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t total8,
-                                                                int H, int W, int Ho, int Wo, int B8, int k, int s) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total8) return;
-    const int b8 = (int)(i % B8);
-    int64_t t = i / B8;
-    const int ow = (int)(t % Wo);
-    t /= Wo;
-    const int oh = (int)(t % Ho);
-    const int64_t pl = t / Ho;
-    const u32x4* xp = x + ((pl * H + (int64_t)oh * s) * W + (int64_t)ow * s) * B8 + b8;
-    float m[8];
-    {
-        const u32x4 v = xp[0];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            m[2 * u] = __builtin_bit_cast(float, v[u] << 16);
-            m[2 * u + 1] = __builtin_bit_cast(float, v[u] & 0xFFFF0000u);
-        }
-    }
-    for (int a = 0; a < k; ++a)
-        for (int c = 0; c < k; ++c) {
-            const u32x4 v = xp[((int64_t)a * W + c) * B8];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                m[2 * u] = fmaxf(m[2 * u], __builtin_bit_cast(float, v[u] << 16));
-                m[2 * u + 1] = fmaxf(m[2 * u + 1], __builtin_bit_cast(float, v[u] & 0xFFFF0000u));
-            }
-        }
-    u32x4 o;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-        o[u] = (__builtin_bit_cast(uint32_t, m[2 * u]) >> 16) | (__builtin_bit_cast(uint32_t, m[2 * u + 1]) & 0xFFFF0000u);
-    y[i] = o;
-}
-
 // fp32 NCHW [B][C][H][W] -> bf16 [C][H][W][B]: 32x32 tile transpose through LDS (planes = C*H*W)
 __global__ __launch_bounds__(256) void nchw_to_chwn_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int B, int P) {
     __shared__ float tile[32][33];
@@ -1617,19 +1580,6 @@ extern "C" int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* 
     a.tstep_h = p.tstep_h; a.tstep_w = p.tstep_w;
     a.Ntiles = p.grid.Ntiles; a.G = p.grid.G; a.nbt = p.grid.nbt; a.Mtiles = p.grid.Mtiles; a.per_xcd = p.grid.per_xcd;
     return launch_dgrad_shape(a, p.tile.shape, p.tile.kgs, p.tile.ws, p.grid.blocks, (hipStream_t)stream);
-}
-
-extern "C" int bbb_maxpool_chwn_bf16(const void* x, void* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream) {
-    if (x == nullptr || y == nullptr || planes <= 0 || h <= 0 || w <= 0 || batch <= 0 || k <= 0 || s <= 0) return BBB_EINVAL;
-    if (batch % 8 != 0 || h < k || w < k) return BBB_ESHAPE;
-    if ((((uintptr_t)x | (uintptr_t)y) & 15u) != 0) return BBB_EALIGN;
-    const int ho = (h - k) / s + 1, wo = (w - k) / s + 1;
-    const int64_t total8 = planes * ho * wo * (batch / 8);
-    const int64_t blocks = (total8 + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    hipLaunchKernelGGL(maxpool_chwn_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const u32x4*>(x), reinterpret_cast<u32x4*>(y), total8, h, w, ho, wo, batch / 8, k, s);
-    return (int)hipGetLastError();
 }
 
 extern "C" int bbb_nchw_to_chwn_bf16(const float* x, void* y, int batch, int64_t plane, void* stream) {

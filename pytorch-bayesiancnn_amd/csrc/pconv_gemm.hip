@@ -29,7 +29,6 @@
 #include "pconv_body.cuh"
 #include "pconv_bf16x3.cuh"
 #include "pconv_plan.h"
-#include "pool_act_bwd.cuh"
 
 namespace {
 
@@ -82,87 +81,6 @@ __global__ __launch_bounds__(kThreads) void pconv_gemm_splitk_kernel(const PConv
     if (blk >= blk_end || blk >= (int64_t)p.G * p.Mtiles * p.ksplit) return;
     const int64_t item = blk / p.ksplit;
     pconv_item<BM, LRT, ILV, kSplit>(p, item, (int)(blk - item * p.ksplit));
-}
-
-// maxpool over [planes][H][W][B] (planes = draws * channels), B innermost; 4 images per thread.
-__global__ __launch_bounds__(256) void maxpool_chwn_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t total4,
-                                                           int H, int W, int Ho, int Wo, int B4, int k, int s) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total4) return;
-    const int b4 = (int)(i % B4);
-    int64_t t = i / B4;
-    const int ow = (int)(t % Wo);
-    t /= Wo;
-    const int oh = (int)(t % Ho);
-    const int64_t pl = t / Ho;
-    const f32x4* xp = reinterpret_cast<const f32x4*>(x) + ((pl * H + (int64_t)oh * s) * W + (int64_t)ow * s) * B4 + b4;
-    f32x4 m = xp[0];
-    for (int a = 0; a < k; ++a)
-        for (int c = 0; c < k; ++c) {
-            const f32x4 v = xp[((int64_t)a * W + c) * B4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) m[u] = fmaxf(m[u], v[u]);
-        }
-    reinterpret_cast<f32x4*>(y)[i] = m;
-}
-
-// Backward of [activation -> MaxPool2d(k, s)] (or of the activation alone, k = 0) in the batch-innermost layout -- training
-// extension.  Gather form, one thread per (plane, h, w, 4 images) of the layer's activated output y:
-//   g_act(h, w) = sum over the pooling windows that contain (h, w) of g_out(window) if (h, w) is that window's FIRST maximum
-//                 in scan order (torch's max_pool2d backward routes the gradient to the first argmax), else 0;
-//   g_pre = g_act * act'(pre-activation), written from y alone: Softplus' = sigmoid(v) = 1 - exp(-y), ReLU' = [y > 0].
-// Overlapping windows (k > s: Bayesian3Conv3FC pools 3x3 / 2) make up to ceil(k/s)^2 windows per element; nothing is
-// scattered, so no atomics and a deterministic result.
-// LRT layers (am != NULL): the layer's output was act(act_mu + sqrt(act_var) * eps), so besides g_pre (= the gradient w.r.t.
-// act_mu) the same pass writes the gradient w.r.t. act_var, g_pre * (v - act_mu) / (2 act_var), with the pre-activation v
-// recovered from the stored activated output (softplus: y + log(1 - exp(-y)); nothing flows where ReLU clipped).  act_mu /
-// act_var hold mom_planes planes: all of them, or one draw's worth when every draw shares one pair of moments (first layer).
-__global__ __launch_bounds__(256) void pool_act_bwd_chwn_kernel(const float* __restrict__ g_out, const float* __restrict__ y,
-                                                                float* __restrict__ g_pre, int64_t total4, int H, int W, int Hp,
-                                                                int Wp, int B4, int k, int s, int act, int64_t out_pitch4,
-                                                                const float* __restrict__ am, const float* __restrict__ av,
-                                                                float* __restrict__ g_var, int64_t mom_planes,
-                                                                const float* __restrict__ g2, const float* __restrict__ xc,
-                                                                int64_t xc_total4) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total4) return;
-    // (the incoming gradient and everything behind the routed gradient: pool_act_bwd.cuh, shared with the average-pool routing)
-    auto incoming = [&](int64_t idx) { return pool_bwd::incoming(g_out, g2, xc, xc_total4, idx); };
-    const int b4 = (int)(i % B4);
-    int64_t t = i / B4;
-    const int w = (int)(t % W);
-    t /= W;
-    const int h = (int)(t % H);
-    const int64_t pl = t / H;
-    const f32x4* yp = reinterpret_cast<const f32x4*>(y) + pl * H * W * B4 + b4;
-    const f32x4 me = yp[((int64_t)h * W + w) * B4];
-    f32x4 g = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (k == 0) {
-        g = incoming(i);
-    } else {
-        const int64_t gbase = pl * Hp * Wp * B4 + b4;
-        // windows (ph, pw) with ph*s <= h < ph*s + k
-        const int ph_lo = h - k + 1 > 0 ? (h - k + 1 + s - 1) / s : 0, ph_hi = h / s < Hp - 1 ? h / s : Hp - 1;
-        const int pw_lo = w - k + 1 > 0 ? (w - k + 1 + s - 1) / s : 0, pw_hi = w / s < Wp - 1 ? w / s : Wp - 1;
-        for (int ph = ph_lo; ph <= ph_hi; ++ph)
-            for (int pw = pw_lo; pw <= pw_hi; ++pw) {
-                // am I the first maximum of this window?  (an earlier element >= me, or a later one > me, disqualifies)
-                bool first[4] = {true, true, true, true};
-                const int my = (h - ph * s) * k + (w - pw * s);
-                for (int a = 0; a < k; ++a)
-                    for (int c = 0; c < k; ++c) {
-                        const int idx = a * k + c;
-                        if (idx == my) continue;
-                        const f32x4 v = yp[((int64_t)(ph * s + a) * W + (pw * s + c)) * B4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) first[u] = first[u] && (idx < my ? v[u] < me[u] : v[u] <= me[u]);
-                    }
-                const f32x4 go = incoming(gbase + ((int64_t)ph * Wp + pw) * B4);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) g[u] += first[u] ? go[u] : 0.0f;
-            }
-    }
-    pool_bwd::act_epilogue(g, me, act, i, pl, (int64_t)H * W * B4, out_pitch4, g_pre, am, av, g_var, mom_planes);
 }
 
 // the descriptor checks (pconv_plan.h, describe) -> the kernel-argument block
@@ -485,59 +403,4 @@ extern "C" int bbb_lrt_conv2d_chwn_fwd(const bbb_conv_desc_t* d, const float* x,
                                        uint32_t stream_id, int sample, const uint32_t* call_dev, void* stream) {
     return bbb_lrt_conv2d_chwn_splitk_fwd(d, x, w_mu, w_var, b_mu, b_var, y, act_mu_out, act_var_out, eps_ext, seed, call0, stream_id,
                                           sample, call_dev, 1, nullptr, 0, stream);
-}
-
-extern "C" int bbb_maxpool_chwn(const float* x, float* y, int64_t planes, int h, int w, int batch, int k, int s, void* stream) {
-    if (x == nullptr || y == nullptr || planes <= 0 || h <= 0 || w <= 0 || batch <= 0 || k <= 0 || s <= 0) return BBB_EINVAL;
-    if (batch % 4 != 0 || h < k || w < k) return BBB_ESHAPE;
-    if ((((uintptr_t)x | (uintptr_t)y) & 15u) != 0) return BBB_EALIGN;
-    const int ho = (h - k) / s + 1, wo = (w - k) / s + 1;
-    const int64_t total4 = planes * ho * wo * (batch / 4);
-    const int64_t blocks = (total4 + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    hipLaunchKernelGGL(maxpool_chwn_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, y, total4, h, w, ho, wo,
-                       batch / 4, k, s);
-    return (int)hipGetLastError();
-}
-
-namespace {
-int pool_act_bwd_launch(const float* g_out, const float* y, float* g_pre, int64_t planes, int h, int w, int batch, int k, int s, int act,
-                        int64_t out_plane_pitch, const float* am, const float* av, float* g_var, int64_t mom_planes, void* stream,
-                        const float* g2 = nullptr, const float* xc = nullptr, int64_t xc_planes = 0) {
-    if (g_out == nullptr || y == nullptr || g_pre == nullptr || planes <= 0 || h <= 0 || w <= 0 || batch <= 0 || k < 0 ||
-        (k > 0 && s <= 0) || act < 0 || act > 2)
-        return BBB_EINVAL;
-    if (batch % 4 != 0 || (k > 0 && (h < k || w < k))) return BBB_ESHAPE;
-    if ((((uintptr_t)g_out | (uintptr_t)y | (uintptr_t)g_pre) & 15u) != 0) return BBB_EALIGN;
-    if (out_plane_pitch != 0 && (out_plane_pitch < (int64_t)h * w * batch || out_plane_pitch % 4 != 0)) return BBB_EINVAL;
-    const int hp = k > 0 ? (h - k) / s + 1 : h, wp = k > 0 ? (w - k) / s + 1 : w;
-    const int64_t total4 = planes * h * w * (batch / 4);
-    const int64_t blocks = (total4 + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    if ((g2 == nullptr) != (xc == nullptr)) return BBB_EINVAL;
-    if (g2 != nullptr) {
-        if (xc_planes <= 0 || planes % xc_planes != 0) return BBB_EINVAL;
-        if ((((uintptr_t)g2 | (uintptr_t)xc) & 15u) != 0) return BBB_EALIGN;
-    }
-    hipLaunchKernelGGL(pool_act_bwd_chwn_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g_out, y, g_pre, total4, h, w,
-                       hp, wp, batch / 4, k, s, act, out_plane_pitch / 4, am, av, g_var, mom_planes, g2, xc,
-                       g2 != nullptr ? xc_planes * hp * wp * (batch / 4) : (int64_t)1);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-extern "C" int bbb_pool_act_bwd_chwn(const float* g_out, const float* y, float* g_pre, int64_t planes, int h, int w, int batch,
-                                     int k, int s, int act, int64_t out_plane_pitch, void* stream) {
-    return pool_act_bwd_launch(g_out, y, g_pre, planes, h, w, batch, k, s, act, out_plane_pitch, nullptr, nullptr, nullptr, 1, stream);
-}
-
-extern "C" int bbb_lrt_pool_act_bwd_chwn(const float* g_out, const float* y, const float* act_mu, const float* act_var, float* g_mu,
-                                         float* g_var, int64_t planes, int64_t moment_planes, int h, int w, int batch, int k, int s,
-                                         int act, int64_t out_plane_pitch, const float* g_out2, const float* x_out, int64_t x_planes,
-                                         void* stream) {
-    if (act_mu == nullptr || act_var == nullptr || g_var == nullptr) return BBB_EINVAL;
-    if (moment_planes <= 0 || planes % moment_planes != 0) return BBB_EINVAL;
-    if ((((uintptr_t)act_mu | (uintptr_t)act_var | (uintptr_t)g_var) & 15u) != 0) return BBB_EALIGN;
-    return pool_act_bwd_launch(g_out, y, g_mu, planes, h, w, batch, k, s, act, out_plane_pitch, act_mu, act_var, g_var, moment_planes,
-                               stream, g_out2, x_out, x_planes);
 }

@@ -1,16 +1,28 @@
-// What the backward passes of [activation -> pooling] share, whatever the pooling routes (pool_act_bwd_chwn_kernel of
-// pconv_gemm.hip: the first maximum; avgpool_act_bwd_chwn_kernel of pool2d.hip: every tap, divided): how the incoming gradient is
-// read, and everything behind the routed gradient g_act -- the activation's derivative from the stored activated output, the
-// padded-pitch store, the LRT split into the gradients w.r.t. act_mu and act_var.  One thread per (plane, h, w, 4 images).
+// What the pooling kernels of pool2d.hip (fp32 planes) and pool2d_bf16.hip (bf16 planes) share on the device: the rows a window
+// covers, and for the backward passes of [activation -> pooling], whatever the pooling routes (pool_act_bwd_*: the first maximum;
+// avgpool_act_bwd_*: every tap, divided): how the incoming gradient is read, and everything behind the routed gradient g_act -- the
+// activation's derivative from the stored activated output, the padded-pitch store, on fp32 planes the LRT split into the gradients
+// w.r.t. act_mu and act_var.  (The bf16 kernels keep their ends -- act', the one rounding, the store -- written out: as a shared
+// device function the same lines compile to other, slower instructions, profiles/pool_home_notes.md.)  One thread per (plane, h, w, 16-byte group of images).
 #ifndef BBB_POOL_ACT_BWD_CUH
 #define BBB_POOL_ACT_BWD_CUH
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_pack.cuh"
+
 namespace pool_bwd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using bf16_pack::f32x4;
+using bf16_pack::u32x4;
+
+// the rows (columns) of the map that window o covers: [lo, hi), never empty (2 * pad <= k, pool_plan.h)
+__device__ __forceinline__ void window(int o, int s, int p, int k, int n, int& lo, int& hi) {
+    const int a = o * s - p;
+    lo = a > 0 ? a : 0;
+    hi = a + k < n ? a + k : n;
+}
 
 // The incoming gradient of 16-byte group idx.  g2 != NULL (an LRT layer below another one): it is g_out + 2 * xc * g2 -- the two
 // input gradients of the layer above combined on the fly (bbb_lrt_glue mode 1's fmaf, bit for bit) instead of by a launch of its own
@@ -55,6 +67,21 @@ __device__ __forceinline__ void act_epilogue(const f32x4 g, const f32x4 me, int 
             gv[u] = (o[u] * t) / (2.0f * v4[u]);
         }
         reinterpret_cast<f32x4*>(g_var)[oi] = gv;
+    }
+}
+
+// ---- bf16 planes: 8 images per 16-byte group, every value fp32 in registers ----
+
+// The incoming gradient of group idx: fp32 (G_F32: two 16-byte vectors; the logits layer's, from bbb_elbo_cb_bwd) or bf16.
+template <bool G_F32>
+__device__ __forceinline__ void incoming8(const void* g_out, int64_t idx, float (&gv)[8]) {
+    if (G_F32) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(g_out) + 2 * idx;
+        const f32x4 a = p[0], b = p[1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { gv[u] = a[u]; gv[4 + u] = b[u]; }
+    } else {
+        bf16_pack::unpack8(reinterpret_cast<const u32x4*>(g_out)[idx], gv);
     }
 }
 

@@ -1,7 +1,5 @@
 // The bf16 training backward's glue (training extension, bf16 storage mode): everything around the
 // gradient contractions, which themselves run on the bf16 forward GEMM (bbb_conv2d_chwn_bf16_fwd):
-//   * pooling + activation backward from the stored bf16 activated output, rounded once to bf16 (or kept as the fp32 values of
-//     that rounding for a first layer's fp32 weight gradient),
 //   * per-plane sums of a bf16 tensor (bias gradients, fp32 accumulation),
 //   * the flipped, channel-transposed bf16 weight rows of an input gradient (dgrad operand at the bf16 GEMM's row pitch),
 //   * [E][C][P][B] -> [E][B][P][Cpad] (the input of a role-swapped weight gradient; pad channels zero),
@@ -11,99 +9,11 @@
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "bf16_pack.cuh"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bf2f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
-
-__device__ __forceinline__ uint32_t f2bf(float v) {             // round to nearest even (v_cvt_pk_bf16_f32)
-    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)v);
-}
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        o[2 * j] = bf2f(v[j] & 0xFFFFu);
-        o[2 * j + 1] = bf2f(v[j] >> 16);
-    }
-}
-
-// g_pre = act'(y) * route(g) for 8 images per thread.  route: the sum (fp32, windows in scan order) of the incoming gradients of
-// every pooling window whose FIRST maximum (torch's max_pool2d backward) is this element, compared on the stored bf16 values;
-// act': ReLU [y > 0], Softplus 1 - exp(-y) (1 above the threshold 20), from the stored bf16 y.  One rounding to bf16 at the end
-// (OUT_F32: the rounded values written as fp32, for the fp32 first-layer weight gradient).  G_F32: the incoming gradient is fp32
-// (the logits layer's, from bbb_elbo_cb_bwd), else bf16.
-template <bool G_F32, bool OUT_F32>
-__global__ __launch_bounds__(256) void pool_act_bwd_bf16_kernel(const void* __restrict__ g_out, const u32x4* __restrict__ y,
-                                                                void* __restrict__ g_pre, int64_t total8, int H, int W, int Hp, int Wp,
-                                                                int B8, int k, int s, int act, int64_t out_pitch8) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total8) return;
-    auto incoming = [&](int64_t idx, float (&gv)[8]) {
-        if (G_F32) {
-            const f32x4* p = reinterpret_cast<const f32x4*>(g_out) + 2 * idx;
-            const f32x4 a = p[0], b = p[1];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { gv[u] = a[u]; gv[4 + u] = b[u]; }
-        } else {
-            unpack8(reinterpret_cast<const u32x4*>(g_out)[idx], gv);
-        }
-    };
-    const int b8 = (int)(i % B8);
-    int64_t t = i / B8;
-    const int w = (int)(t % W);
-    t /= W;
-    const int h = (int)(t % H);
-    const int64_t pl = t / H;
-    const u32x4* yp = y + pl * H * W * B8 + b8;
-    float me[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (y != nullptr) unpack8(yp[((int64_t)h * W + w) * B8], me);      // (no y: k == 0 and no activation -- a rounding only)
-    float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (k == 0) {
-        incoming(i, g);
-    } else {
-        const int64_t gbase = pl * Hp * Wp * B8 + b8;
-        const int ph_lo = h - k + 1 > 0 ? (h - k + 1 + s - 1) / s : 0, ph_hi = h / s < Hp - 1 ? h / s : Hp - 1;
-        const int pw_lo = w - k + 1 > 0 ? (w - k + 1 + s - 1) / s : 0, pw_hi = w / s < Wp - 1 ? w / s : Wp - 1;
-        for (int ph = ph_lo; ph <= ph_hi; ++ph)
-            for (int pw = pw_lo; pw <= pw_hi; ++pw) {
-                bool first[8] = {true, true, true, true, true, true, true, true};
-                const int my = (h - ph * s) * k + (w - pw * s);
-                for (int a = 0; a < k; ++a)
-                    for (int c = 0; c < k; ++c) {
-                        const int idx = a * k + c;
-                        if (idx == my) continue;
-                        float v[8];
-                        unpack8(yp[((int64_t)(ph * s + a) * W + (pw * s + c)) * B8], v);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) first[u] = first[u] && (idx < my ? v[u] < me[u] : v[u] <= me[u]);
-                    }
-                float go[8];
-                incoming(gbase + ((int64_t)ph * Wp + pw) * B8, go);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) g[u] += first[u] ? go[u] : 0.0f;
-            }
-    }
-    uint32_t r[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        float d = 1.0f;
-        if (act == 1) d = me[u] > 0.0f ? 1.0f : 0.0f;
-        else if (act == 2) d = me[u] > 20.0f ? 1.0f : -expm1f(-me[u]);
-        r[u] = f2bf(g[u] * d);
-    }
-    const int64_t oi = out_pitch8 ? pl * out_pitch8 + (i - pl * (int64_t)H * W * B8) : i;
-    if (OUT_F32) {
-        f32x4* o = reinterpret_cast<f32x4*>(g_pre) + 2 * oi;
-        o[0] = f32x4{bf2f(r[0]), bf2f(r[1]), bf2f(r[2]), bf2f(r[3])};
-        o[1] = f32x4{bf2f(r[4]), bf2f(r[5]), bf2f(r[6]), bf2f(r[7])};
-    } else {
-        reinterpret_cast<u32x4*>(g_pre)[oi] = u32x4{r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16)};
-    }
-}
+using namespace bf16_pack;
 
 // out[r] = sum over j < cols of x[r * row_pitch + j] (bf16 in, fp32 out).  One 256-thread block per row: every thread walks
 // 16-byte vectors at a stride of 256 (pairwise within a vector, then in index order), then a fixed LDS tree.
@@ -207,31 +117,6 @@ __global__ __launch_bounds__(256) void batch_chunks_bf16_kernel(const u32x4* __r
 }
 
 }  // namespace
-
-extern "C" int bbb_pool_act_bwd_chwn_bf16(const void* g_out, const void* y, void* g_pre, int64_t planes, int h, int w, int batch, int k,
-                                          int s, int act, int64_t out_plane_pitch, uint32_t flags, void* stream) {
-    if (g_out == nullptr || g_pre == nullptr || (y == nullptr && (k != 0 || act != 0)) || planes <= 0 || h <= 0 || w <= 0 || batch <= 0 || k < 0 || act < 0 ||
-        act > 2 || (k > 0 && s <= 0))
-        return BBB_EINVAL;
-    if ((flags & ~(BBB_BF16_BWD_G_F32 | BBB_BF16_BWD_OUT_F32)) != 0) return BBB_EINVAL;
-    if (batch % 8 != 0 || (k > 0 && (h < k || w < k))) return BBB_ESHAPE;
-    if ((((uintptr_t)g_out | (uintptr_t)y | (uintptr_t)g_pre) & 15u) != 0) return BBB_EALIGN;
-    if (out_plane_pitch != 0 && (out_plane_pitch < (int64_t)h * w * batch || out_plane_pitch % 8 != 0)) return BBB_EINVAL;
-    const int hp = k > 0 ? (h - k) / s + 1 : h, wp = k > 0 ? (w - k) / s + 1 : w;
-    const int64_t total8 = planes * h * w * (batch / 8);
-    const int64_t blocks = (total8 + 255) / 256;
-    if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
-    const bool gf = (flags & BBB_BF16_BWD_G_F32) != 0, of = (flags & BBB_BF16_BWD_OUT_F32) != 0;
-    const u32x4* yv = reinterpret_cast<const u32x4*>(y);
-    const dim3 grid((unsigned)blocks), blk(256);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t p8 = out_plane_pitch / 8;
-    if (gf && of) hipLaunchKernelGGL((pool_act_bwd_bf16_kernel<true, true>), grid, blk, 0, st, g_out, yv, g_pre, total8, h, w, hp, wp, batch / 8, k, s, act, p8);
-    else if (gf) hipLaunchKernelGGL((pool_act_bwd_bf16_kernel<true, false>), grid, blk, 0, st, g_out, yv, g_pre, total8, h, w, hp, wp, batch / 8, k, s, act, p8);
-    else if (of) hipLaunchKernelGGL((pool_act_bwd_bf16_kernel<false, true>), grid, blk, 0, st, g_out, yv, g_pre, total8, h, w, hp, wp, batch / 8, k, s, act, p8);
-    else hipLaunchKernelGGL((pool_act_bwd_bf16_kernel<false, false>), grid, blk, 0, st, g_out, yv, g_pre, total8, h, w, hp, wp, batch / 8, k, s, act, p8);
-    return (int)hipGetLastError();
-}
 
 extern "C" int bbb_plane_sum_bf16(const void* x, float* out, int64_t rows, int64_t cols, int64_t row_pitch, void* stream) {
     if (x == nullptr || out == nullptr || rows <= 0 || cols <= 0 || row_pitch < cols) return BBB_EINVAL;

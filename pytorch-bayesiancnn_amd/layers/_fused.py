@@ -175,8 +175,8 @@ def hooked_chain(wrapper, x, scope):
     lrt_conv2d_layer: batch-innermost GEMM, plain fmaf chain; torch activations; HIP pooling) -- bit for bit that path's results --
     but the layout transposes around every layer are gone: only a module that carries a hook gets its input and output as the
     NCHW tensors the hook expects (and may replace).  ~19 launches per forward instead of ~35 (the path is host-bound).
-    Applies to: a flat wrapper of Bayesian conv / linear layers, ReLU / Softplus(1, 20), MaxPool2d (no padding, floor), the average
-    pools of ops.avgpool_of and a FlattenLayer that keeps one row per image; a 4-d fp32 GPU batch with B % 4 == 0; no autograd; plain hooks (no kwargs hooks, no
+    Applies to: a flat wrapper of Bayesian conv / linear layers, ReLU / Softplus(1, 20), the pools of ops.pool_of (MaxPool2d without
+    padding in floor mode, the average pools) and a FlattenLayer that keeps one row per image; a 4-d fp32 GPU batch with B % 4 == 0; no autograd; plain hooks (no kwargs hooks, no
     global hooks); every layer's weights presampled by enter().  Returns the output, or None (-> the module-by-module loop)."""
     import torch.nn as nn
     import torch.nn.functional as F
@@ -263,14 +263,12 @@ def hooked_chain(wrapper, x, scope):
                 t = st["chwn"] if st["chwn"] is not None else st["nchw"]
                 r = F.softplus(t, m.beta, m.threshold)
                 put(chwn_t=r) if st["chwn"] is not None else put(nchw_t=r)
-            elif isinstance(m, nn.MaxPool2d):
-                put(chwn_t=ops.maxpool_chwn(chwn(), m.kernel_size, m.stride if m.stride is not None else m.kernel_size))
-            elif ops.is_avgpool(m):
+            elif ops.is_pool(m):
                 h = chwn()
-                spec = ops.avgpool_of(m, h.shape[2], h.shape[3])
+                spec = ops.pool_of(m, h.shape[2], h.shape[3])
                 if spec is None:
-                    raise RuntimeError("hooked_chain: an average pool the batched path does not take slipped through the checks")
-                put(chwn_t=ops.avgpool_chwn(h, *spec))
+                    raise RuntimeError("hooked_chain: a pool the batched path does not take slipped through the checks")
+                put(chwn_t=(ops.maxpool_chwn if spec.kind == "max" else ops.avgpool_chwn)(h, *spec))
             elif isinstance(m, FlattenLayer):
                 h = chwn()
                 if h.shape[1] * h.shape[2] * h.shape[3] != m.num_features:

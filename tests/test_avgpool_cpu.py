@@ -43,6 +43,7 @@ def test_entries_are_exported_declared_and_bound(lib):
     for name in ENTRIES:
         assert name in lib.EXPORTS and hasattr(h, name) and name in decl, name
     assert re.search(r"^#define BBB_POOL_AVG 1\b", header, flags=re.M) and lib.POOL_AVG == 1
+    assert re.search(r"^#define BBB_POOL_MAX 2\b", header, flags=re.M) and lib.POOL_MAX == 2
     assert h.bbb_avgpool_plan(None, 1, 0, None, None, None, None) == EINVAL
 
 
@@ -325,7 +326,10 @@ def test_bf16_refusals_name_average_pooling(lib, monkeypatch):
 # ---- 6. the plan header alone under the sanitizers ----
 def test_pool_plan_walk_under_the_sanitizers(tmp_path):
     """tests/host/pool_plan_check.cpp (the plan header alone, no device code, not loaded into Python) under
-    -fsanitize=address,undefined: ordinary geometries with every refusal mixed in, descriptors at the integer limits."""
+    -fsanitize=address,undefined: ordinary geometries with every refusal mixed in, descriptors at the integer limits; then the
+    maximum kind against the program's restatement of the scalar entries' former checks (the same code for any single violation, the
+    same map and grids wherever the plan succeeds: the program exits non-zero otherwise) and the maximum descriptors the plan refuses;
+    and the dump mode, one line per average-kind descriptor."""
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("no g++")
@@ -336,3 +340,9 @@ def test_pool_plan_walk_under_the_sanitizers(tmp_path):
     got = dict(zip(out[:10:2], out[1:10:2]))
     assert out[10] == "checksum" and len(out[11]) == 16
     assert int(got["cases"]) >= 120000 and min(int(got[k]) for k in ("ok", "einval", "eshape")) > 10000 and int(got["ealign"]) == 0
+    mx = dict(zip(out[12::2], out[13::2]))
+    print("pool_plan_check:", " ".join(out))
+    assert int(mx["max_cases"]) >= 80000 and min(int(mx[k]) for k in ("max_ok", "max_single", "max_multi")) > 5000, mx
+    assert int(mx["max_cases"]) == int(mx["max_ok"]) + int(mx["max_single"]) + int(mx["max_multi"])
+    dump = subprocess.run([exe, "dump"], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(dump) > 100000 and all(" f32 " in ln and " bf16 " in ln for ln in dump[:50])
