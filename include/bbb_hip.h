@@ -869,6 +869,34 @@ int bbb_conv2d_chwn_bf16_dgrad(const bbb_conv_desc_t* d, const void* g_pre, cons
 int bbb_conv2d_chwn_bf16_dgrad_plan(const bbb_conv_desc_t* d, int up_h, int up_w, int out_h, int out_w, uint32_t flags,
                                     int32_t* shape, int32_t* k_groups, int32_t* wave_specialised);
 
+/* bf16 training backward, additive in ABI 13: the contraction half of a FIRST layer's input gradient on bf16 operands -- what
+ * bbb_hip/ops.py: first_layer_input_grad runs as a transpose + bbb_conv2d_chwn_fwd for the fp32 node (csrc/input_grad_bf16.hip):
+ *   D[(ci, r, q)][ho][wo][b] = sum over (e, co) of w[e][co][ci][r][q] * g_pre[e][co][ho][wo][b]
+ * followed, unchanged, by bbb_input_grad_col2im(D, d_row_pitch, 0, NULL, dx, d, stream).
+ * d is the LAYER: batch, cin, h, w, cout, kh, kw, stride, pad, dil, draws = E, w_draw_stride = cout * Kp with Kp = cin*kh*kw rounded
+ * up to 8; every other field 0.  g_pre: the E*cout rows (e, co), g_row_pitch (>= ho*wo*batch, % 8 == 0) elements apart, bf16 or,
+ * with BBB_BF16_BWD_G_F32, fp32 values that are exactly bf16-representable (what bbb_pool_act_bwd_chwn_bf16 writes with
+ * BBB_BF16_BWD_OUT_F32, at the padded plane pitch: taken by their high halves while staging, no bf16 copy).  w: the rows
+ * [E][cout][Kp] of the parameter pass, read IN PLACE (no transposed copy), in (ci, r, q) order or, with BBB_BF16_W_TAP_MAJOR
+ * (cin % 8 == 0), (r, q, ci) order; D's rows are in (ci, r, q) order either way, cin*kh*kw of them d_row_pitch (>= ho*wo*batch,
+ * % 4 == 0) fp32 elements apart.  Any other flag bit is BBB_EINVAL.  g_pre, w and D 16-byte aligned (else BBB_EALIGN), B % 8 == 0,
+ * E*cout*g_row_pitch, E*cout*Kp and cin*kh*kw*d_row_pitch below 2^31 (else BBB_ESHAPE).
+ * v_mfma_f32_32x32x16_bf16, fp32 accumulation over (e, co) in ascending order, never split and never rounded: an element of D does
+ * not depend on what else is in the launch, a column not on the other columns.  E*cout, cin*kh*kw and ho*wo*batch need not be
+ * multiples of anything but B's 8: tails are masked on both operands -- nothing outside the E*cout rows' first ho*wo*batch columns
+ * and the weight rows' first cin*kh*kw columns is read, nothing outside D's cin*kh*kw x ho*wo*batch is written (the pad columns of
+ * either pitch are left alone).  No atomics, no scratch.  Every check happens before any launch, in this order: BBB_EINVAL (nulls,
+ * flags, the descriptor), BBB_EALIGN (pointers, pitches), BBB_ESHAPE (the map, B % 8, pitches below a row, the 32-bit limits, the
+ * grid); csrc/input_grad_bf16_plan.h states them one by one. */
+int bbb_first_layer_dgrad_bf16(const bbb_conv_desc_t* d, const void* g_pre, int64_t g_row_pitch, const void* w, float* dcol,
+                               int64_t d_row_pitch, uint32_t flags, void* stream);
+/* What that launch takes (host only): *tile_j rows of D (32 when cin*kh*kw <= 32, else 64: a function of the layer alone) and
+ * *tile_n = 128 columns per workgroup, *k_chunks = ceil(E*cout / 32) steps of the contraction every workgroup walks, *blocks
+ * workgroups: the (row tile, column tile) pairs rounded up to a multiple of 8 (dealt to the 8 XCDs in runs, so that the row tiles
+ * that read one tile of g_pre share an L2).  Out-pointers may be NULL; the launch entry's codes for every check that does not involve an operand pointer. */
+int bbb_first_layer_dgrad_bf16_plan(const bbb_conv_desc_t* d, int64_t g_row_pitch, int64_t d_row_pitch, uint32_t flags,
+                                    int32_t* tile_j, int32_t* tile_n, int32_t* k_chunks, int64_t* blocks);
+
 /* Library / device introspection (host-only). */
 int bbb_abi_version(void);
 const char* bbb_build_info(void);

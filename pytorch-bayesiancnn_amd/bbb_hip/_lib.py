@@ -165,6 +165,10 @@ _SIGNATURES = {
                                            c_void_p]),
     "bbb_conv2d_chwn_bf16_dgrad_plan": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, c_int, c_int, c_u32, ctypes.POINTER(c_i32),
                                                 ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    # (their descriptor is the LAYER, not a launch: passed as a plain pointer, ctypes.byref(ConvDesc) all the same)
+    "bbb_first_layer_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_u32, c_void_p]),
+    "bbb_first_layer_dgrad_bf16_plan": (c_int, [c_void_p, c_i64, c_i64, c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i64)]),
     "bbb_chwn_to_bhwc_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
     "bbb_batch_chunks_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
     "bbb_abi_version": (c_int, []),

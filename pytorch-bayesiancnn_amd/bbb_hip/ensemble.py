@@ -563,6 +563,10 @@ def mc_logits(net, x, draws, seed, call0, fuse_act=True, timers=None, eps=None, 
     the 224x224 AlexNet flatten quirk, where B' = B*49).  layout "auto" takes the batch-innermost fast path
     when it applies (inference, B % 4 == 0, known module kinds), "nchw" forces the reference layout."""
     _lib.require_device(x)
+    if _bf16_x_grad(precision, x) and not any_requires_grad(net):
+        # d/dx with frozen parameters in bf16 storage (LaunchConfig.bf16_input_grad), as the fp32 branch below
+        logits_cb, kl = _bf16_x_grad_logits(net, x, draws, seed, call0, layout != "nchw" and eps is None and fuse_act and timers is None)
+        return logits_cb.permute(0, 2, 1).contiguous(), kl
     _check_precision(precision, net, x, layout != "nchw" and eps is None and fuse_act)
     if (layout != "nchw" and eps is None and precision == "fp32" and not any_requires_grad(net)
             and _x_grad_node_ok(net, x, fuse_act, timers)):
@@ -672,7 +676,9 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     nll_loss(lse, target) * train_size + beta * kl is formed by the tail's own launches (ops.elbo_cb_autograd) and left in elbo[3];
     elbo[3] still None on return: the caller forms it.
     precision="bf16" with elbo (train.forward_loss(precision="bf16")) and autograd on: the bf16 training mode
-    (fast_train.mc_logits_autograd -> _MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing autograd."""
+    (fast_train.mc_logits_autograd -> _MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing
+    autograd -- except, under LaunchConfig.bf16_input_grad, on an input that requires a gradient (_bf16_x_grad): the same node, or a
+    BBBHipError that names what it does not cover."""
     if precision == "bf16" and elbo is not None and torch.is_grad_enabled():
         if not (fuse_act and fast_autograd) or timers is not None or units is not None or int(groups) > 1 or share is not None or b_offset:
             raise _lib.BBBHipError("bf16 training runs on the batch-innermost autograd node only")
@@ -680,6 +686,12 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
         logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias, precision="bf16")
         stats["path"] = "chwn-autograd-bf16"
         return _autograd_tail(logits_cb, kl1, mean_over, elbo)
+    if _bf16_x_grad(precision, x):
+        # a forward-only entry (mc_forward) on an input that requires a gradient, LaunchConfig.bf16_input_grad: the same node
+        plain = (fuse_act and timers is None and units is None and int(groups) == 1 and share is None and not b_offset
+                 and step_end is None)
+        logits_cb, kl1 = _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=param_alias)
+        return _autograd_tail(logits_cb, kl1, mean_over, None)
     _check_precision(precision, net, x, fuse_act)
     if (precision == "fp32" and share is None and int(groups) == 1 and (units is None or units[0] <= 1) and not b_offset
             and step_end is None and _x_grad_node_ok(net, x, fuse_act, timers)):
@@ -731,6 +743,30 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     else:
         lse = _run(timers, "mc_tail", 0, lambda: ops.mc_tail(logits, mean_over=mean_over))
     return lse, kl1
+
+
+_BF16_X_GRAD_ONLY = ("bf16 input gradients (LaunchConfig.bf16_input_grad) run on the batch-innermost autograd node only: fused "
+                     "activations, no timers, external eps, reference layout, work units, groups of steps, shares of a group, batch "
+                     "offsets, captured steps or group= sharding")
+
+
+def _bf16_x_grad(precision, x):
+    """precision="bf16" on an input that requires a gradient with autograd on, under LaunchConfig.bf16_input_grad: the forward-only
+    entry points then take the bf16 autograd node (fast_train._MCForwardBF16, whose backward ends in ops.first_layer_input_grad_bf16)
+    or raise; without the switch they behave as they always did."""
+    return (precision == "bf16" and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
+            and ops.current_config().bf16_input_grad)
+
+
+def _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=None):
+    """-> (logits [E, C, B] batch-innermost, kl of one forward) on the bf16 autograd node; plain: the call asks for nothing but the
+    whole step in one piece.  What the node does not cover raises BBBHipError("bf16 training covers ...") (fast_train.bf16_train_refusal)."""
+    if not (plain and fast_autograd):
+        raise _lib.BBBHipError(_BF16_X_GRAD_ONLY)
+    from . import fast_train
+    logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=alias, precision="bf16")
+    stats["path"] = "chwn-autograd-bf16"
+    return logits_cb, kl1
 
 
 def _x_grad_node_ok(net, x, fuse_act, timers):
@@ -799,6 +835,8 @@ def mc_forward(net, x, num_ens, group=None, fuse_act=True, timers=None, kl_mode=
     rng.assign_stream_ids(net)                       # stream ids by module order: identical on every rank
     seed, call0 = rng.next_calls(num_ens)            # all ranks advance identically
     _refuse_bf16_lrt_sharded(net, precision, world > 1)
+    if world > 1 and _bf16_x_grad(precision, x):
+        raise _lib.BBBHipError(_BF16_X_GRAD_ONLY)
     S, lo, hi = shard_plan(net, x, num_ens, rank, world, fuse_act, precision)
     if hi > lo:
         if S > 1:

@@ -14,7 +14,8 @@ activated output; backward walks the layers in reverse with
                                        regenerated from the counter),
   * `ops.first_layer_input_grad`       d loss / d x when x requires a gradient (saliency maps, adversarial steps): the first
                                        layer's contraction over (draw, channel) on the forward kernel + the bbb_input_grad_col2im
-                                       gather; with frozen parameters the weight side above is skipped altogether,
+                                       gather; with frozen parameters the weight side above is skipped altogether
+                                       (the bf16 node, under LaunchConfig.bf16_input_grad: ops.first_layer_input_grad_bf16),
 so no activation, pooling or convolution of the step runs through torch autograd.  What main_bayesian.py:43-58 does per batch:
 E forwards, KL, log_softmax / logmeanexp, ELBO, backward -- on the training path the tail after the logits is HIP too
 (ops.elbo_cb_autograd: bbb_elbo_cb_fwd / bbb_elbo_cb_bwd); the entry points that return log-probabilities keep it in torch.
@@ -416,7 +417,11 @@ class _MCForwardBF16(torch.autograd.Function):
       * ops.conv2d_chwn_weight_grad_bf16  wgrad on the bf16 GEMM with the roles swapped -> fp32,
       * the first layer (3-channel input shared by every draw): ops.conv2d_chwn_weight_grad_shared_input on the fp32 kernel over
         the fp32 values of the bf16 operands (a bf16 x bf16 product is exact in fp32: the same contraction),
-      * ops.reparam_kl_backward           unchanged (fp32)."""
+      * ops.reparam_kl_backward           unchanged (fp32),
+      * ops.first_layer_input_grad_bf16   d loss / d x when x requires a gradient (LaunchConfig.bf16_input_grad): the first layer's
+        contraction over (draw, channel) on the bf16 MFMA from the sampled rows and g_pre where they are -> fp32, never rounded, + the
+        bbb_input_grad_col2im gather; with frozen parameters the weight side above is skipped altogether and the first layer's g_pre
+        stays bf16."""
 
     @staticmethod
     def forward(ctx, cfg, x, *params):
@@ -443,8 +448,10 @@ class _MCForwardBF16(torch.autograd.Function):
         tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn_bf16, ops.avgpool_chwn_bf16)
         _carry(ctx, cfg, params)
         ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
-        # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted)
-        ctx.x_nchw = x.detach().to(torch.bfloat16).to(torch.float32) if tape[0]["x"].shape[1] % 4 != 0 else None
+        # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted); frozen parameters
+        # (a backward to x alone, LaunchConfig.bf16_input_grad): there is none
+        ctx.x_nchw = (x.detach().to(torch.bfloat16).to(torch.float32)
+                      if tape[0]["x"].shape[1] % 4 != 0 and any(ctx.needs_input_grad[2:]) else None)
         return h.reshape(E, -1, x.shape[0]), kl
 
     @staticmethod
@@ -456,13 +463,16 @@ class _MCForwardBF16(torch.autograd.Function):
         cfg, tape = ctx.cfg, ctx.tape
         mus, rhos, ids, pm, ps, x_shape = ctx.meta
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        # (as in _MCForward) need_w False -- frozen parameters, reached under LaunchConfig.bf16_input_grad alone: no weight side at all;
+        # need_x: the first layer's input gradient (first_layer_input_grad_bf16) at the end.  Without the switch this mode refuses
+        # x.requires_grad (bf16_train_refusal): every backward is then one for the parameters alone, enqueued as it always was
+        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
         gws = [None] * len(mus)
+        dx = None
         g = g_logits.contiguous() if g_logits is not None else None
-        # weight_side=True whatever needs a gradient: this mode refuses x.requires_grad (bf16_train_refusal), so every backward
-        # it sees is one for the parameters
-        sched = _Schedule(g, weight_side=True)
+        sched = _Schedule(g, weight_side=need_w)
         r0 = tape[0]
-        shared0 = r0["x"].shape[1] % 4 != 0
+        shared0 = need_w and r0["x"].shape[1] % 4 != 0                    # (no weight side: the first layer's g_pre stays bf16)
         xk_first = None                                                   # (as in _MCForward: the first layer's im2col forked up front)
         if sched.side is not None and shared0:
             xk_first = sched.fork_early(lambda: ops.im2col_pbj(ctx.x_nchw, (E,) + r0["wshape"], *r0["geom"]))
@@ -500,10 +510,16 @@ class _MCForwardBF16(torch.autograd.Function):
                 g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
                                                     w_flipped=w_flipped.get(li), stride=stride)
             else:
+                if need_x:
+                    # on the sampled rows and g_pre where they are: bf16, or the fp32 form the weight side above reads
+                    dx = ops.first_layer_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), stride, padding,
+                                                         dilation).view(x_shape)
                 g = None
         sched.join()
+        if not need_w:
+            return tuple([None, dx] + [None] * (2 * len(mus)))
         gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        out = [None, None]
+        out = [None, dx]
         for a, b in zip(gmu, grho):
             out += [a, b]
         return tuple(out)
@@ -660,12 +676,14 @@ def _strided_later_conv(net):
 def bf16_train_refusal(net, x):
     """Why the bf16 training mode does not cover (net, x), or None when it does: what train_path_ok calls "bbb" with B % 8 == 0 --
     with stride-1 convolutions behind the first layer, or any stride there under LaunchConfig.bf16_strided_train, and without average
-    pools, or with them under LaunchConfig.bf16_avgpool (both read from the configuration that is current: the caller's use_config,
-    or what GraphedTrainStep snapshotted)."""
+    pools, or with them under LaunchConfig.bf16_avgpool, and with an input that does not require a gradient, or one that does under
+    LaunchConfig.bf16_input_grad (all read from the configuration that is current: the caller's use_config, or what GraphedTrainStep
+    snapshotted)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return "a 4-d fp32 CUDA batch"
-    if x.requires_grad and torch.is_grad_enabled():
-        return "inputs that do not require a gradient (there are no bf16 input gradients; precision='fp32' has them)"
+    if x.requires_grad and torch.is_grad_enabled() and not ops.current_config().bf16_input_grad:
+        return ("inputs that do not require a gradient (precision='fp32' has input gradients) unless LaunchConfig.bf16_input_grad is "
+                "set (ops.use_config(bf16_input_grad=True): the first layer's input gradient on the bf16 operands, opt-in)")
     from . import ensemble
     if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
         return "no eps replay"

@@ -352,11 +352,17 @@ class LaunchConfig:
                 IEEE division, ONE rounding to bf16; the backward in gather form with act' from the stored bf16 output).  Inference
                 (mc_logits / mc_forward / the Graphed* objects / the drop-in loop; LRT models together with bf16_lrt) and BBB
                 training (train_step / forward_loss / GraphedTrainStep), B % 8 == 0.  Opt-in: under the default bf16 on a model
-                with an average pool raises, naming this switch, as it always did"""
+                with an average pool raises, naming this switch, as it always did
+    bf16_input_grad   False | True: forward_loss / mc_forward / mc_logits(precision="bf16") admit an input that requires a gradient
+                (saliency maps, adversarial steps): the bf16 node's backward then ends in first_layer_input_grad_bf16
+                (csrc/input_grad_bf16.hip: the first layer's contraction over (draw, channel) on the bf16 MFMA from the sampled rows
+                and g_pre where they are, fp32 accumulation, an fp32 dx that is never rounded) and, with frozen parameters, runs no
+                weight side at all.  BBB models, B % 8 == 0, eager only.  Opt-in: under the default such an input is refused,
+                naming this switch, as it always was (precision="fp32" has input gradients)"""
     FIELDS = ("gemm_mode", "bf16x3_min_workgroups", "s3_min_images", "split_k", "pool_fusion", "pool_fuse_min_items",
               "pool_fuse_imbalance", "launches_overlap", "pool_fuse_min_items_overlapped", "pool_fuse_weight_budget",
               "bf16_pool_fuse_min_rows", "bf16_pool_fuse_min_rows_overlapped", "bf16_c8", "bf16_c8_min_items", "c8x3", "c8x3_s2d",
-              "dropin_precision", "bf16_lrt", "bf16_strided_train", "bf16_avgpool")
+              "dropin_precision", "bf16_lrt", "bf16_strided_train", "bf16_avgpool", "bf16_input_grad")
     __slots__ = FIELDS
 
     def __init__(self, **kw):
@@ -380,6 +386,7 @@ class LaunchConfig:
         self.bf16_lrt = False                          # precision="bf16" on all-LRT models (lrt_conv2d_chwn_bf16_forward); opt-in
         self.bf16_strided_train = False                # bf16 training of models with strided later layers (bbb_conv2d_chwn_bf16_dgrad); opt-in
         self.bf16_avgpool = False                      # precision="bf16" on models with average pools (csrc/pool2d_bf16.hip); opt-in
+        self.bf16_input_grad = False                   # precision="bf16" on inputs that require a gradient (csrc/input_grad_bf16.hip); opt-in
         self.c8x3 = True                               # split-bf16 mode: layers (behind the first) with Cin % 32 == 0 run on the
                                                        # MFMA-ready-operand kernel (conv2d_c8x3_forward: channel-interleaved split
                                                        # activations + tap-major weights from the parameter pass); False: round 4's
@@ -2640,6 +2647,72 @@ def conv2d_chwn_input_grad_bf16(g_pre, w, w_shape, x_hw, padding, dilation, w_fl
         check(_lib.lib().bbb_conv2d_chwn_bf16_dgrad(ctypes.byref(d), g_pre.data_ptr(), w_t.data_ptr(), gx.data_ptr(), sh, sw, H, W,
                                                     2 if tap_major else 0, cur_stream(g_pre.device)), "bbb_conv2d_chwn_bf16_dgrad")
     return gx
+
+
+def _first_layer_desc(B, cin, cout, kh, kw, x_hw, stride, padding, dilation, draws):
+    """The descriptor of bbb_first_layer_dgrad_bf16 (and of the gather behind it): the LAYER, its weight sets one set of bf16 rows apart."""
+    d, ho, wo = conv_desc(B, cin, (int(x_hw[0]), int(x_hw[1])), cout, (kh, kw), stride, padding, dilation, int(draws),
+                          w_stride=cout * bf16_row_pitch(cin * kh * kw), b_stride=0)
+    d.x_draw_stride = 0
+    return d, ho, wo
+
+
+def first_layer_dgrad_bf16_plan(B, w_shape, x_hw, stride=1, padding=0, dilation=1, draws=1, g_row_pitch=None, d_row_pitch=None,
+                                g_f32=False, tap_major=None):
+    """(rows of D per workgroup 32 | 64, columns per workgroup, steps of the contraction, workgroups) of the launch
+    first_layer_input_grad_bf16 makes for a layer with weights w_shape = (Cout, Cin, kh, kw) over `draws` draws of B images on the map
+    x_hw: the launch entry's own plan (bbb_first_layer_dgrad_bf16_plan, csrc/input_grad_bf16_plan.h; host only).  The pitches default
+    to a dense row, tap_major to bf16_tap_major(w_shape).  What the entry refuses raises BBBHipError with its code."""
+    Cout, Cin, kh, kw = (int(v) for v in w_shape)
+    d, ho, wo = _first_layer_desc(B, Cin, Cout, kh, kw, x_hw, stride, padding, dilation, draws)
+    K = max(ho, 0) * max(wo, 0) * B
+    tm = bf16_tap_major((Cout, Cin, kh, kw)) if tap_major is None else bool(tap_major)
+    tj, tn, kc, blocks = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    check(_lib.lib().bbb_first_layer_dgrad_bf16_plan(ctypes.byref(d), K if g_row_pitch is None else int(g_row_pitch),
+                                                     K if d_row_pitch is None else int(d_row_pitch), (1 if g_f32 else 0) | (2 if tm else 0),
+                                                     ctypes.byref(tj), ctypes.byref(tn), ctypes.byref(kc), ctypes.byref(blocks)),
+          "bbb_first_layer_dgrad_bf16_plan")
+    return tj.value, tn.value, kc.value, blocks.value
+
+
+def first_layer_input_grad_bf16(g_pre, w, w_shape, x_hw, stride, padding, dilation):
+    """first_layer_input_grad on the bf16 node's operands: d loss / d x of a model's FIRST layer, summed over the draws,
+        dx[b, ci, h, w] = sum_e sum_co sum_(r, q) g_pre[e, co, ho, wo, b] * w[e, co, ci, r, q],  h = ho*sh - ph + r*dh, w = wo*sw - pw + q*dw
+    in two launches: bbb_first_layer_dgrad_bf16 (csrc/input_grad_bf16.hip: D[(ci, r, q)] = the contraction over (e, co) on the bf16
+    MFMA, fp32 accumulation, both operands read where they are) and bbb_input_grad_col2im, the fp32 path's gather.  Nothing is
+    rounded: dx is fp32 like the caller's x.
+    g_pre [E, Cout, Ho, Wo, B]: bf16, or fp32 holding bf16 values (pool_act_backward_chwn_bf16(out_f32=True)); a view whose (draw,
+    channel) planes sit at one pitch (% 8 == 0: pad_planes=True) is read in place, anything else is made contiguous first.
+    w: the sampled bf16 rows [E, Cout, Kp] of a layer with weights w_shape = (Cout, Cin, kh, kw) (sample_weights_bf16's layout and
+    column order, bf16_tap_major(w_shape)); x_hw = (H, W) -> dx [B, Cin, H, W] fp32.  A first linear layer behind a flatten:
+    kh = kw = 1, H = W = 1, Cin = in_features."""
+    if g_pre.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BBBHipError("first_layer_input_grad_bf16: g_pre must be bf16, or fp32 holding bf16 values")
+    require_device(g_pre, dtype=g_pre.dtype)
+    require_device(w, dtype=torch.bfloat16)
+    Cout, Cin, kh, kw = (int(v) for v in w_shape)
+    if g_pre.dim() != 5 or w.dim() != 3:
+        raise _lib.BBBHipError("first_layer_input_grad_bf16: g_pre [E, Cout, Ho, Wo, B] and rows [E, Cout, Kp] expected")
+    E, _, Ho, Wo, B = g_pre.shape
+    H, W = int(x_hw[0]), int(x_hw[1])
+    J = Cin * kh * kw
+    d, ho, wo = _first_layer_desc(B, Cin, Cout, kh, kw, (H, W), stride, padding, dilation, E)
+    if (ho, wo) != (Ho, Wo) or g_pre.shape[1] != Cout or tuple(w.shape) != (E, Cout, bf16_row_pitch(J)):
+        raise _lib.BBBHipError("first_layer_input_grad_bf16: geometry mismatch")
+    w = w.contiguous()
+    K, P = Ho * Wo * B, g_pre.stride(1)
+    if not (g_pre.stride(4) == 1 and g_pre.stride(3) == B and g_pre.stride(2) == Wo * B and P >= K and P % 8 == 0
+            and (E == 1 or g_pre.stride(0) == Cout * P)):
+        g_pre, P = g_pre.contiguous(), K
+    flags = (1 if g_pre.dtype == torch.float32 else 0) | (2 if bf16_tap_major((Cout, Cin, kh, kw)) else 0)
+    dcol = torch.empty((J, K), dtype=torch.float32, device=g_pre.device)
+    dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=g_pre.device)
+    with on_device(g_pre.device):
+        st = cur_stream(g_pre.device)
+        check(_lib.lib().bbb_first_layer_dgrad_bf16(ctypes.byref(d), g_pre.data_ptr(), P, w.data_ptr(), dcol.data_ptr(), K, flags, st),
+              "bbb_first_layer_dgrad_bf16")
+        check(_lib.lib().bbb_input_grad_col2im(dcol.data_ptr(), K, 0, 0, dx.data_ptr(), ctypes.byref(d), st), "bbb_input_grad_col2im")
+    return dx
 
 
 def chwn_to_bhwc_bf16(x, c_pad=None):
