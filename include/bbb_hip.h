@@ -897,6 +897,31 @@ int bbb_first_layer_dgrad_bf16(const bbb_conv_desc_t* d, const void* g_pre, int6
 int bbb_first_layer_dgrad_bf16_plan(const bbb_conv_desc_t* d, int64_t g_row_pitch, int64_t d_row_pitch, uint32_t flags,
                                     int32_t* tile_j, int32_t* tile_n, int32_t* k_chunks, int64_t* blocks);
 
+/* bf16 input gradients of LRT models, additive in ABI 13 (opt-in from Python: LaunchConfig.bf16_lrt_input_grad; csrc/pool2d_bf16.hip):
+ * the activation side of a local-reparameterisation layer's backward on bf16 planes -- bbb_lrt_pool_act_bwd_chwn on
+ * bbb_pool_act_bwd_chwn_bf16's storage rules, for frozen parameters (there is no weight side, and no average-pool form).
+ *   y [planes][h][w][B] bf16, the stored activated output bf16(act(act_mu + sqrt(act_var) * eps)) (NULL only with k = 0 and act = 0:
+ *   the logits layer, whose output is fp32 and enters nothing); act_var fp32 [moment_planes][h][w][B]
+ *   (moment_planes = planes, or one draw's worth when every draw shares one pair of moments; a multiple of `channels` that divides
+ *   planes); g_out [planes][hp][wp][B] bf16 or, with BBB_BF16_BWD_G_F32, fp32; or, g_out2 != NULL (never with BBB_BF16_BWD_G_F32), the
+ *   incoming gradient is fmaf(2 * x_out, g_out2, g_out) in fp32: the two bf16 input gradients of the layer above and this layer's
+ *   (pooled) bf16 output x_out [x_planes][hp][wp][B], x_planes dividing planes.  k, s: MaxPool2d(k, s), k = 0 the activation alone.
+ *     g_act = the routing of bbb_pool_act_bwd_chwn_bf16 (first maximum in scan order among the stored bf16 values)
+ *     g_mu  = g_act * act'(y)                      -> bf16, one rounding
+ *     g_var = g_mu * eps / (2 sqrt(act_var))       -> bf16, one rounding (from the fp32 g_mu)
+ *   with eps REGENERATED from the counter: the forward's element of the pre-pool output -- canonical index
+ *   ((b + b_offset) * channels + n) * h * w + pixel, n = plane % channels, call call0 + *call_dev + plane / channels, stream_id, as
+ *   bbb_lrt_sample_chwn_bf16 / bbb_lrt_conv2d_chwn_bf16_fwd draw it.  Everything else fp32 in registers.  g_mu / g_var dense, or planes
+ *   at out_plane_pitch elements (% 8 == 0).  16-byte vector loads and stores only, no atomics, no scratch, the same bits on every run.
+ *   Checks, before any launch: BBB_EINVAL (a null operand, act, a flag other than BBB_BF16_BWD_G_F32, b_offset < 0, non-positive or
+ *   non-dividing plane / channel counts, half a combine or one with fp32 g_out, then the pooling plan's: non-positive sizes),
+ *   BBB_ESHAPE (B % 8 != 0, a window larger than the map, index ranges), BBB_EALIGN (an operand that is not 16-byte aligned). */
+int bbb_lrt_pool_act_bwd_chwn_bf16(const void* g_out, const void* y, const float* act_var, void* g_mu, void* g_var, int64_t planes,
+                                   int64_t moment_planes, int channels, int h, int w, int batch, int k, int s, int act,
+                                   int64_t out_plane_pitch, const void* g_out2, const void* x_out, int64_t x_planes, uint64_t seed,
+                                   uint32_t call0, const uint32_t* call_dev, uint32_t stream_id, int b_offset, uint32_t flags,
+                                   void* stream);
+
 /* Library / device introspection (host-only). */
 int bbb_abi_version(void);
 const char* bbb_build_info(void);

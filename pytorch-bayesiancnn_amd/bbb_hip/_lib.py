@@ -169,6 +169,9 @@ _SIGNATURES = {
     "bbb_first_layer_dgrad_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_u32, c_void_p]),
     "bbb_first_layer_dgrad_bf16_plan": (c_int, [c_void_p, c_i64, c_i64, c_u32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
                                                 ctypes.POINTER(c_i32), ctypes.POINTER(c_i64)]),
+    "bbb_lrt_pool_act_bwd_chwn_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int, c_int,
+                                               c_int, c_int, c_int, c_i64, c_void_p, c_void_p, c_i64, c_u64, c_u32, c_void_p, c_u32,
+                                               c_int, c_u32, c_void_p]),
     "bbb_chwn_to_bhwc_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_void_p]),
     "bbb_batch_chunks_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p]),
     "bbb_abi_version": (c_int, []),

@@ -563,9 +563,12 @@ def mc_logits(net, x, draws, seed, call0, fuse_act=True, timers=None, eps=None, 
     the 224x224 AlexNet flatten quirk, where B' = B*49).  layout "auto" takes the batch-innermost fast path
     when it applies (inference, B % 4 == 0, known module kinds), "nchw" forces the reference layout."""
     _lib.require_device(x)
-    if _bf16_x_grad(precision, x) and not any_requires_grad(net):
-        # d/dx with frozen parameters in bf16 storage (LaunchConfig.bf16_input_grad), as the fp32 branch below
-        logits_cb, kl = _bf16_x_grad_logits(net, x, draws, seed, call0, layout != "nchw" and eps is None and fuse_act and timers is None)
+    lrt_x = _bf16_lrt_x_grad(precision, x, net)
+    if _bf16_x_grad(precision, x, net) and (lrt_x or not any_requires_grad(net)):
+        # d/dx with frozen parameters in bf16 storage (LaunchConfig.bf16_input_grad; all-LRT models: bf16_lrt_input_grad, whose node
+        # refuses trainable parameters by name), as the fp32 branch below
+        logits_cb, kl = _bf16_x_grad_logits(net, x, draws, seed, call0, layout != "nchw" and eps is None and fuse_act and timers is None,
+                                            lrt=lrt_x)
         return logits_cb.permute(0, 2, 1).contiguous(), kl
     _check_precision(precision, net, x, layout != "nchw" and eps is None and fuse_act)
     if (layout != "nchw" and eps is None and precision == "fp32" and not any_requires_grad(net)
@@ -684,13 +687,14 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
             raise _lib.BBBHipError("bf16 training runs on the batch-innermost autograd node only")
         from . import fast_train
         logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=param_alias, precision="bf16")
-        stats["path"] = "chwn-autograd-bf16"
+        stats["path"] = "chwn-autograd-bf16-lrt" if _has_lrt(net) else "chwn-autograd-bf16"      # (LRT: _MCForwardLRTBF16 alone gets here)
         return _autograd_tail(logits_cb, kl1, mean_over, elbo)
-    if _bf16_x_grad(precision, x):
+    lrt_x = _bf16_lrt_x_grad(precision, x, net)
+    if _bf16_x_grad(precision, x, net):
         # a forward-only entry (mc_forward) on an input that requires a gradient, LaunchConfig.bf16_input_grad: the same node
         plain = (fuse_act and timers is None and units is None and int(groups) == 1 and share is None and not b_offset
                  and step_end is None)
-        logits_cb, kl1 = _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=param_alias)
+        logits_cb, kl1 = _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=param_alias, lrt=lrt_x)
         return _autograd_tail(logits_cb, kl1, mean_over, None)
     _check_precision(precision, net, x, fuse_act)
     if (precision == "fp32" and share is None and int(groups) == 1 and (units is None or units[0] <= 1) and not b_offset
@@ -750,22 +754,41 @@ _BF16_X_GRAD_ONLY = ("bf16 input gradients (LaunchConfig.bf16_input_grad) run on
                      "offsets, captured steps or group= sharding")
 
 
-def _bf16_x_grad(precision, x):
+def _bf16_x_grad(precision, x, net=None):
     """precision="bf16" on an input that requires a gradient with autograd on, under LaunchConfig.bf16_input_grad: the forward-only
     entry points then take the bf16 autograd node (fast_train._MCForwardBF16, whose backward ends in ops.first_layer_input_grad_bf16)
-    or raise; without the switch they behave as they always did."""
+    or raise; without the switch they behave as they always did.  net: also a model with LRT layers under LaunchConfig.bf16_lrt +
+    bf16_lrt_input_grad (_bf16_lrt_x_grad)."""
     return (precision == "bf16" and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad
-            and ops.current_config().bf16_input_grad)
+            and (ops.current_config().bf16_input_grad or (net is not None and _bf16_lrt_x_grad(precision, x, net))))
 
 
-def _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=None):
+def _bf16_lrt_input_grad_asked(net):
+    """LaunchConfig.bf16_lrt_input_grad is set and the model has LRT layers: fast_train.bf16_train_refusal then asks the rules of the
+    bf16 LRT input-gradient node instead of the BBB training mode's."""
+    return ops.current_config().bf16_lrt_input_grad and _has_lrt(net)
+
+
+def _bf16_lrt_x_grad(precision, x, net):
+    """_bf16_x_grad for models with LRT layers: precision="bf16" on an input that requires a gradient with autograd on, under
+    LaunchConfig.bf16_lrt together with LaunchConfig.bf16_lrt_input_grad (it does not need bf16_input_grad): the forward-only entry
+    points then take fast_train._MCForwardLRTBF16 or raise what it does not cover by name (trainable parameters among it); without
+    both switches they behave as they always did."""
+    cfg = ops.current_config()
+    return (cfg.bf16_lrt_input_grad and cfg.bf16_lrt and precision == "bf16" and torch.is_grad_enabled() and torch.is_tensor(x)
+            and x.requires_grad and _has_lrt(net))
+
+
+def _bf16_x_grad_logits(net, x, draws, seed, call0, plain, alias=None, lrt=False):
     """-> (logits [E, C, B] batch-innermost, kl of one forward) on the bf16 autograd node; plain: the call asks for nothing but the
-    whole step in one piece.  What the node does not cover raises BBBHipError("bf16 training covers ...") (fast_train.bf16_train_refusal)."""
+    whole step in one piece.  What the node does not cover raises BBBHipError("bf16 training covers ...") (fast_train.bf16_train_refusal).
+    lrt: the call came in under LaunchConfig.bf16_lrt_input_grad (_bf16_lrt_x_grad) -- the same exclusions, named after that switch."""
     if not (plain and fast_autograd):
-        raise _lib.BBBHipError(_BF16_X_GRAD_ONLY)
+        raise _lib.BBBHipError(_BF16_X_GRAD_ONLY.replace("LaunchConfig.bf16_input_grad", "LaunchConfig.bf16_lrt_input_grad") if lrt
+                               else _BF16_X_GRAD_ONLY)
     from . import fast_train
     logits_cb, kl1 = fast_train.mc_logits_autograd(net, x, draws, seed, call0, alias=alias, precision="bf16")
-    stats["path"] = "chwn-autograd-bf16"
+    stats["path"] = "chwn-autograd-bf16-lrt" if _has_lrt(net) else "chwn-autograd-bf16"          # (LRT: _MCForwardLRTBF16 alone gets here)
     return logits_cb, kl1
 
 

@@ -20,7 +20,8 @@ so no activation, pooling or convolution of the step runs through torch autograd
 E forwards, KL, log_softmax / logmeanexp, ELBO, backward -- on the training path the tail after the logits is HIP too
 (ops.elbo_cb_autograd: bbb_elbo_cb_fwd / bbb_elbo_cb_bwd); the entry points that return log-probabilities keep it in torch.
 
-Three nodes -- _MCForward (fp32), _MCForwardBF16 (bf16 storage), _MCForwardLRT (local reparameterisation) -- over one forward walk
+Four nodes -- _MCForward (fp32), _MCForwardBF16 (bf16 storage), _MCForwardLRT (local reparameterisation), _MCForwardLRTBF16 (its
+activation side in bf16 storage: input gradients with frozen parameters, no weight side) -- over one forward walk
 (_walk: layer / activation / pool pairing, the tape) and one backward schedule (_Schedule: which stream a layer's weight side runs
 on, the early fork, the join); _carry / _run_backward take the launch configuration and scratch scope from the forward to the
 backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weight side, its input gradient, its flips up front.
@@ -667,10 +668,147 @@ class _MCForwardLRT(torch.autograd.Function):
         return (None, dx, *grads)
 
 
+def _lrt_bf16_forward(cfg, x, params):
+    """The forward of _MCForwardLRTBF16 -> (tape, fp32 logits [E, C, B] batch-innermost): the launches of the bf16 LRT inference path
+    (ensemble._mc_logits_chwn under LaunchConfig.bf16_lrt: ops.lrt_weights_bf16 once for every layer; per layer
+    ops.lrt_conv2d_chwn_bf16_forward -- the shared first layer of a many-draw step as moments only + ops.lrt_sample_chwn_bf16 --;
+    ops.maxpool_chwn_bf16 unfused), so the logits are that path's bit for bit, with the fp32 act_var of every layer kept beside them.
+    params: per layer W_mu, sigma_W^2, bias_mu, sigma_b^2 (fp32).  A record of the tape: x (the bf16 input), y (the stored bf16
+    activated output before the pool; the logits layer's is fp32), av (act_var: y's shape, or one draw's worth for the shared first
+    layer), w_mu / w_var (the bf16 rows), wshape, sid (the noise stream), and what _walk adds (geom, act, pool, first, out_shape)."""
+    from . import ensemble
+    _LRTLayer = _layers()[3]
+    E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+    mods = ensemble.flat_children(cfg["net"])
+    n_layers = sum(isinstance(m, _LRTLayer) for m in mods)
+    params = [t.detach() for t in params]
+    rows = ops.lrt_weights_bf16([params[4 * li + j] for li in range(n_layers) for j in (0, 1)])
+
+    def run_layer(m, li, x_in, is_conv, geom, act, pooled):
+        w_mu, w_var, b_mu, b_var = rows[2 * li], rows[2 * li + 1], params[4 * li + 2], params[4 * li + 3]
+        wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
+        last = li == n_layers - 1
+        if last and (act is not None or pooled):
+            raise _lib.BBBHipError("bf16 LRT input gradients: the logits layer (fp32 output) must not be followed by an activation or a pool")
+        sid = m._stream_base + 2
+        tapm = is_conv and ops.bf16_tap_major(wshape)
+        args = (x_in, w_mu, w_var, b_mu, b_var, wshape[1:], seed, call0, sid, *geom)
+        if x_in.shape[0] == 1 and E > 1 and not last:        # the shared first layer: one pair of moments, E samples of it
+            _, am, av = ops.lrt_conv2d_chwn_bf16_forward(*args, sample=False, moments_only=True, tap_major=tapm)
+            y = ops.lrt_sample_chwn_bf16(am, av, E, seed, call0, sid, act=act)
+        else:
+            y, _, av = ops.lrt_conv2d_chwn_bf16_forward(*args, sample=True, want_moments=True, act=act, out_f32=last, tap_major=tapm,
+                                                        n_slabs=E)
+        return dict(w_mu=w_mu, w_var=w_var, wshape=wshape, y=y, av=av, sid=sid)
+
+    def no_avgpool(*a):
+        raise _lib.BBBHipError("bf16 LRT input gradients: no average pools (bf16_train_refusal refuses them)")
+
+    h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)              # [1, C, H, W, B] bf16
+    tape, h = _walk(mods, h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn_bf16, no_avgpool)
+    return tape, h.reshape(E, -1, x.shape[0])
+
+
+class _MCForwardLRTBF16(torch.autograd.Function):
+    """Input gradients of all-LRT models in bf16 storage, frozen parameters (LaunchConfig.bf16_lrt + bf16_lrt_input_grad; the arithmetic
+    contract is DESIGN.md section 4.5b): (x, W_mu0, sigma_W0^2, b_mu0, sigma_b0^2, ...) -> fp32 logits [E, C, B] batch-innermost.
+    Forward = _lrt_bf16_forward.  Backward = _MCForwardLRT._backward with the weight side removed -- no _Schedule weight side, no side
+    streams, no parameter gradient -- on bf16 storage, per layer from the top:
+      * ops.lrt_pool_act_backward_chwn_bf16   pooling / activation backward and the split into (g_mu, g_var) in one pass, eps
+        regenerated from the counter (the stored y is rounded: the fp32 kernel's y - act_mu would cancel rounded values), the layer
+        above's g1 + 2 x g2 combined on the fly; each of the pair rounded once to bf16,
+      * ops.conv2d_chwn_input_grad_bf16       below the first layer d1 = dgrad(g_mu, W_mu), d2 = dgrad(g_var, sigma^2) on the bf16 GEMM
+        over the flipped rows (a strided layer, under LaunchConfig.bf16_strided_train: the transposed launch), each rounded once,
+      * ops.first_layer_input_grad_bf16_lrt   the first layer: dx = T(g_mu, W_mu) + 2 x_b * T(g_var, sigma^2), the sum over draws part
+        of the fp32 accumulation, x_b the bf16-rounded input; fp32, never rounded."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, *params):
+        tape, logits = _lrt_bf16_forward(cfg, x, params)
+        _carry(ctx, cfg, params)
+        ctx.tape = tape
+        ctx.x_b = x.detach().to(torch.bfloat16).to(torch.float32)         # what the forward multiplied, widened
+        return logits
+
+    @staticmethod
+    def backward(ctx, g_logits):
+        return _run_backward(ctx, _MCForwardLRTBF16._backward, g_logits)
+
+    @staticmethod
+    def _backward(ctx, g_logits):
+        cfg, tape = ctx.cfg, ctx.tape
+        if any(ctx.needs_input_grad[2:]):
+            raise _lib.BBBHipError("bf16 LRT has input gradients only: no parameter gradient (bf16_train_refusal refuses trainable parameters)")
+        seed, call0 = cfg["seed"], cfg["call0"]
+        dx = None
+        g = g_logits.contiguous()
+        for li in range(len(tape) - 1, -1, -1):
+            rec = tape[li]
+            y, x_in, wshape = rec["y"], rec["x"], rec["wshape"]
+            stride, padding, dilation = rec["geom"]
+            # the incoming gradient: the logits' fp32 gradient, or the layer above's two bf16 input gradients + this layer's output,
+            # combined (d1 + 2 x d2) inside the pass
+            comb = None
+            if isinstance(g, tuple):
+                g, comb = g[0].reshape(rec["out_shape"]), (g[1].reshape(rec["out_shape"]), g[2].reshape(rec["out_shape"]))
+            else:
+                g = g.reshape(rec["out_shape"])
+            g_pair = _pool_pass(rec, ops.lrt_pool_act_backward_chwn_bf16, None, g, y if y.dtype == torch.bfloat16 else None, rec["av"],
+                                noise=(seed, call0, rec["sid"]), combine=comb)            # [2, E, Cout, Ho, Wo, B] bf16
+            hw = (x_in.shape[2], x_in.shape[3])
+            if rec["first"]:
+                if ctx.needs_input_grad[1]:
+                    dx = ops.first_layer_input_grad_bf16_lrt(g_pair, rec["w_mu"], rec["w_var"], wshape, hw, stride, padding,
+                                                             dilation, ctx.x_b).view(ctx.x_b.shape)
+            else:
+                d1 = ops.conv2d_chwn_input_grad_bf16(g_pair[0], rec["w_mu"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
+                d2 = ops.conv2d_chwn_input_grad_bf16(g_pair[1], rec["w_var"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
+                g = (d1, x_in, d2)                         # (d1 + 2 x d2 is formed by the layer below's pass)
+        return (None, dx) + (None,) * (4 * len(tape))
+
+
 def _strided_later_conv(net):
     """A convolution behind the first Bayesian layer has a stride other than 1."""
     from . import ensemble
     return any(hasattr(m, "stride") and ops._pair(m.stride) != (1, 1) for m in ensemble.bayesian_layers(net)[1:])
+
+
+_BF16_STRIDED_REFUSAL = ("stride-1 convolutions after the first layer (the strided input gradient has an fp32 kernel only; "
+                         "precision='fp32' trains such a model) unless LaunchConfig.bf16_strided_train is set "
+                         "(ops.use_config(bf16_strided_train=True) or launch_config= on GraphedTrainStep: the transposed bf16 launch, opt-in)")
+
+
+def _bf16_lrt_input_grad_refusal(net, x):
+    """bf16_train_refusal for a model with LRT layers under LaunchConfig.bf16_lrt_input_grad: why the bf16 LRT input-gradient node
+    (_MCForwardLRTBF16) does not cover (net, x), or None when it does -- an all-LRT model on the training path (train_path_ok "lrt") with
+    EVERY parameter frozen, an input that requires a gradient, B % 8 == 0, no eps replay, max pools only, stride-1 convolutions behind
+    the first layer (any stride under LaunchConfig.bf16_strided_train), under LaunchConfig.bf16_lrt."""
+    from . import ensemble
+    cfg = ops.current_config()
+    if not cfg.bf16_lrt:
+        return ("BBB (weight-space) layers; LaunchConfig.bf16_lrt_input_grad takes effect only together with LaunchConfig.bf16_lrt: "
+                + ensemble._BF16_LRT_HINT)
+    if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
+        return "no eps replay"
+    if ensemble.any_requires_grad(net):
+        return ("frozen parameters on LRT models: bf16 LRT has input gradients only (LaunchConfig.bf16_lrt_input_grad; there is no bf16 "
+                "LRT training) -- freeze them with net.requires_grad_(False), or use precision='fp32', which trains LRT models")
+    if not (x.requires_grad and torch.is_grad_enabled()):
+        return ("an input that requires a gradient: bf16 LRT has input gradients only (LaunchConfig.bf16_lrt_input_grad); without one, "
+                "ensemble.mc_logits / mc_forward under torch.no_grad() run the bf16 LRT inference path")
+    kind = train_path_ok(net, x)
+    if kind != "lrt":
+        return ("a model whose Bayesian layers are ALL local-reparameterisation layers, and an input, on the batch-innermost training "
+                "path (fast_train.train_path_ok): no mixed BBB / LRT models")
+    if ensemble._has_avgpool(net):
+        return ("LRT models without average pooling: the LRT pooling / activation backward has no average-pool form on bf16 planes "
+                "(lrt_pool_act_backward_chwn_bf16 routes max pools only), with or without LaunchConfig.bf16_avgpool; precision='fp32' "
+                "has it")
+    if _strided_later_conv(net) and not cfg.bf16_strided_train:
+        return _BF16_STRIDED_REFUSAL
+    if x.shape[0] % 8 != 0:
+        return "a batch size that is a multiple of 8"
+    return None
 
 
 def bf16_train_refusal(net, x):
@@ -678,13 +816,16 @@ def bf16_train_refusal(net, x):
     with stride-1 convolutions behind the first layer, or any stride there under LaunchConfig.bf16_strided_train, and without average
     pools, or with them under LaunchConfig.bf16_avgpool, and with an input that does not require a gradient, or one that does under
     LaunchConfig.bf16_input_grad (all read from the configuration that is current: the caller's use_config, or what GraphedTrainStep
-    snapshotted)."""
+    snapshotted).  Under LaunchConfig.bf16_lrt_input_grad a model with LRT layers is asked of _bf16_lrt_input_grad_refusal instead: input
+    gradients of all-LRT models with frozen parameters."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         return "a 4-d fp32 CUDA batch"
+    from . import ensemble
+    if ensemble._bf16_lrt_input_grad_asked(net):             # (evaluated under that switch alone: off, nothing below moves)
+        return _bf16_lrt_input_grad_refusal(net, x)
     if x.requires_grad and torch.is_grad_enabled() and not ops.current_config().bf16_input_grad:
         return ("inputs that do not require a gradient (precision='fp32' has input gradients) unless LaunchConfig.bf16_input_grad is "
                 "set (ops.use_config(bf16_input_grad=True): the first layer's input gradient on the bf16 operands, opt-in)")
-    from . import ensemble
     if any(m.eps_source is not None for m in ensemble.bayesian_layers(net)):
         return "no eps replay"
     kind = train_path_ok(net, x)
@@ -696,12 +837,11 @@ def bf16_train_refusal(net, x):
     if kind is None:
         return "a model and input on the batch-innermost training path (fast_train.train_path_ok)"
     if _strided_later_conv(net) and not ops.current_config().bf16_strided_train:
-        return ("stride-1 convolutions after the first layer (the strided input gradient has an fp32 kernel only; "
-                "precision='fp32' trains such a model) unless LaunchConfig.bf16_strided_train is set "
-                "(ops.use_config(bf16_strided_train=True) or launch_config= on GraphedTrainStep: the transposed bf16 launch, opt-in)")
+        return _BF16_STRIDED_REFUSAL
     if x.shape[0] % 8 != 0:
         return "a batch size that is a multiple of 8"
     return None
+
 
 def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32"):
     """Differentiable batched forward: -> (logits [E, C, B] batch-innermost, kl of one forward), gradients flow to every
@@ -720,19 +860,21 @@ def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32")
         why = bf16_train_refusal(net, x)
         if why is not None:
             raise _lib.BBBHipError("bf16 training covers " + why)
-        node = _MCForwardBF16
-    else:
+        node = _MCForwardLRTBF16 if train_path_ok(net, x) == "lrt" else _MCForwardBF16       # (an LRT model passes the refusal under
+    else:                                                                                     #  LaunchConfig.bf16_lrt_input_grad alone)
         node = _MCForwardLRT if train_path_ok(net, x) == "lrt" else _MCForward
     layers = ensemble.bayesian_layers(net)
     mus, rhos, _ = _param_lists(layers, A)
     if node is _MCForwardLRT:                # its leaves are (mu, sigma^2) from the KL pass, which carries the gradients to (mu, rho)
         kl, rhos, mus = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True,
                                     mu_through=True)
+    elif node is _MCForwardLRTBF16:          # frozen parameters: the inference path's KL pass (fp32), sigma^2 beside it
+        kl, rhos = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True)
     params = []
     for li in range(len(layers)):            # per layer: W_mu, W_rho (LRT: W_var), bias_mu, bias_rho (LRT: bias_var)
         params += [mus[2 * li], rhos[2 * li], mus[2 * li + 1], rhos[2 * li + 1]]
     cfg = dict(net=net, draws=int(draws), seed=seed, call0=call0)
     out = node.apply(cfg, x, *params)
-    logits, kl = (out, kl) if node is _MCForwardLRT else out
+    logits, kl = (out, kl) if node in (_MCForwardLRT, _MCForwardLRTBF16) else out
     logits.bbb_cfg = cfg
     return logits, kl

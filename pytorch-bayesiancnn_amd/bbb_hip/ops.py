@@ -358,11 +358,19 @@ class LaunchConfig:
                 (csrc/input_grad_bf16.hip: the first layer's contraction over (draw, channel) on the bf16 MFMA from the sampled rows
                 and g_pre where they are, fp32 accumulation, an fp32 dx that is never rounded) and, with frozen parameters, runs no
                 weight side at all.  BBB models, B % 8 == 0, eager only.  Opt-in: under the default such an input is refused,
-                naming this switch, as it always was (precision="fp32" has input gradients)"""
+                naming this switch, as it always was (precision="fp32" has input gradients)
+    bf16_lrt_input_grad   False | True: together with bf16_lrt, forward_loss / mc_forward / mc_logits(precision="bf16") admit an input
+                that requires a gradient on an all-LRT model whose parameters are ALL FROZEN (saliency maps, adversarial steps against
+                the reference's default layer type): fast_train._MCForwardLRTBF16 -- the bf16 LRT inference launches with a tape, and
+                the activation side of the LRT backward in bf16 storage (lrt_pool_act_backward_chwn_bf16, csrc/pool2d_bf16.hip: the
+                noise regenerated from the counter; the two input-gradient contractions on conv2d_chwn_input_grad_bf16; an fp32 dx
+                from first_layer_input_grad_bf16_lrt that is never rounded).  No parameter gradient (bf16 LRT training does not
+                exist: trainable parameters are refused), no average pools, B % 8 == 0, eager only, one device.  Does not need
+                bf16_input_grad; without bf16_lrt it changes nothing.  Opt-in: under the default such a call raises what it always did"""
     FIELDS = ("gemm_mode", "bf16x3_min_workgroups", "s3_min_images", "split_k", "pool_fusion", "pool_fuse_min_items",
               "pool_fuse_imbalance", "launches_overlap", "pool_fuse_min_items_overlapped", "pool_fuse_weight_budget",
               "bf16_pool_fuse_min_rows", "bf16_pool_fuse_min_rows_overlapped", "bf16_c8", "bf16_c8_min_items", "c8x3", "c8x3_s2d",
-              "dropin_precision", "bf16_lrt", "bf16_strided_train", "bf16_avgpool", "bf16_input_grad")
+              "dropin_precision", "bf16_lrt", "bf16_strided_train", "bf16_avgpool", "bf16_input_grad", "bf16_lrt_input_grad")
     __slots__ = FIELDS
 
     def __init__(self, **kw):
@@ -387,6 +395,7 @@ class LaunchConfig:
         self.bf16_strided_train = False                # bf16 training of models with strided later layers (bbb_conv2d_chwn_bf16_dgrad); opt-in
         self.bf16_avgpool = False                      # precision="bf16" on models with average pools (csrc/pool2d_bf16.hip); opt-in
         self.bf16_input_grad = False                   # precision="bf16" on inputs that require a gradient (csrc/input_grad_bf16.hip); opt-in
+        self.bf16_lrt_input_grad = False               # ... on all-LRT models with frozen parameters, together with bf16_lrt (_MCForwardLRTBF16); opt-in
         self.c8x3 = True                               # split-bf16 mode: layers (behind the first) with Cin % 32 == 0 run on the
                                                        # MFMA-ready-operand kernel (conv2d_c8x3_forward: channel-interleaved split
                                                        # activations + tap-major weights from the parameter pass); False: round 4's
@@ -2556,6 +2565,94 @@ def avgpool_act_backward_chwn_bf16(g_out, y, kernel, stride, padding, count_incl
     stored bf16 y [..., H, W, B], rounded once to bf16.  g_out bf16 or fp32, of the pooled size; out_f32 / pad_planes as there."""
     return pool_act_backward_chwn_bf16(g_out, y, 0, 1, act, out_f32=out_f32, pad_planes=pad_planes,
                                        avg=(kernel, stride, padding, count_include_pad))
+
+
+def lrt_pool_act_backward_chwn_bf16(g_out, y, act_var, k, s, act, noise, combine=None, b_offset=0):
+    """lrt_pool_act_backward_chwn(stacked=True) on bf16 storage (bbb_lrt_pool_act_bwd_chwn_bf16; LaunchConfig.bf16_lrt_input_grad):
+    the activation side of a local-reparameterisation layer's backward -> [2, *y.shape] bf16, [0] = g_mu = act'(y) * route(g), the
+    gradient w.r.t. act_mu, [1] = g_var = g_mu * eps / (2 sqrt(act_var)), the gradient w.r.t. act_var, each rounded once.
+    y: the layer's stored bf16 activated output [E, C, H, W, B] (None: k = 0 and no activation -- the logits layer, whose output is
+    fp32; the shape is then g_out's); act_var fp32, y's shape or one draw's worth [1, C, H, W, B]; g_out bf16 or fp32, of the
+    (pooled) output's shape.  noise = (seed, call0, stream_id): eps is the forward's element, regenerated from the counter (draw e of
+    the launch under call0 + e; b_offset: the global index of the first image).  combine = (x_out, g_out2): the incoming gradient is
+    g_out + 2 * x_out * g_out2 in fp32 -- g_out / g_out2 the layer above's two bf16 input gradients, x_out this layer's (pooled) bf16
+    output.  Max pools only: there is no average-pool form."""
+    if g_out.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: g_out must be bf16 or fp32")
+    require_device(g_out, dtype=g_out.dtype)
+    require_device(act_var)
+    if y is None:
+        if int(k) != 0 or act is not None:
+            raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: pooling / activation backward needs the stored output y")
+    else:
+        require_device(y, dtype=torch.bfloat16)
+        y = y.contiguous()
+    g_out, act_var = g_out.contiguous(), act_var.contiguous()
+    shape = tuple(g_out.shape) if y is None else tuple(y.shape)
+    if len(shape) < 4:
+        raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: planes [..., C, H, W, B] expected")
+    _, H, W, B, planes = _planes_of(shape)
+    C = shape[-4]
+    mom_planes = act_var.numel() // (H * W * B)
+    if act_var.numel() != mom_planes * H * W * B or mom_planes == 0 or planes % mom_planes != 0 or mom_planes % C != 0:
+        raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: act_var must hold y's planes, or one draw's worth of them")
+    g2p, xcp, x_planes = 0, 0, 0
+    if combine is not None:
+        if g_out.dtype != torch.bfloat16:
+            raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: the combine is of two bf16 input gradients")
+        xc, g2 = combine[0].contiguous(), combine[1].contiguous()
+        require_device(xc, g2, dtype=torch.bfloat16)
+        if g2.numel() != g_out.numel() or xc.numel() == 0 or g_out.numel() % xc.numel() != 0:
+            raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: combine = (x_out, g_out2) of g_out's shape (x_out may hold one draw)")
+        g2p, xcp, x_planes = g2.data_ptr(), xc.data_ptr(), planes * xc.numel() // g_out.numel()
+    ho, wo = (H, W) if int(k) == 0 else pooled_map(H, W, (k, s))
+    if g_out.numel() != planes * ho * wo * B:
+        raise _lib.BBBHipError("lrt_pool_act_backward_chwn_bf16: g_out must hold %d planes of the map %d x %d x %d" % (planes, ho, wo, B))
+    seed, call0, stream_id = noise
+    out = torch.empty((2,) + shape, dtype=torch.bfloat16, device=g_out.device)
+    with on_device(g_out.device):
+        check(_lib.lib().bbb_lrt_pool_act_bwd_chwn_bf16(g_out.data_ptr(), ptr(y), act_var.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                                        planes, mom_planes, C, H, W, B, int(k), int(s), ACT_CODE[act], 0, g2p, xcp,
+                                                        x_planes, seed, call0 & 0xFFFFFFFF, rng.call_dev_ptr(g_out.device), stream_id,
+                                                        int(b_offset), 1 if g_out.dtype == torch.float32 else 0,
+                                                        cur_stream(g_out.device)), "bbb_lrt_pool_act_bwd_chwn_bf16")
+    return out
+
+
+def first_layer_input_grad_bf16_lrt(g_pair, w_mu, w_var, w_shape, x_hw, stride, padding, dilation, x_b):
+    """first_layer_input_grad(x_lrt=) on the bf16 LRT node's operands: d loss / d x of a local-reparameterisation FIRST layer,
+        dx = T(g_mu, W_mu) + 2 x_b * T(g_var, sigma^2),   T(g, w)[b, ci, h, w] = sum_e sum_co sum_(r, q) g[e, co, ho, wo, b] * w[co, ci, r, q]
+    g_pair [2, E, Cout, Ho, Wo, B] bf16 (lrt_pool_act_backward_chwn_bf16: the per-draw g_mu / g_var as they are -- the sum over
+    draws is part of the fp32 accumulation); w_mu / w_var: the bf16 rows [Cout, Kp] of lrt_weights_bf16 for weights w_shape = (Cout, Cin,
+    kh, kw), shared by every draw (one small copy per draw: the contraction reads one weight set per draw); x_b [B, Cin, H, W] fp32, the
+    bf16-rounded input the forward multiplied.  Two launches of bbb_first_layer_dgrad_bf16 into the two sets of one buffer, then
+    bbb_input_grad_col2im in its LRT form (fmaf(2 x, set 1, set 0)); nothing is rounded -> dx [B, Cin, H, W] fp32."""
+    require_device(g_pair, w_mu, w_var, dtype=torch.bfloat16)
+    require_device(x_b)
+    Cout, Cin, kh, kw = (int(v) for v in w_shape)
+    if g_pair.dim() != 6 or g_pair.shape[0] != 2 or w_mu.dim() != 2 or w_mu.shape != w_var.shape:
+        raise _lib.BBBHipError("first_layer_input_grad_bf16_lrt: g_pair [2, E, Cout, Ho, Wo, B] and rows [Cout, Kp] expected")
+    _, E, _, Ho, Wo, B = g_pair.shape
+    H, W = int(x_hw[0]), int(x_hw[1])
+    J = Cin * kh * kw
+    d, ho, wo = _first_layer_desc(B, Cin, Cout, kh, kw, (H, W), stride, padding, dilation, E)
+    if ((ho, wo) != (Ho, Wo) or g_pair.shape[2] != Cout or tuple(w_mu.shape) != (Cout, bf16_row_pitch(J))
+            or x_b.numel() != B * Cin * H * W):
+        raise _lib.BBBHipError("first_layer_input_grad_bf16_lrt: geometry mismatch")
+    g_pair, x_b = g_pair.contiguous(), x_b.contiguous()
+    K = Ho * Wo * B
+    flags = 2 if bf16_tap_major((Cout, Cin, kh, kw)) else 0
+    dcol = torch.empty((2, J, K), dtype=torch.float32, device=g_pair.device)
+    dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=g_pair.device)
+    with on_device(g_pair.device):
+        st = cur_stream(g_pair.device)
+        for i, w in enumerate((w_mu, w_var)):
+            rows = w.unsqueeze(0).expand(E, -1, -1).contiguous()
+            check(_lib.lib().bbb_first_layer_dgrad_bf16(ctypes.byref(d), g_pair[i].data_ptr(), K, rows.data_ptr(), dcol[i].data_ptr(), K,
+                                                        flags, st), "bbb_first_layer_dgrad_bf16")
+        check(_lib.lib().bbb_input_grad_col2im(dcol.data_ptr(), K, J * K, x_b.data_ptr(), dx.data_ptr(), ctypes.byref(d), st),
+              "bbb_input_grad_col2im")
+    return dx
 
 
 def plane_sums_bf16(g):

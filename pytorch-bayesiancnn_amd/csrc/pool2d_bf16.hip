@@ -7,14 +7,17 @@
 //
 // All kernels are bound by memory traffic, one thread per 16-byte group of 8 images, rows of images read and written as whole
 // vectors, no LDS.  The order of every sum depends on the window alone -- never on the plane count or the launch size -- so a draw
-// computed alone, inside a many-draw launch or as a work unit is the same bits.  There is no LRT form of the backward: bf16 LRT
-// training does not exist.
+// computed alone, inside a many-draw launch or as a work unit is the same bits.  The LRT form of the backward
+// (bbb_lrt_pool_act_bwd_chwn_bf16: the activation side of a local-reparameterisation layer, input gradients only) regenerates the
+// forward's noise element from the counter (that arithmetic, not the traffic, sets its time: profiles/bf16_lrt_input_grad_notes.md);
+// there is no average-pool form of it, and bf16 LRT training does not exist.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "../../include/bbb_hip.h"
+#include "bbb_common.cuh"
 #include "pool_act_bwd.cuh"
 #include "pool_plan.h"
 
@@ -215,6 +218,122 @@ __global__ __launch_bounds__(256) void avgpool_act_bwd_bf16_kernel(const void* _
     }
 }
 
+// The kernel arguments of the LRT backward below.
+struct LrtBwdArgs {
+    const void* g_out;           // [planes][Hp][Wp][B] bf16 (G_F32: fp32), the gradient w.r.t. the (pooled) output ...
+    const u32x4* g2;             // ... or, g2 != NULL, d1 of the combine fmaf(2 * x_out, d2, d1): g2 = d2, xc = x_out (bf16, xc_total8
+    const u32x4* xc;             //     16-byte groups: all planes, or one draw's worth)
+    int64_t xc_total8;
+    const u32x4* y;              // [planes][H][W][B] bf16, the stored activated output
+    const f32x4* av;             // [mom_planes][H][W][B] fp32 act_var
+    int64_t mom_planes;
+    u32x4* g_mu;                 // [planes][H][W][B] bf16 (dense, or planes at out_pitch8 16-byte groups)
+    u32x4* g_var;
+    int64_t total;               // threads: planes * (H * W / PPT) * B8
+    int H, W, Hp, Wp, B8, k, s, act, C;
+    int64_t out_pitch8;
+    uint32_t k0, k1, call0, stream_id;
+    const uint32_t* call_dev;
+    int b_off;
+};
+
+// Backward of [sample -> activation -> MaxPool2d(k, s)] (k = 0: no pool) of a local-reparameterisation layer on bf16 planes: the
+// forward stored y = bf16(act(act_mu + sqrt(act_var) * eps)).  Gather form, one pass, fp32 in registers:
+//   g_act = pool_act_bwd_bf16_kernel's routing (first maximum in scan order among the stored bf16 values) of the incoming gradient --
+//           bf16, fp32 (G_F32: the logits layer's) or the on-the-fly combine fmaf(2 * x_out, d2, d1) of the layer above's two bf16
+//           input gradients (pool_bwd::incoming's bf16 twin),
+//   g_mu  = g_act * act'(y)                          (the gradient w.r.t. act_mu),
+//   g_var = g_mu * eps / (2 * sqrt(act_var))         (the gradient w.r.t. act_var), from the fp32 g_mu,
+// each rounded ONCE to bf16.  eps is the forward's element, REGENERATED from the counter -- the stored y is rounded, so the fp32
+// kernel's y - act_mu would be a cancellation of rounded values: canonical NCHW index ((b + b_off) * C + n) * HW + pix of the
+// pre-pool output, call call0 + *call_dev + draw (draw = plane / C), bbb::normal4(idx >> 2, ...) lane idx & 3, as
+// lrt_sample_chwn_bf16_kernel and the epilogue of pconv_bf16_lrt.hip draw it.  One normal4 call yields four consecutive pixels of
+// one (image, channel): a thread owns 8 images of PPT pixels -- PPT = 4 (H * W % 4 == 0: every value is used) or 1 (3 of 4 dropped).
+template <bool G_F32, int PPT>
+__global__ __launch_bounds__(256) void lrt_pool_act_bwd_bf16_kernel(const LrtBwdArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.total) return;
+    const int HW = a.H * a.W, HWq = HW / PPT, B8 = a.B8, k = a.k, s = a.s;
+    const int b8 = (int)(i % B8);
+    int64_t t = i / B8;
+    const int q = (int)(t % HWq);
+    const int64_t pl = t / HWq;
+    const int n = (int)(pl % a.C);
+    const uint32_t call = a.call0 + (a.call_dev ? *a.call_dev : 0u) + (uint32_t)(pl / a.C);
+    float z[8][4];                       // PPT == 4: image u's four pixels (idx0 % 4 == 0); PPT == 1: z[u][0] is image u's pixel
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const uint64_t idx0 = (uint64_t)(((int64_t)(8 * b8 + u + a.b_off) * a.C + n) * HW + (int64_t)q * PPT);
+        bbb::normal4(idx0 >> 2, a.stream_id, call, a.k0, a.k1, z[u]);
+        if (PPT == 1) {
+            const int c = (int)(idx0 & 3);
+            z[u][0] = c == 0 ? z[u][0] : c == 1 ? z[u][1] : c == 2 ? z[u][2] : z[u][3];
+        }
+    }
+    const u32x4* yp = a.y + pl * HW * B8 + b8;
+    const int64_t gbase = pl * a.Hp * a.Wp * B8 + b8;
+    auto incoming = [&](int64_t idx, float (&gv)[8]) {
+        pool_bwd::incoming8<G_F32>(a.g_out, idx, gv);
+        if (!G_F32 && a.g2 != nullptr) {
+            float d2[8], xo[8];
+            unpack8(a.g2[idx], d2);
+            unpack8(a.xc[idx % a.xc_total8], xo);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) gv[u] = fmaf(2.0f * xo[u], d2[u], gv[u]);
+        }
+    };
+    for (int j = 0; j < PPT; ++j) {
+        const int pix = q * PPT + j;
+        const int h = pix / a.W, w = pix - h * a.W;
+        const int64_t in_plane = (int64_t)pix * B8 + b8;
+        float me[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (a.y != nullptr) unpack8(yp[(int64_t)pix * B8], me);      // (no y: k == 0 and no activation -- the logits layer, fp32 output)
+        float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (k == 0) {
+            incoming(pl * HW * B8 + in_plane, g);
+        } else {
+            const int ph_lo = h - k + 1 > 0 ? (h - k + 1 + s - 1) / s : 0, ph_hi = h / s < a.Hp - 1 ? h / s : a.Hp - 1;
+            const int pw_lo = w - k + 1 > 0 ? (w - k + 1 + s - 1) / s : 0, pw_hi = w / s < a.Wp - 1 ? w / s : a.Wp - 1;
+            for (int ph = ph_lo; ph <= ph_hi; ++ph)
+                for (int pw = pw_lo; pw <= pw_hi; ++pw) {
+                    bool first[8] = {true, true, true, true, true, true, true, true};
+                    const int my = (h - ph * s) * k + (w - pw * s);
+                    for (int r = 0; r < k; ++r)
+                        for (int c = 0; c < k; ++c) {
+                            const int idx = r * k + c;
+                            if (idx == my) continue;
+                            float v[8];
+                            unpack8(yp[((int64_t)(ph * s + r) * a.W + (pw * s + c)) * B8], v);
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) first[u] = first[u] && (idx < my ? v[u] < me[u] : v[u] <= me[u]);
+                        }
+                    float go[8];
+                    incoming(gbase + ((int64_t)ph * a.Wp + pw) * B8, go);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) g[u] += first[u] ? go[u] : 0.0f;
+                }
+        }
+        const int64_t mi = (pl % a.mom_planes) * HW * B8 + in_plane;
+        const f32x4 v0 = a.av[2 * mi], v1 = a.av[2 * mi + 1];
+        uint32_t rm[8], rv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float d = 1.0f;
+            if (a.act == 1) d = me[u] > 0.0f ? 1.0f : 0.0f;
+            else if (a.act == 2) d = me[u] > 20.0f ? 1.0f : -expm1f(-me[u]);      // y = softplus(v) -> sigmoid(v) = 1 - exp(-y)
+            const float gm = g[u] * d;
+            const float eps = PPT == 1 ? z[u][0] : j == 0 ? z[u][0] : j == 1 ? z[u][1] : j == 2 ? z[u][2] : z[u][3];
+            const float var = u < 4 ? v0[u & 3] : v1[u & 3];
+            rm[u] = f2bf(gm);
+            rv[u] = f2bf((gm * eps) * (0.5f * __builtin_amdgcn_rsqf(var)));      // g_mu * eps / (2 sqrt(act_var))
+        }
+        // out_pitch8 != 0: planes are written at that pitch (in 16-byte units of bf16) instead of densely
+        const int64_t oi = (a.out_pitch8 ? pl * a.out_pitch8 : pl * HW * B8) + in_plane;
+        a.g_mu[oi] = pack8(rm);
+        a.g_var[oi] = pack8(rv);
+    }
+}
+
 // launch(G_F32, OUT_F32) with the two storage flags of a bf16 backward as compile-time constants (std::bool_constant values)
 template <typename L>
 void with_bwd_flags(uint32_t flags, L&& launch) {
@@ -277,6 +396,52 @@ extern "C" int bbb_pool_act_bwd_chwn_bf16(const void* g_out, const void* y, void
     if (g_out == nullptr || g_pre == nullptr || (y == nullptr && (k != 0 || act != 0))) return BBB_EINVAL;
     const bbb_pool_desc_t d = pool_plan::max_desc(h, w, batch, k, s, true);
     return bwd_launch(&d, k, g_out, y, g_pre, planes, act, out_plane_pitch, flags, stream);
+}
+
+extern "C" int bbb_lrt_pool_act_bwd_chwn_bf16(const void* g_out, const void* y, const float* act_var, void* g_mu, void* g_var,
+                                              int64_t planes, int64_t moment_planes, int channels, int h, int w, int batch, int k, int s,
+                                              int act, int64_t out_plane_pitch, const void* g_out2, const void* x_out, int64_t x_planes,
+                                              uint64_t seed, uint32_t call0, const uint32_t* call_dev, uint32_t stream_id, int b_offset,
+                                              uint32_t flags, void* stream) {
+    if (g_out == nullptr || act_var == nullptr || g_mu == nullptr || g_var == nullptr || (y == nullptr && (k != 0 || act != 0)))
+        return BBB_EINVAL;
+    if (act < 0 || act > 2 || (flags & ~BBB_BF16_BWD_G_F32) != 0 || b_offset < 0) return BBB_EINVAL;
+    if (channels <= 0 || planes <= 0 || planes % channels != 0 || moment_planes <= 0 || moment_planes % channels != 0 ||
+        planes % moment_planes != 0)
+        return BBB_EINVAL;
+    const bool gf = (flags & BBB_BF16_BWD_G_F32) != 0;
+    if ((g_out2 == nullptr) != (x_out == nullptr)) return BBB_EINVAL;
+    if (g_out2 != nullptr && (gf || x_planes <= 0 || planes % x_planes != 0)) return BBB_EINVAL;      // (the combine is of bf16 gradients)
+    const bbb_pool_desc_t d = pool_plan::max_desc(h, w, batch, k, s, true);
+    pool_plan::Plan pl;
+    if (const int rc = pool_plan::plan_bf16(&d, planes, out_plane_pitch, &pl)) return rc;
+    if ((((uintptr_t)g_out | (uintptr_t)y | (uintptr_t)act_var | (uintptr_t)g_mu | (uintptr_t)g_var | (uintptr_t)g_out2 |
+          (uintptr_t)x_out) & 15u) != 0)
+        return BBB_EALIGN;
+    const int64_t hw = (int64_t)h * w;
+    // the canonical noise index ((b + b_offset) * channels + n) * hw + pix and the kernel's per-plane sizes stay in range
+    if (hw > 0x7fffffffLL || pool_plan::mul_cap((int64_t)batch + b_offset, channels, hw) >= conv_desc_check::kCap) return BBB_ESHAPE;
+    const int ppt = hw % 4 == 0 ? 4 : 1;
+    LrtBwdArgs a = {};
+    a.g_out = g_out; a.g2 = reinterpret_cast<const u32x4*>(g_out2); a.xc = reinterpret_cast<const u32x4*>(x_out);
+    a.xc_total8 = g_out2 != nullptr ? x_planes * pl.ho * pl.wo * pl.b4 : (int64_t)1;
+    a.y = reinterpret_cast<const u32x4*>(y); a.av = reinterpret_cast<const f32x4*>(act_var); a.mom_planes = moment_planes;
+    a.g_mu = reinterpret_cast<u32x4*>(g_mu); a.g_var = reinterpret_cast<u32x4*>(g_var);
+    a.total = pl.bwd_total4 / ppt;
+    a.H = h; a.W = w; a.Hp = pl.ho; a.Wp = pl.wo; a.B8 = pl.b4; a.k = k; a.s = d.stride_h; a.act = act; a.C = channels;
+    a.out_pitch8 = out_plane_pitch / 8;
+    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.call0 = call0; a.stream_id = stream_id; a.call_dev = call_dev;
+    a.b_off = b_offset;
+    const dim3 grid((unsigned)((a.total + pool_plan::kThreads - 1) / pool_plan::kThreads)), blk(pool_plan::kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (gf) {
+        if (ppt == 4) hipLaunchKernelGGL((lrt_pool_act_bwd_bf16_kernel<true, 4>), grid, blk, 0, st, a);
+        else          hipLaunchKernelGGL((lrt_pool_act_bwd_bf16_kernel<true, 1>), grid, blk, 0, st, a);
+    } else {
+        if (ppt == 4) hipLaunchKernelGGL((lrt_pool_act_bwd_bf16_kernel<false, 4>), grid, blk, 0, st, a);
+        else          hipLaunchKernelGGL((lrt_pool_act_bwd_bf16_kernel<false, 1>), grid, blk, 0, st, a);
+    }
+    return (int)hipGetLastError();
 }
 
 extern "C" int bbb_avgpool_chwn_bf16(const bbb_pool_desc_t* d, const void* x, void* y, int64_t planes, void* stream) {
