@@ -670,11 +670,16 @@ int bbb_lrt_weights_bf16(const bbb_bf16_rows_segment_t* segs, int nseg, void* st
  *   logits [draws][B][C]  ->  lse [B][C] = log sum_e exp(log_softmax(logits[e])[b][c])
  * log_outputs = lse - log(E_total) (applied when mean_over > 0: lse - log(mean_over)).
  * Ranks of an ensemble-sharded job combine their lse blocks with one more log-sum-exp.
+ * Every entry below subtracts a row's maximum before its log partition, ls = (v - max) - log sum exp(v - max), forward and
+ * backward alike: adding a constant to a row of logits changes no rounding.  classes <= 1024 here and in bbb_uncertainty.
  */
 int bbb_mc_tail(const float* logits, int draws, int batch, int classes, int mean_over,
                 float* lse_out, void* stream);
 
-/* bbb_mc_tail for logits stored batch-innermost, [draws][C][B] (output of the batched ensemble path); lse_out is [B][C]. */
+/* bbb_mc_tail for logits stored batch-innermost, [draws][C][B] (output of the batched ensemble path); lse_out is [B][C].
+ * draws <= 512.  This and the four entries after the ELBO pair are one kernel launched from one plan (csrc/mc_tail_plan.h): one float
+ * of LDS per image and draw the image reduces over, so at most 640 such draws (160 KB; more: BBB_ESHAPE), at most 4096 slabs in a
+ * launch, slices * batch_slice <= 2^31 - 64 images. */
 int bbb_mc_tail_cb(const float* logits, int draws, int batch, int classes, int mean_over,
                    float* lse_out, void* stream);
 /* Backward of bbb_mc_tail_cb (training extension, ABI 12; loss.backward() of main_bayesian.py:57 through log_softmax + logmeanexp):
@@ -697,7 +702,8 @@ int bbb_elbo_cb_bwd(const float* logits, const float* lse, const int64_t* target
 
 /* The same for a rank's WORK UNITS (bbb_conv_desc_t: unit u = unit_off + e is draw u / slices, batch slice u % slices):
  * logits [units][C][batch_slice] -> lse_out [slices * batch_slice][C]; image b of slice s gets the log-sum-exp over the local
- * units of that slice, -inf where the rank holds none (the ranks' blocks are then combined by one more log-sum-exp). */
+ * units of that slice, -inf where the rank holds none (the ranks' blocks are then combined by one more log-sum-exp).
+ * units <= 4096, ceil(units / slices) <= 640; unit_off of any size (taken modulo slices). */
 int bbb_mc_tail_units(const float* logits, int units, int slices, int unit_off, int batch_slice, int classes, int mean_over,
                       float* lse_out, void* stream);
 
@@ -712,7 +718,8 @@ int bbb_mc_tail_units_step(const float* logits, int units, int slices, int unit_
 /* Several Monte-Carlo steps in one set of launches (ABI 8): logits [groups * draws][C][batch] hold `groups` consecutive steps of
  * `draws` forwards each, step g on its own batch (slab g * draws + j = draw j of step g; main_bayesian.py:73-80 run `groups`
  * times) -> lse_out [groups * batch][C], block g = the log-sum-exp over step g's draws (minus log(mean_over) when > 0).
- * kl_in / kl_scale / kl_out / counter / counter_add as in bbb_mc_tail_units_step (all NULL / 0 = plain tail). */
+ * kl_in / kl_scale / kl_out / counter / counter_add as in bbb_mc_tail_units_step (all NULL / 0 = plain tail).
+ * groups * draws <= 4096, draws <= 640. */
 int bbb_mc_tail_groups_step(const float* logits, int groups, int draws, int batch, int classes, int mean_over,
                             float* lse_out, const float* kl_in, float kl_scale, float* kl_out, uint32_t* counter,
                             uint32_t counter_add, void* stream);
@@ -720,7 +727,8 @@ int bbb_mc_tail_groups_step(const float* logits, int groups, int draws, int batc
 /* A RANK'S SHARE of a group of steps (ABI 8): the `slabs` local draws are draws first_off, first_off + 1, ... of the draw-major
  * enumeration (step g, draw j) -> g * draws + j of `steps` consecutive local steps (the share may start and end in the middle of a
  * step): lse_out [steps * batch][C], block k = the log-sum-exp over the LOCAL draws of local step k (no mean; -inf where it holds none);
- * the ranks' blocks are combined by one more log-sum-exp.  kl / counter arguments as in bbb_mc_tail_units_step. */
+ * the ranks' blocks are combined by one more log-sum-exp.  kl / counter arguments as in bbb_mc_tail_units_step.
+ * slabs <= 4096, 0 <= first_off < draws <= 640, first_off + slabs <= steps * draws. */
 int bbb_mc_tail_share_step(const float* logits, int slabs, int steps, int draws, int first_off, int batch, int classes,
                            float* lse_out, const float* kl_in, float kl_scale, float* kl_out, uint32_t* counter,
                            uint32_t counter_add, void* stream);

@@ -1397,8 +1397,14 @@ def avgpool_chwn_bf16(x, kernel, stride, padding=0, count_include_pad=True):
     return y
 
 
+# Draws ONE image reduces over in a batch-innermost tail launch, at most (csrc/mc_tail_plan.h): each takes 64 images x 4 bytes of the
+# workgroup's 160 KB of LDS.  The plain entry and the autograd entries stay at 512 draws.
+MC_TAIL_MAX_PER_SLICE = 640
+MC_TAIL_MAX_DRAWS = 512
+
+
 def mc_tail_cb(logits, mean_over=0, step_end=None):
-    """mc_tail for batch-innermost logits [E, C, B] -> [B, C]."""
+    """mc_tail for batch-innermost logits [E <= 512, C, B] -> [B, C]."""
     return mc_tail_units(logits, 1, 0, mean_over, step_end)
 
 
@@ -1485,20 +1491,21 @@ def elbo_cb_autograd(logits, kl, target, beta, train_size, mean_over=0):
 def mc_tail_cb_autograd(logits, mean_over=0):
     """Differentiable mc_tail_cb: logits [E, C, B] (requires grad) -> lse [B, C]."""
     require_device(logits)
-    if logits.shape[0] > 512:
+    if logits.shape[0] > MC_TAIL_MAX_DRAWS:
         raise _lib.BBBHipError("too many draws for one tail launch")
     return _McTailCB.apply(logits, int(mean_over))
 
 
 def mc_tail_units(logits, slices, unit_off, mean_over=0, step_end=None):
     """mc_tail_cb for a rank's work units: logits [U, C, Bs] (unit u = unit_off + e is draw u // slices, batch slice
-    u % slices) -> [slices * Bs, C]; -inf rows for slices the rank holds no unit of.
+    u % slices) -> [slices * Bs, C]; -inf rows for slices the rank holds no unit of.  U <= 4096 (512 with one slice) and at most
+    640 units per slice (ceil(U / slices): the launch keeps one float per local unit and image in LDS).
     step_end = (kl_one_forward, scale, counter | None, counter_add): the end of a captured Monte-Carlo step in the same launch
     (bbb_mc_tail_units_step) -> returns (lse, kl_one_forward * scale) and adds counter_add to the int32 device counter."""
     require_device(logits)
     logits = logits.contiguous()
     U, C, Bs = logits.shape
-    if U > (512 if int(slices) == 1 else 4096):
+    if int(slices) <= 0 or U > (MC_TAIL_MAX_DRAWS if int(slices) == 1 else 4096) or -(-U // int(slices)) > MC_TAIL_MAX_PER_SLICE:
         raise _lib.BBBHipError("too many draws / units for one tail launch")
     out = torch.empty((int(slices) * Bs, C), dtype=torch.float32, device=logits.device)
     L = _lib.lib()
@@ -1521,12 +1528,12 @@ def mc_tail_units(logits, slices, unit_off, mean_over=0, step_end=None):
 def mc_tail_groups(logits, groups, draws, mean_over=0, step_end=None):
     """Tail of `groups` Monte-Carlo steps that share one set of launches: logits [groups * draws, C, B] (slab g * draws + j =
     draw j of step g) -> [groups * B, C], block g = log-sum-exp over step g's draws of the per-draw log_softmax, minus
-    log(mean_over) when > 0.  step_end as in mc_tail_units."""
+    log(mean_over) when > 0.  groups * draws <= 4096 and draws <= 640 (the LDS of the launch).  step_end as in mc_tail_units."""
     require_device(logits)
     logits = logits.contiguous()
     U, C, B = logits.shape
-    if U != int(groups) * int(draws) or U > 4096:
-        raise _lib.BBBHipError("mc_tail_groups: logits must hold groups * draws <= 4096 slabs")
+    if U != int(groups) * int(draws) or U > 4096 or int(draws) > MC_TAIL_MAX_PER_SLICE:
+        raise _lib.BBBHipError("mc_tail_groups: logits must hold groups * draws <= 4096 slabs of at most 640 draws per step")
     out = torch.empty((int(groups) * B, C), dtype=torch.float32, device=logits.device)
     kl_in, scale, counter, add = step_end if step_end is not None else (None, 0.0, None, 0)
     require_device(kl_in)
@@ -1544,12 +1551,14 @@ def mc_tail_share(logits, steps, draws, first_off, step_end=None):
     """Tail of one rank's share of a GROUP of steps: logits [slabs, C, B], slab e = draw (first_off + e) of the draw-major (step,
     draw) enumeration of `steps` local steps with `draws` draws each -> [steps * B, C], block k = log-sum-exp over the LOCAL draws
     of local step k of the per-draw log_softmax (no mean: the ranks' blocks are combined by one more log-sum-exp; -inf where the
-    share holds no draw of the step).  step_end as in mc_tail_units."""
+    share holds no draw of the step).  0 <= first_off < draws <= 640, slabs <= 4096 and first_off + slabs <= steps * draws.  step_end
+    as in mc_tail_units."""
     require_device(logits)
     logits = logits.contiguous()
     U, C, B = logits.shape
-    if U > 4096 or not 0 <= int(first_off) < int(draws) or int(steps) * int(draws) < U + int(first_off):
-        raise _lib.BBBHipError("mc_tail_share: the slabs must fit the steps * draws grid, <= 4096 slabs")
+    if (U > 4096 or not 0 <= int(first_off) < int(draws) or int(steps) * int(draws) < U + int(first_off)
+            or int(draws) > MC_TAIL_MAX_PER_SLICE):
+        raise _lib.BBBHipError("mc_tail_share: the slabs must fit the steps * draws grid, <= 4096 slabs of at most 640 draws per step")
     out = torch.empty((int(steps) * B, C), dtype=torch.float32, device=logits.device)
     kl_in, scale, counter, add = step_end if step_end is not None else (None, 0.0, None, 0)
     require_device(kl_in)

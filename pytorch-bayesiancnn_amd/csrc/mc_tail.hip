@@ -10,13 +10,38 @@
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
 #include "conv_desc_check.h"
+#include "mc_tail_plan.h"
+#include "smem_attr.h"
 
+// Shift invariance: log_softmax does not change when a constant is added to a row, and neither do these kernels' roundings --
+// every tail kernel forms ls = (v - mx) - logf(se), the row maximum subtracted FIRST (as the sum-exp does), so each rounding
+// scales with the log-probability and not with the size of the logits.  (mx + logf(se) rounds at ulp(|mx|): 4.8e-4 at logits
+// around 1e4.)  Forward and backward use the same order.
 namespace {
 
 constexpr int kMaxPerLane = 16;   // classes <= 64 * 16
 
-__global__ __launch_bounds__(64) void mc_tail_kernel(const float* __restrict__ logits, int E, int B, int C, float sub,
+// log(mean_over) is taken ON THE DEVICE, by the logf that also takes the log of the sum over draws: the log-mean-exp of equal values
+// is then that value exactly (the host's logf and the device's differ in the last bit for some arguments).
+__device__ __forceinline__ float log_mean_over(int mean_over) { return mean_over > 0 ? logf((float)mean_over) : 0.0f; }
+
+// logf(sum_c expf(p[c * stride] - mx)) where ONE thread adds all C terms: a compensated sum.  A plain running sum of 1024 terms was
+// off by 125 ulp on the sweep's cases (tests/tail_contract.py: 62 x the error scale in the log-probabilities, where the wave-reduced
+// mc_tail_kernel and a pairwise sum stay below 4).
+__device__ __forceinline__ float row_log_sum_exp(const float* __restrict__ p, int64_t stride, int C, float mx) {
+    float se = 0.0f, comp = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        const float y = expf(p[(int64_t)c * stride] - mx) - comp;
+        const float t = se + y;
+        comp = (t - se) - y;
+        se = t;
+    }
+    return logf(se);
+}
+
+__global__ __launch_bounds__(64) void mc_tail_kernel(const float* __restrict__ logits, int E, int B, int C, int mean_over,
                                                      float* __restrict__ out) {
+    const float sub = log_mean_over(mean_over);
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
     float run_m[kMaxPerLane], run_s[kMaxPerLane];
@@ -40,12 +65,12 @@ __global__ __launch_bounds__(64) void mc_tail_kernel(const float* __restrict__ l
             if (c < C) se += expf(v[i] - mx);
         }
         se = bbb::wave_sum_all(se);
-        const float lz = mx + logf(se);            // log partition of this draw
+        const float lse_row = logf(se);            // log partition of this draw, relative to its maximum
 #pragma unroll
         for (int i = 0; i < kMaxPerLane; ++i) {
             const int c = lane + i * 64;
             if (c < C) {
-                const float ls = v[i] - lz;         // log_softmax
+                const float ls = (v[i] - mx) - lse_row;       // log_softmax
                 const float nm = fmaxf(run_m[i], ls);
                 run_s[i] = run_s[i] * expf(run_m[i] - nm) + expf(ls - nm);
                 run_m[i] = nm;
@@ -61,10 +86,14 @@ __global__ __launch_bounds__(64) void mc_tail_kernel(const float* __restrict__ l
 
 // Same reduction for logits stored batch-innermost, [E][C][B] (what the batched ensemble path produces): one thread
 // per image, lanes = consecutive images so every read is coalesced; the per-draw log-partition values sit in LDS.
-constexpr int kCbThreads = 64;
-constexpr int kCbRows = 16;
+using mc_tail_plan::kCbThreads;
+using mc_tail_plan::kCbRows;
+constexpr int kCbTile = 4;        // classes a thread carries through one sweep over the draws in phase 2
 // blockDim = (64 images, ny <= 16): phase 1 spreads the draws over y (log-partition of each draw), phase 2 spreads the
 // classes over y (log-sum-exp over draws) -- the serial chain per thread is E*C/ny long instead of E*C.
+// LDS holds one float per (local draw, image), logf(sum-exp) of the draw's row relative to its maximum, and behind them (mx_off > 0:
+// up to 320 draws per image, mc_tail_plan.h) the row maxima; with more draws the second array does not fit and phase 2 finds the
+// maximum again (C reads that hit the cache, once per draw for the kCbTile classes a thread carries).  The same values either way.
 // Work units (ensemble sharding, include/bbb_hip.h): the E slabs are units u = off + e of the draw-major (draw, batch slice)
 // grid with S slices of Bs images; image b = s*Bs + bl reduces over the local units of ITS slice, e = e0, e0 + S, ...
 // (e0 = (s - off) mod S), and gets -inf when the rank holds none.  S = 1, off = 0 is the plain [E][C][B] case.
@@ -75,12 +104,13 @@ constexpr int kCbRows = 16;
 // and counter += counter_add (the device-side noise call counter of include/bbb_hip.h `call_dev`: every kernel that reads it
 // runs before the tail of the same step).
 __global__ __launch_bounds__(kCbThreads * kCbRows) void mc_tail_cb_kernel(const float* __restrict__ logits, int E, int Bs, int S,
-                                                                          int off, int C, float sub, float* __restrict__ out,
+                                                                          int off, int C, int mean_over, float* __restrict__ out,
                                                                           const float* __restrict__ kl_in, float kl_scale,
                                                                           float* __restrict__ kl_out, uint32_t* counter,
-                                                                          uint32_t counter_add, int grp, int goff) {
-    extern __shared__ float lz[];                       // [ceil(E/S)][64]
+                                                                          uint32_t counter_add, int grp, int goff, int mx_off) {
+    extern __shared__ float lz[];                       // [per_slice][64] log sum-exp, then [per_slice][64] maxima (mc_tail_plan.h)
     const int tx = threadIdx.x, ty = threadIdx.y, ny = blockDim.y;
+    const float sub = log_mean_over(mean_over);
     if (blockIdx.x == 0 && tx == 0 && ty == 0) {
         if (kl_out != nullptr) *kl_out = *kl_in * kl_scale;
         if (counter != nullptr) *counter += counter_add;
@@ -101,20 +131,36 @@ __global__ __launch_bounds__(kCbThreads * kCbRows) void mc_tail_cb_kernel(const 
         const float* p = logits + (int64_t)(e0 + k * es) * C * Bs + bl;
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[(int64_t)c * Bs]);
-        float se = 0.0f;
-        for (int c = 0; c < C; ++c) se += expf(p[(int64_t)c * Bs] - mx);
-        lz[k * kCbThreads + tx] = mx + logf(se);
+        lz[k * kCbThreads + tx] = row_log_sum_exp(p, Bs, C, mx);
+        if (mx_off > 0) lz[mx_off + k * kCbThreads + tx] = mx;
     }
     __syncthreads();
-    for (int c = ty; c < C; c += ny) {
-        float m = -INFINITY, s = 0.0f;
+    for (int c0 = ty; c0 < C; c0 += ny * kCbTile) {
+        float m[kCbTile], s[kCbTile];
+#pragma unroll
+        for (int j = 0; j < kCbTile; ++j) { m[j] = -INFINITY; s[j] = 0.0f; }
         for (int k = 0; k < ne; ++k) {
-            const float ls = logits[((int64_t)(e0 + k * es) * C + c) * Bs + bl] - lz[k * kCbThreads + tx];
-            const float nm = fmaxf(m, ls);
-            s = s * expf(m - nm) + expf(ls - nm);
-            m = nm;
+            const float* p = logits + (int64_t)(e0 + k * es) * C * Bs + bl;
+            float mx = -INFINITY;
+            if (mx_off > 0) mx = lz[mx_off + k * kCbThreads + tx];
+            else for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[(int64_t)c * Bs]);
+            const float lse_row = lz[k * kCbThreads + tx];
+#pragma unroll
+            for (int j = 0; j < kCbTile; ++j) {
+                const int c = c0 + j * ny;
+                if (c < C) {
+                    const float ls = (p[(int64_t)c * Bs] - mx) - lse_row;
+                    const float nm = fmaxf(m[j], ls);
+                    s[j] = s[j] * expf(m[j] - nm) + expf(ls - nm);
+                    m[j] = nm;
+                }
+            }
         }
-        if (ok) out[(int64_t)b * C + c] = ne > 0 ? m + logf(s) - sub : -INFINITY;
+#pragma unroll
+        for (int j = 0; j < kCbTile; ++j) {
+            const int c = c0 + j * ny;
+            if (ok && c < C) out[(int64_t)b * C + c] = ne > 0 ? m[j] + logf(s[j]) - sub : -INFINITY;
+        }
     }
 }
 
@@ -441,21 +487,17 @@ __global__ __launch_bounds__(256) void lrt_sample_nchw_kernel(const float* __res
 namespace {
 int mc_tail_launch(const float* logits, int units, int slices, int unit_off, int batch_slice, int classes, int mean_over, float* lse_out,
                    const float* kl_in, float kl_scale, float* kl_out, uint32_t* counter, uint32_t counter_add, int grp, int goff, void* stream) {
-    if ((kl_out != nullptr && kl_in == nullptr) || (((uintptr_t)kl_in | (uintptr_t)kl_out | (uintptr_t)counter) & 3u) != 0) return BBB_EINVAL;
-    if (logits == nullptr || lse_out == nullptr || units <= 0 || slices <= 0 || unit_off < 0 || batch_slice <= 0 || classes <= 0 ||
-        mean_over < 0 || units > 4096 || grp < 0 || goff < 0 || (grp > 0 && (goff >= grp || (int64_t)grp * slices < (int64_t)units + goff)))
-        return BBB_EINVAL;
-    if ((((uintptr_t)logits | (uintptr_t)lse_out) & 3u) != 0) return BBB_EALIGN;
-    const float sub = mean_over > 0 ? logf((float)mean_over) : 0.0f;
-    const int64_t batch = (int64_t)batch_slice * slices;
-    if (batch > 0x7fffffffLL) return BBB_ESHAPE;
-    const int blocks = (int)((batch + kCbThreads - 1) / kCbThreads);
-    const int per_slice = grp > 0 ? grp : (units + slices - 1) / slices;   // local units an image reduces over, at most
-    const int mx = per_slice > classes ? per_slice : classes;
-    const int ny = mx < kCbRows ? mx : kCbRows;
-    hipLaunchKernelGGL(mc_tail_cb_kernel, dim3(blocks), dim3(kCbThreads, ny), (size_t)per_slice * kCbThreads * sizeof(float),
-                       (hipStream_t)stream, logits, units, batch_slice, slices, unit_off, classes, sub, lse_out, kl_in, kl_scale, kl_out,
-                       counter, counter_add, grp, goff);
+    mc_tail_plan::Plan p;
+    if (const int rc = mc_tail_plan::plan(logits, lse_out, kl_in, kl_out, counter, units, slices, unit_off, batch_slice, classes, mean_over,
+                                          grp, goff, &p))
+        return rc;
+    if (p.lds_bytes > mc_tail_plan::kDefaultLdsBytes) {     // (more than 256 draws per image: beyond what a kernel gets unasked)
+        static SmemAttrState attr_state;
+        if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(mc_tail_cb_kernel), p.lds_bytes, attr_state)) return rc;
+    }
+    hipLaunchKernelGGL(mc_tail_cb_kernel, dim3(p.blocks), dim3(kCbThreads, p.ny), (size_t)p.lds_bytes,
+                       (hipStream_t)stream, logits, units, batch_slice, slices, unit_off, classes, mean_over, lse_out, kl_in, kl_scale, kl_out,
+                       counter, counter_add, grp, goff, p.keep_max ? p.per_slice * kCbThreads : 0);
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -500,7 +542,7 @@ namespace {
 template <bool ELBO>
 __global__ __launch_bounds__(256) void mc_tail_cb_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
                                                              const float* __restrict__ g, float* __restrict__ g_logits, int E, int C, int B,
-                                                             float add, const int64_t* __restrict__ target, const float* __restrict__ g_loss,
+                                                             int mean_over, const int64_t* __restrict__ target, const float* __restrict__ g_loss,
                                                              float gscale, float beta, const float* __restrict__ beta_dev,
                                                              float* __restrict__ g_kl) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -514,31 +556,30 @@ __global__ __launch_bounds__(256) void mc_tail_cb_bwd_kernel(const float* __rest
     const float* p = logits + (int64_t)e * C * B + b;
     float mx = -INFINITY;
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[(int64_t)c * B]);
-    float se = 0.0f;
-    for (int c = 0; c < C; ++c) se += expf(p[(int64_t)c * B] - mx);
-    const float lz = mx + logf(se);
+    const float lse_row = row_log_sum_exp(p, B, C, mx);       // (the forward's own value: same order, same sum)
+    const float add = log_mean_over(mean_over);
     float* o = g_logits + (int64_t)e * C * B + b;
     if (ELBO) {
         const int64_t t = target[b];
         float h = 0.0f, sum_h = 0.0f;
         if (t >= 0 && t < C) {
-            const float ls = p[t * B] - lz;
+            const float ls = (p[t * B] - mx) - lse_row;
             h = -gscale * gl * expf(ls - (lse[(int64_t)b * C + t] + add));
             sum_h = h;
         }
         for (int c = 0; c < C; ++c) {
-            const float ls = p[(int64_t)c * B] - lz;
+            const float ls = (p[(int64_t)c * B] - mx) - lse_row;
             o[(int64_t)c * B] = (c == t ? h : 0.0f) - expf(ls) * sum_h;
         }
         return;
     }
     float sum_h = 0.0f;
     for (int c = 0; c < C; ++c) {
-        const float ls = p[(int64_t)c * B] - lz;
+        const float ls = (p[(int64_t)c * B] - mx) - lse_row;
         sum_h += g[(int64_t)b * C + c] * expf(ls - (lse[(int64_t)b * C + c] + add));
     }
     for (int c = 0; c < C; ++c) {
-        const float ls = p[(int64_t)c * B] - lz;
+        const float ls = (p[(int64_t)c * B] - mx) - lse_row;
         const float h = g[(int64_t)b * C + c] * expf(ls - (lse[(int64_t)b * C + c] + add));
         o[(int64_t)c * B] = h - expf(ls) * sum_h;
     }
@@ -575,7 +616,7 @@ extern "C" int bbb_mc_tail_cb_bwd(const float* logits, const float* lse, const f
     const int64_t blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
     hipLaunchKernelGGL(mc_tail_cb_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, lse, g_lse, g_logits,
-                       draws, classes, batch, mean_over > 0 ? logf((float)mean_over) : 0.0f, (const int64_t*)nullptr, (const float*)nullptr,
+                       draws, classes, batch, mean_over, (const int64_t*)nullptr, (const float*)nullptr,
                        0.0f, 0.0f, (const float*)nullptr, (float*)nullptr);
     return (int)hipGetLastError();
 }
@@ -603,7 +644,7 @@ extern "C" int bbb_elbo_cb_bwd(const float* logits, const float* lse, const int6
     const int64_t blocks = (n + 255) / 256;
     if (blocks > 0x7fffffffLL) return BBB_ESHAPE;
     hipLaunchKernelGGL(mc_tail_cb_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, lse,
-                       (const float*)nullptr, g_logits, draws, classes, batch, mean_over > 0 ? logf((float)mean_over) : 0.0f, target, g_loss,
+                       (const float*)nullptr, g_logits, draws, classes, batch, mean_over, target, g_loss,
                        train_size / (float)batch, beta, beta_dev, g_kl);
     return (int)hipGetLastError();
 }
@@ -641,8 +682,7 @@ extern "C" int bbb_mc_tail(const float* logits, int draws, int batch, int classe
         mean_over < 0)
         return BBB_EINVAL;
     if ((((uintptr_t)logits | (uintptr_t)lse_out) & 3u) != 0) return BBB_EALIGN;
-    const float sub = mean_over > 0 ? logf((float)mean_over) : 0.0f;
-    hipLaunchKernelGGL(mc_tail_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, logits, draws, batch, classes, sub, lse_out);
+    hipLaunchKernelGGL(mc_tail_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, logits, draws, batch, classes, mean_over, lse_out);
     return (int)hipGetLastError();
 }
 
