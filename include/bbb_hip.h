@@ -167,7 +167,8 @@ typedef struct bbb_conv_desc {
     int64_t x_draw_stride; /* elements between draws of x (0 = every draw reads the same x) */
     int64_t w_draw_stride; /* elements between draws of w (0 = shared weights) */
     int64_t b_draw_stride; /* elements between draws of bias (0 = shared) */
-    int32_t act;          /* fused epilogue: 0 none, 1 ReLU, 2 Softplus(beta=1, threshold=20) */
+    int32_t act;          /* fused epilogue: 0 none, 1 ReLU, 2 Softplus(beta=1, threshold=20).  A NaN pre-activation gives a NaN, as
+                             torch.relu / F.softplus do (never 0 or 20); +Inf stays +Inf, -Inf becomes 0. */
     /* Work units for ensemble sharding (batch-innermost entry points only; all zero = every slab is a whole draw).
      * With unit_div = S > 1 the `draws` slabs of a launch are UNITS u = unit_off + e of the draw-major grid
      * (Monte-Carlo draw, batch slice): draw = u / S, slice = u % S, `batch` = images per slice.  Slab e then reads
@@ -431,7 +432,9 @@ int bbb_conv2d_chwn_plan(const bbb_conv_desc_t* d, int lrt, int k_split, int has
  * Pooling on batch-innermost planes x [planes][h][w][B] -> y [planes][ho][wo][B] (csrc/pool2d.hip; bf16 planes: csrc/pool2d_bf16.hip),
  * one descriptor and one plan (csrc/pool_plan.h) for both kinds.  The output map is floor mode's, ho = (h + 2 pad_h - kh) / stride_h + 1.
  *   BBB_POOL_MAX  nn.MaxPool2d(kernel_size=k, stride=s) (no padding, floor mode; models/BayesianModels/BayesianAlexNet.py:37): a square
- *                 window, one stride, no padding, count_include_pad 0 -- what the maximum kernels implement.  Its launch entries take
+ *                 window, one stride, no padding, count_include_pad 0 -- what the maximum kernels implement.  Every maximum of the
+ *                 forward (these entries, the S3 / c8 S3 pools and the pooled conv forms) keeps a NaN wherever it sits in the
+ *                 window, as F.max_pool2d does.  Its launch entries take
  *                 scalars (bbb_maxpool_chwn, bbb_pool_act_bwd_chwn, bbb_lrt_pool_act_bwd_chwn, and on bf16 planes bbb_maxpool_chwn_bf16,
  *                 bbb_pool_act_bwd_chwn_bf16) and build this descriptor themselves; a backward's k = 0 (the activation alone) is
  *                 planned as the 1 x 1 window at stride 1.

@@ -141,12 +141,19 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return a * b;
 }
 
+// Non-finite values, ONE rule for every activation and every pooling maximum of the forward: a NaN operand gives a NaN result, as
+// torch.relu / F.softplus / F.max_pool2d do (fmaxf and med3(a, b, +inf) return the OTHER operand, which turns a broken batch into
+// finite logits).  max_nan is the IEEE 754-2019 `maximum`: one v_maximum3_f32 on gfx950, no canonicalisation of the operands, and an
+// intrinsic the compiler sees (it keeps the wait states a read of MFMA results needs).  On finite operands it is bitwise fmaxf.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return max_nan(v, 0.0f); }
+
 __device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
+    if (act == 1) return relu_nan(v);
     if (act == 2) {
         const float t = __builtin_amdgcn_exp2f(fminf(v, 20.0f) * 1.4426950408889634f);
         const float sp = 0.6931471805599453f * __builtin_amdgcn_logf(1.0f + t);
-        return v > 20.0f ? v : sp;
+        return !(v <= 20.0f) ? v : sp;          // (the select this way round: a NaN takes the `v` arm)
     }
     return v;
 }

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64 * WN * WM * KG + (WS ? 256 : 0)) void pconv_bf16
         };
         // one branch on the activation kind instead of one per element
         if (p.act == 2)      stage_block([](float v) { return bbb::apply_act(v, 2); });
-        else if (p.act == 1) stage_block([](float v) { return fmaxf(v, 0.0f); });
+        else if (p.act == 1) stage_block([](float v) { return bbb::relu_nan(v); });
         else                 stage_block([](float v) { return v; });
         // same-wave LDS accesses complete in order, so no s_barrier is needed between the writes above and the reads
         // below -- but the compiler must not move the (differently typed) vector reads above the 2-byte writes
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void pconv_bf16_smallk_kernel(const PConvArgs 
                 }
         };
         if (p.act == 2)      stage_block([](float v) { return bbb::apply_act(v, 2); });
-        else if (p.act == 1) stage_block([](float v) { return fmaxf(v, 0.0f); });
+        else if (p.act == 1) stage_block([](float v) { return bbb::relu_nan(v); });
         else                 stage_block([](float v) { return v; });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -760,10 +760,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT == 1 ? 2
             // this conv pixel into its windows (fp32 contraction results: the epilogue comes after the maximum).  Both running maxima
             // are updated UNCONDITIONALLY: `pold` is dead between the column that closes its window and the next window start (where
             // it is overwritten), `pnew` is dead past the strip's last window start -- so values outside a window only ever land in
-            // a register nobody reads.  One instruction per maximum: med3(a, v, +inf) = max(a, v) (fmaxf canonicalises its operands first;
-            // both are arithmetic results) -- 2 VALU instructions per accumulator element instead of ~8 (strip form 124.6 -> 111 us at 16
-            // steps per launch).  An intrinsic, not inline asm: the compiler must see the read of the MFMA's result registers to
-            // keep the wait states that hazard needs (an asm v_max_f32 here computed wrong maxima once the schedule changed).
+            // a register nobody reads (a NaN there is dropped with it: a window start overwrites the register).  One instruction per
+            // maximum: bbb::max_nan, the NaN-propagating v_maximum3_f32 (fmaxf canonicalises its operands first, and drops a NaN)
+            // -- 2 VALU instructions per accumulator element instead of ~8 (strip form 124.6 -> 111 us at 16 steps per launch).
+            // An intrinsic, not inline asm: the compiler must see the read of the MFMA's result registers to keep the wait states
+            // that hazard needs (an asm v_max_f32 here computed wrong maxima once the schedule changed).
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -771,8 +772,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT == 1 ? 2
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float v = acc[nt][mt][r];
-                        pnew[nt][mt][r] = __builtin_amdgcn_fmed3f(pnew[nt][mt][r], v, __builtin_inff());
-                        pold[nt][mt][r] = __builtin_amdgcn_fmed3f(pold[nt][mt][r], v, __builtin_inff());
+                        pnew[nt][mt][r] = bbb::max_nan(pnew[nt][mt][r], v);
+                        pold[nt][mt][r] = bbb::max_nan(pold[nt][mt][r], v);
                     }
             // a window is complete after the last row of its last column: older window first (overlapping windows), else the
             // newest (pk <= ps); the host admits only geometries where at most one window closes per column
@@ -815,11 +816,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NT == 1 ? 2
                 };
                 if constexpr (C8) {
                     if (p.act == 2)      store_c8([](float v) { return bbb::apply_act(v, 2); });
-                    else if (p.act == 1) store_c8([](float v) { return fmaxf(v, 0.0f); });
+                    else if (p.act == 1) store_c8([](float v) { return bbb::relu_nan(v); });
                     else                 store_c8([](float v) { return v; });
                 } else {
                     if (p.act == 2)      stage_block([](float v) { return bbb::apply_act(v, 2); });
-                    else if (p.act == 1) stage_block([](float v) { return fmaxf(v, 0.0f); });
+                    else if (p.act == 1) stage_block([](float v) { return bbb::relu_nan(v); });
                     else                 stage_block([](float v) { return v; });
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -990,9 +991,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     uint16_t* T = Tall + wave * (32 * TP);
-    // max without the canonicalisation fmaxf asks for (both operands are arithmetic results): ONE instruction per element
-    // (med3(x, y, +inf) = max(x, y); an intrinsic rather than an asm v_max_f32, so that the compiler sees the read of MFMA results)
-    auto vmax = [](float x, float y) { return __builtin_amdgcn_fmed3f(x, y, __builtin_inff()); };
+    // max without the canonicalisation fmaxf asks for, and keeping a NaN (bbb_common.cuh): ONE instruction per element
+    // (an intrinsic rather than an asm v_max_f32, so that the compiler sees the read of MFMA results)
+    auto vmax = [](float x, float y) { return bbb::max_nan(x, y); };
 
     f32x16 pnew, pold;
 #pragma unroll
@@ -1278,7 +1279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         };
         if (p.act == 2)      emit([](float v) { return bbb::apply_act(v, 2); });
-        else if (p.act == 1) emit([](float v) { return fmaxf(v, 0.0f); });
+        else if (p.act == 1) emit([](float v) { return bbb::relu_nan(v); });
         else                 emit([](float v) { return v; });
         return;
     }
@@ -1296,7 +1297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             T[(nt * 32 + 8 * r4 + 4 * lk + i) * TP + lrow] = f2bf(act(acc[j][nt][r4 * 4 + i] + bq[nt][r4][i]));
             };
             if (p.act == 2)      stage_block([](float v) { return bbb::apply_act(v, 2); });
-            else if (p.act == 1) stage_block([](float v) { return fmaxf(v, 0.0f); });
+            else if (p.act == 1) stage_block([](float v) { return bbb::relu_nan(v); });
             else                 stage_block([](float v) { return v; });
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll

@@ -414,7 +414,7 @@ __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t ite
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     const float v = bbb::apply_act(acc[nt][mt][r] + bn, p.act);
-                    agpr_write(tot[nt][mt][r], fmaxf(agpr_read(tot[nt][mt][r]), v));
+                    agpr_write(tot[nt][mt][r], bbb::max_nan(agpr_read(tot[nt][mt][r]), v));
                     acc[nt][mt][r] = 0.0f;
                 }
             }
@@ -452,7 +452,7 @@ __device__ __forceinline__ void pconv_item(const PConvArgs& p, const int64_t ite
                         v = v + __builtin_amdgcn_sqrtf(var) * z;
                     }
                     v = bbb::apply_act(v, p.act);
-                    agpr_write(tot[nt][mt][r], fmaxf(agpr_read(tot[nt][mt][r]), v));
+                    agpr_write(tot[nt][mt][r], bbb::max_nan(agpr_read(tot[nt][mt][r]), v));
                     acc[nt][mt][r] = 0.0f;
                     accv[nt][mt][r] = 0.0f;
                     __builtin_amdgcn_sched_barrier(0);     // one element's Philox at a time: interleaved, sixteen of them hold ~90 VGPRs

@@ -468,7 +468,7 @@ void pconv_c8x3_kernel(const PConvArgs p) {
                     for (int w2 = 1; w2 < 4; ++w2) {
                         const f32x4 u = ex4[(w2 * 4 + wave) * 64 + lane];
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) v[c] = fmaxf(v[c], u[c]);
+                        for (int c = 0; c < 4; ++c) v[c] = bbb::max_nan(v[c], u[c]);
                     }
                     const float o4[4] = {v[0], v[1], v[2], v[3]};
                     store4(o4, n0 + nt * 32 + 8 * wave, b0 + mt * 32 + lrow, pix, opixels);

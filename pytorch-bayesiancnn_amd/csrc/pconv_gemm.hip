@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void maxpool_s3_kernel(const unsigned short* _
             float v[8];
             s3_join(xp[o], xp[o + xps], xp[o + 2 * xps], v);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) best[u] = (a == 0 && q == 0) ? v[u] : fmaxf(best[u], v[u]);
+            for (int u = 0; u < 8; ++u) best[u] = (a == 0 && q == 0) ? v[u] : bbb::max_nan(best[u], v[u]);
         }
     s3_u32x4 h, m, l;
     s3_cut(best, h, m, l);

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "bbb_common.cuh"
 #include "pool_act_bwd.cuh"
 #include "pool_plan.h"
 
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256) void maxpool_chwn_kernel(const float* __restri
         for (int c = 0; c < k; ++c) {
             const f32x4 v = xp[((int64_t)a * W + c) * B4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) m[u] = fmaxf(m[u], v[u]);
+            for (int u = 0; u < 4; ++u) m[u] = bbb::max_nan(m[u], v[u]);
         }
     reinterpret_cast<f32x4*>(y)[i] = m;
 }

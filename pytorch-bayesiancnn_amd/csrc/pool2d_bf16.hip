@@ -54,8 +54,8 @@ __global__ __launch_bounds__(256) void maxpool_chwn_bf16_kernel(const u32x4* __r
             const u32x4 v = xp[((int64_t)a * W + c) * B8];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                m[2 * u] = fmaxf(m[2 * u], __builtin_bit_cast(float, v[u] << 16));
-                m[2 * u + 1] = fmaxf(m[2 * u + 1], __builtin_bit_cast(float, v[u] & 0xFFFF0000u));
+                m[2 * u] = bbb::max_nan(m[2 * u], __builtin_bit_cast(float, v[u] << 16));
+                m[2 * u + 1] = bbb::max_nan(m[2 * u + 1], __builtin_bit_cast(float, v[u] & 0xFFFF0000u));
             }
         }
     u32x4 o;
