@@ -744,6 +744,36 @@ int bbb_mc_tail_share_step(const float* logits, int slabs, int steps, int draws,
 int bbb_uncertainty(const float* logits, int draws, int batch, int classes, int normalized,
                     float* pred, float* epistemic, float* aleatoric, void* stream);
 
+/*
+ * Uncertainty scores of batch-innermost logits in ONE launch (additive to ABI 13): logits [draws][C][B] fp32, as the batched
+ * ensemble path leaves them -- no transpose, no atomics, lanes = 64 consecutive images.  With p_t = softmax(logits[t]) over the
+ * classes (normalized != 0: softplus(v) / sum softplus(v), softplus(v) = v for v > 20) and p_bar = (1/draws) sum_t p_t:
+ *   pred, p_mean, epistemic, aleatoric [B][C]: mean logit, p_bar, (1/draws) sum_t (p_t - p_bar)^2 (second pass over the draws,
+ *                                              no cancellation), p_bar - (1/draws) sum_t p_t^2
+ *   entropy, expected_entropy, mutual_info [B]: H[p_bar] = -sum_c p_bar log p_bar, (1/draws) sum_t H[p_t], and
+ *                                              (1/draws) sum_t sum_c p_t (log p_t - log p_bar) -- the KL form, clamped below at 0,
+ *                                              not the difference of the two entropies (which loses the small values)
+ * log p_t is the log-softmax in the order of the tail entries, (v - max) - log sum exp(v - max); normalized: log softplus(v) -
+ * log sum softplus.  A term with p = 0 contributes exactly 0 (a class at -inf does not make an entropy NaN); with draws = 1
+ * log p_bar IS log p_t, so epistemic and mutual_info are exactly 0.  Image b's results depend on its own draws x C logits only.
+ * Any output pointer may be NULL: that output is not written, the others keep their bits.
+ * Limits (csrc/mc_uncertainty_plan.h): draws <= 202 -- a workgroup keeps three floats per (draw, image) and 8 KB of row partials
+ * in its 160 KB of LDS; batch <= INT32_MAX - 63; any classes.  Checks in this order: BBB_EINVAL (NULL logits, a size that is not
+ * positive, all seven outputs NULL), BBB_EALIGN (a pointer that is not 4-byte aligned), BBB_ESHAPE (batch or draws beyond the
+ * limits).
+ */
+int bbb_mc_uncertainty_cb(const float* logits, int draws, int batch, int classes, int normalized, float* pred, float* p_mean,
+                          float* epistemic, float* aleatoric, float* entropy, float* expected_entropy, float* mutual_info,
+                          void* stream);
+
+/* What bbb_mc_uncertainty_cb launches for these arguments, without the launch (host only, needs no device): the same checks and
+ * return codes; *rows: rows of the 64-lane block, min(16, max(draws, classes)); *blocks: ceil(batch / 64); *lds_bytes: the dynamic
+ * LDS of the launch, draws * 768 + 8192.  Each of the three may be NULL. */
+int bbb_mc_uncertainty_cb_plan(const float* logits, int draws, int batch, int classes, const float* pred, const float* p_mean,
+                               const float* epistemic, const float* aleatoric, const float* entropy,
+                               const float* expected_entropy, const float* mutual_info, int32_t* rows, int32_t* blocks,
+                               int32_t* lds_bytes);
+
 /* [rows][cols] -> [cols][rows] (e.g. an NCHW batch [B][C*H*W] into the batch-innermost [C*H*W][B] layout). */
 int bbb_transpose2d(const float* in, float* out, int64_t rows, int64_t cols, void* stream);
 

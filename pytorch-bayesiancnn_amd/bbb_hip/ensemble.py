@@ -662,6 +662,21 @@ def mc_logits(net, x, draws, seed, call0, fuse_act=True, timers=None, eps=None, 
     return h, kl
 
 
+def mc_logits_cb(net, x, draws, seed, call0, precision="fp32"):
+    """mc_logits for consumers that reduce batch-innermost logits (uncertainty.mc_uncertainty): -> (logits [E, C, B'], kl of ONE
+    forward), the same numbers as mc_logits(...).permute(0, 2, 1).  Where the batch-innermost inference path applies, its own buffer
+    comes back without a copy (a view of it when the batch was padded) and stats["path"] is as for mc_logits; elsewhere mc_logits
+    runs as always and its result is transposed once.  precision and its refusals: those of mc_logits."""
+    _check_precision(precision, net, x, True)
+    if _chwn_ok(net, x):
+        _lib.require_device(x)
+        out = _mc_logits_chwn(net, x, draws, seed, call0, precision=precision)
+        if out is not None:
+            return out
+    logits, kl = mc_logits(net, x, draws, seed, call0, precision=precision)
+    return logits.permute(0, 2, 1).contiguous(), kl
+
+
 def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None, streams=1, precision="fp32", units=None, b_offset=0,
                step_end=None, groups=1, param_alias=None, share=None, elbo=None):
     """(log-sum-exp over the local draws of the per-draw log_softmax [B, C], kl of one forward), staying in the

@@ -6,6 +6,7 @@ gradients run on the SAME fp32-MFMA implicit-GEMM kernel as the forward (wgrad =
 flipped-weight convolution of the stride-upsampled output gradient) -- no ATen / MIOpen / rocBLAS convolution or GEMM
 anywhere.  Activations, pooling and the loss tail use torch autograd (element-wise ops) in this mode.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -302,8 +303,8 @@ def graph_capture(graph, stream=None):
 class LaunchConfig:
     """The launch-shape / arithmetic-mode choices of the batch-innermost path, as ONE object instead of process-wide switches.
 
-    A `GraphedMC` / `GraphedPipeline` / `GraphedLogits` / `GraphedTrainStep` snapshots the configuration that is current when it
-    is built (or takes `launch_config=`) and enqueues every launch under it, so two models -- or two pipelines of one model --
+    A `GraphedMC` / `GraphedPipeline` / `GraphedLogits` / `GraphedTrainStep` / `GraphedUncertainty` snapshots the configuration that
+    is current when it is built (or takes `launch_config=`) and enqueues every launch under it, so two models -- or two pipelines of one model --
     with different modes coexist in one process and on several threads.  `ops.gemm_mode = ...` and friends still exist: they
     read / write the fields of the process DEFAULT configuration (what applies when nobody asked for anything else).
 
@@ -1582,6 +1583,31 @@ def uncertainty(logits, normalized=False):
         check(_lib.lib().bbb_uncertainty(logits.data_ptr(), T, B, C, 1 if normalized else 0, outs[0].data_ptr(),
                                          outs[1].data_ptr(), outs[2].data_ptr(), cur_stream(logits.device)), "bbb_uncertainty")
     return tuple(outs)
+
+
+# Draws one bbb_mc_uncertainty_cb launch takes (csrc/mc_uncertainty_plan.h): three floats per (draw, image) and 8 KB of row partials
+# in the workgroup's 160 KB of LDS.
+MC_UNCERTAINTY_MAX_DRAWS = 202
+Uncertainty = collections.namedtuple("Uncertainty", "pred p_mean epistemic aleatoric entropy expected_entropy mutual_info")
+
+
+def mc_uncertainty_cb(logits_cb, normalized=False, want=None):
+    """Batch-innermost logits [T <= 202, C, B] -> ops.Uncertainty in one launch (bbb_mc_uncertainty_cb): pred, p_mean, epistemic,
+    aleatoric [B, C] and entropy, expected_entropy, mutual_info [B], device tensors.  want: the field names to compute (None: all
+    seven); the other fields are None, and a field's bits do not depend on what else was asked for."""
+    require_device(logits_cb)
+    want = Uncertainty._fields if want is None else tuple(want)
+    unknown = [w for w in want if w not in Uncertainty._fields]
+    if unknown or not want:
+        raise _lib.BBBHipError(f"want must name at least one of {Uncertainty._fields}, got {want!r}")
+    logits_cb = logits_cb.contiguous()
+    T, C, B = logits_cb.shape
+    outs = [torch.empty((B, C) if i < 4 else (B,), dtype=torch.float32, device=logits_cb.device) if f in want else None
+            for i, f in enumerate(Uncertainty._fields)]
+    with on_device(logits_cb.device):
+        check(_lib.lib().bbb_mc_uncertainty_cb(logits_cb.data_ptr(), T, B, C, 1 if normalized else 0, *[ptr(t) for t in outs],
+                                               cur_stream(logits_cb.device)), "bbb_mc_uncertainty_cb")
+    return Uncertainty(*outs)
 
 
 def to_batch_innermost(x):

@@ -1,0 +1,195 @@
+// Uncertainty scores of T Monte-Carlo forwards on batch-innermost logits, [T][C][B], in one launch on gfx950: the mean logit, the mean
+// probability, the epistemic / aleatoric split of bbb_uncertainty, and the three entropy scores (predictive entropy, expected entropy,
+// mutual information).  No transpose, no atomics; a result never depends on which workgroup ran first.
+//
+// blockDim = (64 images, ny <= 16), lanes = consecutive images so every read is coalesced (as mc_tail_cb_kernel).
+//   Phase 1, rows over draws: per (draw, image) the row's maximum, its log partition logf(sum exp(v - mx)) and the entropy H[p_t] go
+//   into LDS (normalized: the softplus sum, its logarithm, H[p_t]).  ONE thread adds the C terms of a row: compensated sums.
+//   Phase 2, rows over classes: per (image, class) a first sweep over the draws for sum v, sum p, sum p^2, then -- p_bar known -- a
+//   second sweep for sum (p - p_bar)^2 and the KL sum p (log p - log p_bar).  A thread's shares of sum_c p_bar log p_bar and of the KL
+//   sum (compensated over its classes) go into LDS; row 0 adds the rows in ascending order and writes the three per-image scores.
+// log p_t = (v - mx) - log partition, the max-first order of the tail kernels (mc_tail.hip), and p_t = expf(log p_t); normalized:
+// p_t = q / z, log p_t = logf(q) - logf(z) with q = softplus(v).  A term with p = 0 contributes exactly 0 (0 * -inf never forms);
+// the tests `p == 0.0f` are false for NaN, so a NaN stays a NaN.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/bbb_hip.h"
+#include "mc_uncertainty_plan.h"
+#include "smem_attr.h"
+
+namespace {
+
+using mc_uncertainty_plan::kThreads;
+using mc_uncertainty_plan::kRows;
+
+struct UncOut {
+    float *pred, *p_mean, *epi, *ale, *ent, *exp_ent, *mi;
+};
+
+// Compensated running sum (as row_log_sum_exp in mc_tail.hip: a plain sum of 1024 terms was 125 ulp off).
+struct Comp {
+    float s = 0.0f, c = 0.0f;
+    __device__ __forceinline__ void add(float x) {
+        const float y = x - c;
+        const float t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
+__device__ __forceinline__ float softplus20(float v) { return v > 20.0f ? v : log1pf(expf(v)); }      // as uncertainty_kernel
+
+// (log p, p) of one logit; a = the row's maximum (NORM: its softplus sum), lz = the row's log partition.
+template <bool NORM>
+__device__ __forceinline__ void prob(float v, float a, float lz, float* ls, float* p) {
+    if (NORM) {
+        const float q = softplus20(v);
+        *ls = logf(q) - lz;
+        *p = q / a;
+    } else {
+        *ls = (v - a) - lz;
+        *p = expf(*ls);
+    }
+}
+
+// f(i, p[i * stride]) for i = 0 .. n - 1 in ascending order, four loads in flight: every loop of the kernel is a chain of dependent
+// adds behind a strided read, and one read per trip leaves the kernel waiting on memory (the order of the arithmetic is untouched).
+template <class F>
+__device__ __forceinline__ void strided(const float* __restrict__ p, int64_t stride, int n, F f) {
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = p[(i + j) * stride];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f(i + j, v[j]);
+    }
+    for (; i < n; ++i) f(i, p[i * stride]);
+}
+
+template <bool NORM>
+__global__ __launch_bounds__(kThreads * kRows) void mc_uncertainty_cb_kernel(const float* __restrict__ logits, int T, int C, int B,
+                                                                             const UncOut o) {
+    extern __shared__ float lds[];
+    const int tx = threadIdx.x, ty = threadIdx.y, ny = blockDim.y;
+    float* s_a = lds;                           // [T][64] row maximum (NORM: softplus sum)
+    float* s_l = lds + T * kThreads;            // [T][64] log partition
+    float* s_h = lds + 2 * T * kThreads;        // [T][64] H[p_t]
+    float* red = lds + 3 * T * kThreads;        // [2][ny][64] the rows' shares of sum_c p_bar log p_bar and of the KL sum
+    const int b = blockIdx.x * kThreads + tx;
+    const bool ok = b < B;
+    const int bb = ok ? b : B - 1;
+    const int64_t slab = (int64_t)C * B;
+    for (int t = ty; t < T; t += ny) {
+        const float* p = logits + t * slab + bb;
+        float a;
+        Comp z;
+        if (NORM) {
+            strided(p, B, C, [&](int, float v) { z.add(softplus20(v)); });
+            a = z.s;
+        } else {
+            float mx = -INFINITY;
+            strided(p, B, C, [&](int, float v) { mx = fmaxf(mx, v); });
+            strided(p, B, C, [&](int, float v) { z.add(expf(v - mx)); });
+            a = mx;
+        }
+        const float lz = logf(z.s);
+        Comp h;
+        strided(p, B, C, [&](int, float v) {
+            float ls, pr;
+            prob<NORM>(v, a, lz, &ls, &pr);
+            h.add(pr == 0.0f ? 0.0f : pr * ls);
+        });
+        s_a[t * kThreads + tx] = a;
+        s_l[t * kThreads + tx] = lz;
+        s_h[t * kThreads + tx] = -h.s;
+    }
+    __syncthreads();
+    const float fT = (float)T;
+    Comp ent, kl;
+    for (int c = ty; c < C; c += ny) {
+        const float* p = logits + (int64_t)c * B + bb;
+        float s_v = 0.0f, s_p = 0.0f, s_p2 = 0.0f;
+        strided(p, slab, T, [&](int t, float v) {
+            float ls, pr;
+            prob<NORM>(v, s_a[t * kThreads + tx], s_l[t * kThreads + tx], &ls, &pr);
+            s_v += v;
+            s_p += pr;
+            s_p2 += pr * pr;
+        });
+        const float pbar = s_p / fT;
+        const float lpbar = logf(pbar);
+        float s_d2 = 0.0f, s_kl = 0.0f;
+        strided(p, slab, T, [&](int t, float v) {
+            float ls, pr;
+            prob<NORM>(v, s_a[t * kThreads + tx], s_l[t * kThreads + tx], &ls, &pr);
+            const float d = pr - pbar;
+            s_d2 += d * d;
+            const float lpb = T == 1 ? ls : lpbar;          // one draw: log p_bar IS log p_t (logf(expf(ls)) is not ls in every bit)
+            s_kl += (pr == 0.0f || pbar == 0.0f) ? 0.0f : pr * (ls - lpb);
+        });
+        ent.add(pbar == 0.0f ? 0.0f : pbar * lpbar);
+        kl.add(s_kl);
+        if (ok) {
+            const int64_t i = (int64_t)b * C + c;
+            if (o.pred != nullptr) o.pred[i] = s_v / fT;
+            if (o.p_mean != nullptr) o.p_mean[i] = pbar;
+            if (o.epi != nullptr) o.epi[i] = s_d2 / fT;
+            if (o.ale != nullptr) o.ale[i] = pbar - s_p2 / fT;
+        }
+    }
+    red[ty * kThreads + tx] = ent.s;
+    red[(ny + ty) * kThreads + tx] = kl.s;
+    __syncthreads();
+    if (ty == 0 && ok) {
+        float e = 0.0f, m = 0.0f, h = 0.0f;
+        for (int r = 0; r < ny; ++r) {
+            e += red[r * kThreads + tx];
+            m += red[(ny + r) * kThreads + tx];
+        }
+        for (int t = 0; t < T; ++t) h += s_h[t * kThreads + tx];
+        m /= fT;
+        if (o.ent != nullptr) o.ent[b] = -e;
+        if (o.exp_ent != nullptr) o.exp_ent[b] = h / fT;
+        if (o.mi != nullptr) o.mi[b] = m < 0.0f ? 0.0f : m;        // (not fmaxf: a NaN stays)
+    }
+}
+
+template <bool NORM>
+int launch(const float* logits, int draws, int batch, int classes, const UncOut& o, const mc_uncertainty_plan::Plan& p, hipStream_t stream) {
+    if (p.lds_bytes > mc_uncertainty_plan::kDefaultLdsBytes) {      // (more than 74 draws: beyond what a kernel gets unasked)
+        static SmemAttrState attr_state;
+        if (const int rc = ensure_dynamic_smem(reinterpret_cast<const void*>(mc_uncertainty_cb_kernel<NORM>), p.lds_bytes, attr_state))
+            return rc;
+    }
+    hipLaunchKernelGGL(mc_uncertainty_cb_kernel<NORM>, dim3(p.blocks), dim3(kThreads, p.rows), (size_t)p.lds_bytes, stream, logits, draws,
+                       classes, batch, o);
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int bbb_mc_uncertainty_cb_plan(const float* logits, int draws, int batch, int classes, const float* pred, const float* p_mean,
+                                          const float* epistemic, const float* aleatoric, const float* entropy,
+                                          const float* expected_entropy, const float* mutual_info, int32_t* rows, int32_t* blocks,
+                                          int32_t* lds_bytes) {
+    const void* const outs[mc_uncertainty_plan::kOutputs] = {pred, p_mean, epistemic, aleatoric, entropy, expected_entropy, mutual_info};
+    mc_uncertainty_plan::Plan p;
+    const int rc = mc_uncertainty_plan::plan(logits, draws, batch, classes, outs, &p);
+    if (rows != nullptr) *rows = p.rows;
+    if (blocks != nullptr) *blocks = p.blocks;
+    if (lds_bytes != nullptr) *lds_bytes = p.lds_bytes;
+    return rc;
+}
+
+extern "C" int bbb_mc_uncertainty_cb(const float* logits, int draws, int batch, int classes, int normalized, float* pred, float* p_mean,
+                                     float* epistemic, float* aleatoric, float* entropy, float* expected_entropy, float* mutual_info,
+                                     void* stream) {
+    const void* const outs[mc_uncertainty_plan::kOutputs] = {pred, p_mean, epistemic, aleatoric, entropy, expected_entropy, mutual_info};
+    mc_uncertainty_plan::Plan p;
+    if (const int rc = mc_uncertainty_plan::plan(logits, draws, batch, classes, outs, &p)) return rc;
+    const UncOut o{pred, p_mean, epistemic, aleatoric, entropy, expected_entropy, mutual_info};
+    return normalized ? launch<true>(logits, draws, batch, classes, o, p, (hipStream_t)stream)
+                      : launch<false>(logits, draws, batch, classes, o, p, (hipStream_t)stream);
+}
