@@ -774,6 +774,36 @@ int bbb_mc_uncertainty_cb_plan(const float* logits, int draws, int batch, int cl
                                const float* expected_entropy, const float* mutual_info, int32_t* rows, int32_t* blocks,
                                int32_t* lds_bytes);
 
+/*
+ * Backward of bbb_mc_uncertainty_cb in ONE launch (additive to ABI 13): d_logits [draws][C][B] = d L / d logits for
+ * L = sum of (upstream gradient x output) over the seven outputs; every element is written.  logits and normalized as in the forward;
+ * p_mean [B][C] is the forward's p_mean output of the same logits (required: with it a (draw, image) pair needs no other pair).
+ * Upstream gradients: w_pred, w_p_mean, w_epistemic, w_aleatoric [B][C]; w_entropy, w_expected_entropy, w_mutual_info [B]; a NULL
+ * pointer is a zero in the same arithmetic.  Per image, with p, log p, p_bar as the forward defines them:
+ *   G[t][k] = (-(w_ent + w_mi) log p_bar[k] - (w_ee - w_mi) log p[t][k] + w_pm[k] + 2 w_epi[k] (p[t][k] - p_bar[k])
+ *              + w_ale[k] (1 - 2 p[t][k])) / draws,          D[t] = sum_k p[t][k] G[t][k]   (compensated, one thread),
+ *   d_logits[t][c] = J[t][c] (G[t][c] - D[t]) + w_pred[c] / draws,   J = p (softmax); sigmoid(v) / sum softplus (normalized; the
+ *   derivative of softplus(v) is 1 for v > 20).
+ * A class with p = 0 contributes exactly 0 to D and receives w_pred / draws alone (neither 0 * -inf nor log 0 is formed), the
+ * log p_bar term is 0 where p_bar = 0, and a NaN stays a NaN inside its image; with draws = 1 log p_bar IS log p.  The forward's clamp of
+ * mutual_info at 0 is not differentiated: the gradient is that of the KL form.  No atomics; image b's gradient depends on its own
+ * draws x C logits only, not on the batch or the launch shape.
+ * Limits (csrc/mc_uncertainty_plan.h): draws <= 202 (the forward's), batch <= INT32_MAX - 63; any classes.  Checks in this order:
+ * BBB_EINVAL (NULL logits, p_mean or d_logits, a size that is not positive, all seven upstream gradients NULL), BBB_EALIGN (a
+ * pointer that is not 4-byte aligned), BBB_ESHAPE (batch or draws beyond the limits).
+ */
+int bbb_mc_uncertainty_cb_bwd(const float* logits, const float* p_mean, int draws, int batch, int classes, int normalized,
+                              const float* w_pred, const float* w_p_mean, const float* w_epistemic, const float* w_aleatoric,
+                              const float* w_entropy, const float* w_expected_entropy, const float* w_mutual_info, float* d_logits,
+                              void* stream);
+
+/* What bbb_mc_uncertainty_cb_bwd launches for these arguments, without the launch (host only): the same checks and return codes;
+ * *rows: draws of a 64-lane block, 1; *blocks: gridDim.x = ceil(batch / 64) (gridDim.y = draws); *lds_bytes: 0.  Each may be NULL. */
+int bbb_mc_uncertainty_cb_bwd_plan(const float* logits, const float* p_mean, int draws, int batch, int classes, const float* w_pred,
+                                   const float* w_p_mean, const float* w_epistemic, const float* w_aleatoric, const float* w_entropy,
+                                   const float* w_expected_entropy, const float* w_mutual_info, const float* d_logits, int32_t* rows,
+                                   int32_t* blocks, int32_t* lds_bytes);
+
 /* [rows][cols] -> [cols][rows] (e.g. an NCHW batch [B][C*H*W] into the batch-innermost [C*H*W][B] layout). */
 int bbb_transpose2d(const float* in, float* out, int64_t rows, int64_t cols, void* stream);
 

@@ -133,6 +133,9 @@ _SIGNATURES = {
     "bbb_uncertainty": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bbb_mc_uncertainty_cb": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_void_p]),
     "bbb_mc_uncertainty_cb_plan": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [ctypes.POINTER(c_i32)] * 3),
+    "bbb_mc_uncertainty_cb_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_void_p, c_void_p]),
+    "bbb_mc_uncertainty_cb_bwd_plan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [c_void_p]
+                                       + [ctypes.POINTER(c_i32)] * 3),
     "bbb_transpose2d": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p]),
     "bbb_flip_transpose_w": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
     "bbb_flip_transpose_w_multi": (c_int, [ctypes.POINTER(FlipSeg), c_int, c_void_p]),

@@ -677,6 +677,38 @@ def mc_logits_cb(net, x, draws, seed, call0, precision="fp32"):
     return logits.permute(0, 2, 1).contiguous(), kl
 
 
+def mc_logits_cb_autograd(net, x, draws, seed, call0, precision="fp32"):
+    """mc_logits_cb for consumers that differentiate (uncertainty.mc_uncertainty(grad=True), uncertainty.saliency): -> (logits
+    [E, C, B'] batch-innermost WITH a gradient, kl of ONE forward).  Where mc_logits takes the batch-innermost autograd node
+    (fast_train.mc_logits_autograd: fp32 on an input that requires a gradient, or trainable parameters on the training path; bf16
+    storage under LaunchConfig.bf16_input_grad, or bf16_lrt + bf16_lrt_input_grad) the node's own [E, C, B] output comes back, without
+    the permute round trip; elsewhere mc_logits runs as always and is transposed once.  A result without a gradient (autograd off,
+    nothing that requires one, a mode that lands on the inference path) raises BBBHipError.  Consumes `draws` noise calls."""
+    _lib.require_device(x)
+    lrt_x = _bf16_lrt_x_grad(precision, x, net)
+    if _bf16_x_grad(precision, x, net) and (lrt_x or not any_requires_grad(net)):
+        logits_cb, kl = _bf16_x_grad_logits(net, x, draws, seed, call0, True, lrt=lrt_x)
+    else:
+        _check_precision(precision, net, x, True)
+        node = False
+        if precision == "fp32" and fast_autograd and torch.is_grad_enabled() and (x.requires_grad or any_requires_grad(net)):
+            from . import fast_train
+            node = fast_train.train_path_ok(net, x) is not None
+        if node:
+            logits_cb, kl = fast_train.mc_logits_autograd(net, x, draws, seed, call0)
+            stats["path"] = "chwn-autograd"
+        else:
+            logits, kl = mc_logits(net, x, draws, seed, call0, precision=precision)
+            logits_cb = logits.permute(0, 2, 1).contiguous()
+    if not (torch.is_grad_enabled() and logits_cb.requires_grad):
+        hint = (': precision="bf16x3" as a string runs the inference path; for split-bf16 GEMMs under autograd use precision="fp32" '
+                'inside ops.use_config(gemm_mode="bf16x3")') if precision == "bf16x3" else ""
+        raise _lib.BBBHipError("mc_logits_cb_autograd: the logits do not require a gradient (autograd is off, neither the input nor a "
+                               "parameter requires one, or this model / batch / precision landed on the inference path -- the "
+                               "batch-innermost autograd node takes what fast_train.train_path_ok admits, B % 4 == 0 among it)" + hint)
+    return logits_cb, kl
+
+
 def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None, streams=1, precision="fp32", units=None, b_offset=0,
                step_end=None, groups=1, param_alias=None, share=None, elbo=None):
     """(log-sum-exp over the local draws of the per-draw log_softmax [B, C], kl of one forward), staying in the

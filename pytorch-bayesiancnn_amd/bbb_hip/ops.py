@@ -1610,6 +1610,59 @@ def mc_uncertainty_cb(logits_cb, normalized=False, want=None):
     return Uncertainty(*outs)
 
 
+class _McUncertaintyCB(torch.autograd.Function):
+    """The wanted fields of mc_uncertainty_cb(logits [T, C, B]) with their backward in ONE launch (bbb_mc_uncertainty_cb_bwd): the
+    scores written as torch expressions on permuted logits are dozens of ATen launches forward and backward, and p * log p gives NaN
+    gradients where a probability is 0.  The forward launch also writes p_mean for the backward when it was not asked for (a field's
+    bits do not depend on what else is computed); fields that receive no gradient go down as NULL."""
+
+    @staticmethod
+    def forward(ctx, logits, normalized, want):
+        logits = logits.contiguous()
+        full = mc_uncertainty_cb(logits, normalized=normalized, want=want if "p_mean" in want else want + ("p_mean",))
+        ctx.save_for_backward(logits, full.p_mean)
+        ctx.normalized, ctx.want = bool(normalized), want
+        ctx.set_materialize_grads(False)
+        return tuple(getattr(full, f) for f in want)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        logits, p_mean = ctx.saved_tensors
+        T, C, B = logits.shape
+        ups = dict.fromkeys(Uncertainty._fields)
+        for f, g in zip(ctx.want, grads):
+            if g is not None:
+                ups[f] = g.to(dtype=torch.float32).contiguous()
+        if all(g is None for g in ups.values()):
+            return None, None, None
+        out = torch.empty_like(logits)
+        with on_device(logits.device):
+            check(_lib.lib().bbb_mc_uncertainty_cb_bwd(logits.data_ptr(), p_mean.data_ptr(), T, B, C, 1 if ctx.normalized else 0,
+                                                       *[ptr(ups[f]) for f in Uncertainty._fields], out.data_ptr(),
+                                                       cur_stream(logits.device)), "bbb_mc_uncertainty_cb_bwd")
+        return out, None, None
+
+
+def mc_uncertainty_cb_autograd(logits_cb, normalized=False, want=None):
+    """Differentiable mc_uncertainty_cb: logits [T <= 202, C, B] (requires grad) -> ops.Uncertainty whose fields carry a gradient
+    back to the logits; the values are bit for bit mc_uncertainty_cb's, fields not in `want` are None.  The gradient of
+    mutual_info is that of its KL form (the clamp at 0 only repairs rounding); a class with probability 0 gets an exact 0 from the
+    probability side, where torch expressions give NaN."""
+    require_device(logits_cb)
+    want = Uncertainty._fields if want is None else tuple(want)
+    unknown = [w for w in want if w not in Uncertainty._fields]
+    if unknown or not want:
+        raise _lib.BBBHipError(f"want must name at least one of {Uncertainty._fields}, got {want!r}")
+    if logits_cb.dim() != 3 or logits_cb.dtype != torch.float32:
+        raise _lib.BBBHipError("mc_uncertainty_cb_autograd takes fp32 logits [T, C, B]")
+    if logits_cb.shape[0] > MC_UNCERTAINTY_MAX_DRAWS:
+        raise _lib.BBBHipError(f"too many draws for one uncertainty launch: {logits_cb.shape[0]} > {MC_UNCERTAINTY_MAX_DRAWS}")
+    want = tuple(f for f in Uncertainty._fields if f in want)
+    outs = dict(zip(want, _McUncertaintyCB.apply(logits_cb, bool(normalized), want)))
+    return Uncertainty(*[outs.get(f) for f in Uncertainty._fields])
+
+
 def to_batch_innermost(x):
     """[B, C, H, W] -> [C, H, W, B] (LDS-tiled transpose)."""
     require_device(x)

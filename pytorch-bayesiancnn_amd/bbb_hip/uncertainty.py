@@ -6,6 +6,7 @@ launch and the softmax / moment reduction is one HIP kernel instead of a Python 
 
 Beyond the reference: mc_uncertainty returns those moments together with predictive entropy, expected entropy and mutual information
 (BALD) as device tensors, from one reduction launch on the batch-innermost logits; GraphedUncertainty is its captured form.
+mc_uncertainty(grad=True) carries a gradient through the scores (one backward launch), and saliency returns d score / d input.
 """
 import torch
 
@@ -31,16 +32,41 @@ def get_uncertainty_per_batch(model, batch, T=15, normalized=False):
     return pred.cpu().numpy(), epi.cpu().numpy(), ale.cpu().numpy()
 
 
-def mc_uncertainty(net, batch, T=15, normalized=False, precision="fp32"):
+def mc_uncertainty(net, batch, T=15, normalized=False, precision="fp32", grad=False, want=None):
     """T stochastic forwards of the batch -> ops.Uncertainty (pred, p_mean, epistemic, aleatoric [B, C]; entropy, expected_entropy,
     mutual_info [B]), all on the device and without a synchronisation: the scores active learning, out-of-distribution detection
     and selective prediction rank by.  The logits stay batch-innermost from the forward into ONE reduction launch
     (ops.mc_uncertainty_cb); a model off the batch-innermost path runs ensemble.mc_logits as always and is transposed once, so every
-    model gets the same kernel and numerics.  Consumes T noise calls, as get_uncertainty_per_batch does.  precision: as mc_logits."""
-    with torch.no_grad():
-        seed, call0 = rng.next_calls(T)
-        logits_cb, _ = ensemble.mc_logits_cb(net, batch.to(next(net.parameters()).device), T, seed, call0, precision=precision)
-        return ops.mc_uncertainty_cb(logits_cb, normalized=normalized)
+    model gets the same kernel and numerics.  Consumes T noise calls, as get_uncertainty_per_batch does.  precision: as mc_logits.
+    grad=True: the same scores WITH a gradient to whatever requires one (the batch, the parameters), autograd left on: the forwards on
+    ensemble.mc_logits_cb_autograd, the reduction and its one-launch backward on ops.mc_uncertainty_cb_autograd; want: the fields to
+    compute (None: all seven), the others are None.  grad=False ignores requires_grad, as it always did."""
+    if not grad:
+        with torch.no_grad():
+            seed, call0 = rng.next_calls(T)
+            logits_cb, _ = ensemble.mc_logits_cb(net, batch.to(next(net.parameters()).device), T, seed, call0, precision=precision)
+            return ops.mc_uncertainty_cb(logits_cb, normalized=normalized, want=want)
+    _lib.require_device(batch)
+    seed, call0 = rng.next_calls(T)
+    logits_cb, _ = ensemble.mc_logits_cb_autograd(net, batch, T, seed, call0, precision=precision)
+    return ops.mc_uncertainty_cb_autograd(logits_cb, normalized=normalized, want=want)
+
+
+SCORES = ("entropy", "expected_entropy", "mutual_info")
+
+
+def saliency(net, x, T=15, score="mutual_info", normalized=False, precision="fp32"):
+    """(scores [B], d scores.sum() / d x with the shape of x) of one of the three per-image scores under the next T noise calls:
+    epistemic (mutual_info) or total (entropy) saliency maps, the step direction of attacks and defences on BALD.  Works on a
+    detached copy of x -- x.grad and every parameter's .grad stay as they are (torch.autograd.grad on the input alone)."""
+    if score not in SCORES:
+        raise _lib.BBBHipError(f"score must be one of {SCORES}, got {score!r}")
+    _lib.require_device(x)
+    xg = x.detach().clone().requires_grad_(True)
+    with torch.enable_grad():
+        s = getattr(mc_uncertainty(net, xg, T=T, normalized=normalized, precision=precision, grad=True, want=(score,)), score)
+        g, = torch.autograd.grad(s.sum(), xg)
+    return s.detach(), g
 
 
 class GraphedUncertainty:

@@ -11,6 +11,7 @@
 // log p_t = (v - mx) - log partition, the max-first order of the tail kernels (mc_tail.hip), and p_t = expf(log p_t); normalized:
 // p_t = q / z, log p_t = logf(q) - logf(z) with q = softplus(v).  A term with p = 0 contributes exactly 0 (0 * -inf never forms);
 // the tests `p == 0.0f` are false for NaN, so a NaN stays a NaN.
+// The backward (mc_uncertainty_cb_bwd_kernel, further down) is one launch too: one thread per (draw, image), no LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -168,7 +169,106 @@ int launch(const float* logits, int draws, int batch, int classes, const UncOut&
     return (int)hipGetLastError();
 }
 
+// ---- backward: d (sum of upstream x outputs) / d logits, [T][C][B], in one launch ------------------------------------------------------
+// Upstream gradients of the seven outputs; a NULL pointer is a zero, in the SAME arithmetic (0 * NaN stays NaN, as the reference's).
+struct UncUp {
+    const float *pred, *p_mean, *epi, *ale, *ent, *exp_ent, *mi;
+};
+
+__device__ __forceinline__ float up(const float* w, int64_t i) { return w != nullptr ? w[i] : 0.0f; }
+
+// One thread = one (draw t, image b): with p_bar read back from the forward nothing else of the image is needed.  Sweeps over the C
+// classes as phase 1 of the forward (maximum, log partition), then D = sum_k p G (compensated), then the C results:
+//   G[k] = (-(w_ent + w_mi) log p_bar[k] - (w_ee - w_mi) log p[k] + w_pm[k] + 2 w_epi[k] (p[k] - p_bar[k]) + w_ale[k] (1 - 2 p[k])) / T
+//   d logits[c] = J[c] (G[c] - D) + w_pred[c] / T,     J = p (softmax),  sigmoid(v) / z (normalized; 1 / z for v > 20)
+// A class with p == 0 adds exactly 0 to D and gets w_pred / T alone (its log p may be -inf: neither 0 * -inf nor log 0 is formed); the
+// log p_bar term is 0 where p_bar == 0 (p_bar >= p / T: only beside a p in the subnormals).  The tests are false for NaN.  T == 1:
+// log p_bar IS log p.  blockDim = (64, 1), grid = (ceil(B / 64), T): lanes = consecutive images, every [.][.][B] access coalesced.
+template <bool NORM>
+__global__ __launch_bounds__(kThreads) void mc_uncertainty_cb_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ p_mean,
+                                                                         int T, int C, int B, const UncUp w, float* __restrict__ out) {
+    const int b = blockIdx.x * kThreads + threadIdx.x;
+    if (b >= B) return;
+    const int64_t off = (int64_t)blockIdx.y * C * B + b;
+    const float* p = logits + off;
+    float a;
+    Comp z;
+    if (NORM) {
+        strided(p, B, C, [&](int, float v) { z.add(softplus20(v)); });
+        a = z.s;
+    } else {
+        float mx = -INFINITY;
+        strided(p, B, C, [&](int, float v) { mx = fmaxf(mx, v); });
+        strided(p, B, C, [&](int, float v) { z.add(expf(v - mx)); });
+        a = mx;
+    }
+    const float lz = logf(z.s);
+    const float fT = (float)T;
+    const float c_bar = -(up(w.ent, b) + up(w.mi, b)), c_t = -(up(w.exp_ent, b) - up(w.mi, b));
+    const int64_t row = (int64_t)b * C;
+    // (G, p) of class k; G is only used where p != 0
+    auto grad = [&](int k, float v, float* pr) {
+        float ls;
+        prob<NORM>(v, a, lz, &ls, pr);
+        const float pb = p_mean[row + k];
+        const float lpb = T == 1 ? ls : logf(pb);
+        const float t_bar = pb == 0.0f ? 0.0f : c_bar * lpb;
+        const float t_epi = 2.0f * up(w.epi, row + k) * (*pr - pb);
+        const float t_ale = up(w.ale, row + k) * (1.0f - 2.0f * *pr);
+        return ((((t_bar + c_t * ls) + up(w.p_mean, row + k)) + t_epi) + t_ale) / fT;
+    };
+    Comp d;
+    strided(p, B, C, [&](int k, float v) {
+        float pr;
+        const float g = grad(k, v, &pr);
+        d.add(pr == 0.0f ? 0.0f : pr * g);
+    });
+    float* o = out + off;
+    strided(p, B, C, [&](int k, float v) {
+        float pr;
+        const float g = grad(k, v, &pr);
+        float j = pr;
+        if (NORM) j = (v > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-v))) / a;
+        o[(int64_t)k * B] = (pr == 0.0f ? 0.0f : j * (g - d.s)) + up(w.pred, row + k) / fT;
+    });
+}
+
+template <bool NORM>
+int launch_bwd(const float* logits, const float* p_mean, int draws, int batch, int classes, const UncUp& w, float* out,
+               const mc_uncertainty_plan::Plan& p, hipStream_t stream) {
+    hipLaunchKernelGGL(mc_uncertainty_cb_bwd_kernel<NORM>, dim3(p.blocks, draws), dim3(kThreads, p.rows), 0, stream, logits, p_mean, draws,
+                       classes, batch, w, out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
+
+extern "C" int bbb_mc_uncertainty_cb_bwd_plan(const float* logits, const float* p_mean, int draws, int batch, int classes, const float* w_pred,
+                                              const float* w_p_mean, const float* w_epistemic, const float* w_aleatoric,
+                                              const float* w_entropy, const float* w_expected_entropy, const float* w_mutual_info,
+                                              const float* d_logits, int32_t* rows, int32_t* blocks, int32_t* lds_bytes) {
+    const void* const ups[mc_uncertainty_plan::kUpstreams] = {w_pred, w_p_mean, w_epistemic, w_aleatoric, w_entropy, w_expected_entropy,
+                                                              w_mutual_info};
+    mc_uncertainty_plan::Plan p;
+    const int rc = mc_uncertainty_plan::plan_bwd(logits, p_mean, draws, batch, classes, ups, d_logits, &p);
+    if (rows != nullptr) *rows = p.rows;
+    if (blocks != nullptr) *blocks = p.blocks;
+    if (lds_bytes != nullptr) *lds_bytes = p.lds_bytes;
+    return rc;
+}
+
+extern "C" int bbb_mc_uncertainty_cb_bwd(const float* logits, const float* p_mean, int draws, int batch, int classes, int normalized,
+                                         const float* w_pred, const float* w_p_mean, const float* w_epistemic, const float* w_aleatoric,
+                                         const float* w_entropy, const float* w_expected_entropy, const float* w_mutual_info,
+                                         float* d_logits, void* stream) {
+    const void* const ups[mc_uncertainty_plan::kUpstreams] = {w_pred, w_p_mean, w_epistemic, w_aleatoric, w_entropy, w_expected_entropy,
+                                                              w_mutual_info};
+    mc_uncertainty_plan::Plan p;
+    if (const int rc = mc_uncertainty_plan::plan_bwd(logits, p_mean, draws, batch, classes, ups, d_logits, &p)) return rc;
+    const UncUp w{w_pred, w_p_mean, w_epistemic, w_aleatoric, w_entropy, w_expected_entropy, w_mutual_info};
+    return normalized ? launch_bwd<true>(logits, p_mean, draws, batch, classes, w, d_logits, p, (hipStream_t)stream)
+                      : launch_bwd<false>(logits, p_mean, draws, batch, classes, w, d_logits, p, (hipStream_t)stream);
+}
 
 extern "C" int bbb_mc_uncertainty_cb_plan(const float* logits, int draws, int batch, int classes, const float* pred, const float* p_mean,
                                           const float* epistemic, const float* aleatoric, const float* entropy,
