@@ -148,6 +148,16 @@ typedef struct bbb_adam_segment {
  */
 int bbb_adam_step(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
                   int64_t step, const float* step_dev, const float* lr_dev, void* stream);
+/* What bbb_adam_step launches for these arguments (additive to ABI 13; host only, needs no device: tests): the entry's own plan
+ * (csrc/adam_plan.h), without the launch.  Addresses are only looked at.  *chunks: blocks of 1024 elements, at most 2^31 - 1 (more:
+ * BBB_ESHAPE); chunk_begin[17]: first block of segment s, [nseg .. 16] = *chunks; scalars[7]: the host path's fp32 step_size =
+ * lr / (1 - beta1^step), sqrt(1 - beta2^step), beta1, beta2, 1 - beta1, 1 - beta2, eps, each formed in double and rounded once (with
+ * step_dev the kernel forms the first two itself; they are then those of max(step, 1)); vec[16]: 1 where a segment's four pointers
+ * are jointly 16-byte aligned and n >= 4, so that some thread moves 16 bytes at a time.  Returns what the launch entry returns before
+ * its launch; a refusal writes zeros.  Out-pointers may be NULL. */
+int bbb_adam_step_plan(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
+                       int64_t step, const float* step_dev, const float* lr_dev, int32_t* chunks, int32_t* chunk_begin,
+                       float* scalars, int32_t* vec);
 
 /* Test entry: materialise n elements of a noise stream starting at element `start`. */
 int bbb_eps_dump(float* out, int64_t n, int64_t start, uint64_t seed, uint32_t call, uint32_t stream_id, void* stream);

@@ -209,6 +209,34 @@ def reparam_plan(segs, draws, slots=0, nseg=None):
     return plan
 
 
+ADAM_PLAN_SCALARS = ("step_size", "sqrt_bc2", "beta1", "beta2", "omb1", "omb2", "eps")
+
+
+def adam_plan(segs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, step=1, step_dev=0, lr_dev=0, nseg=None):
+    """What bbb_adam_step launches for these arguments (bbb_adam_step_plan: the launch entry's own plan, csrc/adam_plan.h; host only:
+    needs no device).  segs: a ctypes array of AdamSegment as the launch takes it, or a sequence whose items are element counts or
+    dicts of AdamSegment fields (absent pointers get a 16-byte aligned placeholder address that is never read).  step_dev / lr_dev:
+    addresses (0 = none).  Returns a dict: status (0 or the BBB_E* code the launch entry would return -- a refusal is reported, not
+    raised, and leaves every other field zero), chunks, chunk_begin (17 entries), vec (one bool per segment: some thread can move 16
+    bytes at a time) and the seven fp32 scalars of ADAM_PLAN_SCALARS as Python floats."""
+    if isinstance(segs, ctypes.Array):
+        arr, nseg = segs, (len(segs) if nseg is None else nseg)
+    else:
+        arr = (_lib.AdamSegment * max(len(segs), 1))()
+        for s, item in zip(arr, segs):
+            s.param = s.grad = s.exp_avg = s.exp_avg_sq = 4096
+            for k, v in ({"n": item} if isinstance(item, int) else dict(item)).items():
+                setattr(s, k, v)
+        nseg = len(segs) if nseg is None else nseg
+    chunks, begin = ctypes.c_int32(0), (ctypes.c_int32 * (_lib.MAX_SEGMENTS + 1))()
+    sc, vec = (ctypes.c_float * len(ADAM_PLAN_SCALARS))(), (ctypes.c_int32 * _lib.MAX_SEGMENTS)()
+    rc = _lib.lib().bbb_adam_step_plan(arr, nseg, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), step_dev or None,
+                                       lr_dev or None, ctypes.byref(chunks), begin, sc, vec)
+    plan = {"status": rc, "chunks": chunks.value, "chunk_begin": list(begin), "vec": [bool(v) for v in vec[:max(min(nseg, len(vec)), 0)]]}
+    plan.update(zip(ADAM_PLAN_SCALARS, sc))
+    return plan
+
+
 def eps_dump(n, seed, call, stream_id, device, start=0):
     out = torch.empty(n, dtype=torch.float32, device=device)
     with on_device(out.device):

@@ -5,15 +5,17 @@
 //     v <- v * beta2 + (1 - beta2) * g * g               (mul, addcmul)
 //     p <- p - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
 // HBM traffic per element: 16 B read + 12 B written; purely bandwidth-bound.
+// The argument checks, the chunk walk and the host-path scalars live in csrc/adam_plan.h (host only; bbb_adam_step_plan reports them).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/bbb_hip.h"
+#include "adam_plan.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kChunk = kThreads * 4;
+constexpr int kThreads = adam_plan::kThreads;
+constexpr int kChunk = adam_plan::kChunk;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -86,34 +88,32 @@ __global__ __launch_bounds__(kThreads) void adam_step_kernel(const AdamArgs a) {
 
 extern "C" int bbb_adam_step(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
                              int64_t step, const float* step_dev, const float* lr_dev, void* stream) {
-    if (segs == nullptr || nseg <= 0 || nseg > BBB_MAX_SEGMENTS || (step <= 0 && step_dev == nullptr)) return BBB_EINVAL;
-    if (lr_dev != nullptr && step_dev == nullptr) return BBB_EINVAL;      // device-side lr goes with the device-side step count
-    if ((((uintptr_t)step_dev | (uintptr_t)lr_dev) & 3u) != 0) return BBB_EALIGN;
-    if (step <= 0) step = 1;
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0)) return BBB_EINVAL;
+    adam_plan::Plan p;
+    const int rc = adam_plan::plan(segs, nseg, lr, beta1, beta2, eps, step, step_dev, lr_dev, &p);
+    if (rc != 0) return rc;
     AdamArgs a = {};
-    int chunks = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const bbb_adam_segment_t& g = segs[s];
-        if (g.param == nullptr || g.grad == nullptr || g.exp_avg == nullptr || g.exp_avg_sq == nullptr || g.n <= 0) return BBB_EINVAL;
-        if ((((uintptr_t)g.param | (uintptr_t)g.grad | (uintptr_t)g.exp_avg | (uintptr_t)g.exp_avg_sq) & 3u) != 0) return BBB_EALIGN;
-        a.seg[s] = g;
-        a.chunk_begin[s] = chunks;
-        const int64_t c = (g.n + kChunk - 1) / kChunk;
-        if (c + chunks > 0x7fffffffLL) return BBB_ESHAPE;
-        chunks += (int)c;
-    }
-    for (int s = nseg; s <= BBB_MAX_SEGMENTS; ++s) a.chunk_begin[s] = chunks;
+    for (int s = 0; s < nseg; ++s) a.seg[s] = segs[s];
+    for (int s = 0; s <= BBB_MAX_SEGMENTS; ++s) a.chunk_begin[s] = p.chunk_begin[s];
     a.nseg = nseg;
-    // scalars in double on the host and rounded to fp32 once, as torch does with its Python-side hyper-parameters
-    // (1 - 0.999 must become float(0.001), not 1.0f - 0.999f)
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    a.step_size = (float)(lr / bc1);
-    a.sqrt_bc2 = (float)sqrt(bc2);
-    a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
+    a.step_size = p.step_size; a.sqrt_bc2 = p.sqrt_bc2;
+    a.beta1 = p.beta1; a.beta2 = p.beta2; a.omb1 = p.omb1; a.omb2 = p.omb2; a.eps = p.eps;
     a.lr_d = lr; a.beta1_d = beta1; a.beta2_d = beta2; a.step_dev = step_dev; a.lr_dev = lr_dev;
-    hipLaunchKernelGGL(adam_step_kernel, dim3(chunks), dim3(kThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(adam_step_kernel, dim3(p.chunks), dim3(kThreads), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+// What bbb_adam_step launches for these arguments: the same plan, no launch, no device.  Out-pointers may be NULL; a refusal writes zeros.
+extern "C" int bbb_adam_step_plan(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
+                                  int64_t step, const float* step_dev, const float* lr_dev, int32_t* chunks, int32_t* chunk_begin,
+                                  float* scalars, int32_t* vec) {
+    adam_plan::Plan p;
+    const int rc = adam_plan::plan(segs, nseg, lr, beta1, beta2, eps, step, step_dev, lr_dev, &p);
+    if (chunks) *chunks = p.chunks;
+    if (chunk_begin) for (int s = 0; s <= BBB_MAX_SEGMENTS; ++s) chunk_begin[s] = p.chunk_begin[s];
+    if (scalars) {
+        const float sc[7] = {p.step_size, p.sqrt_bc2, p.beta1, p.beta2, p.omb1, p.omb2, p.eps};
+        for (int k = 0; k < 7; ++k) scalars[k] = sc[k];
+    }
+    if (vec) for (int s = 0; s < BBB_MAX_SEGMENTS; ++s) vec[s] = p.vec[s];
+    return rc;
 }
