@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, pool_desc, rng, _lib
+from .conv_desc import out_map
 from .infer_walk import (BAYES_FORMS, ChwnPartition, ChwnPlan, ChwnStep, chwn_partition, conv_flops,  # noqa: F401
                          _act_name, _chwn_steps, _chwn_walk, _run)
 
@@ -147,10 +148,7 @@ def output_rows(net, x_shape):
     pools_ok = True                      # every pool is admitted on the map it meets (pool_desc.pool_of): _pools_ok
     for m in flat_children(net) or []:
         if isinstance(m, (_BBBConv, _LRTConv)):
-            (sh, sw), (ph, pw), (dh, dw) = ops._pair(m.stride), ops._pair(m.padding), ops._pair(m.dilation)
-            kh, kw = m.kernel_size
-            H = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-            W = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+            H, W = out_map(H, W, m.kernel_size, m.stride, m.padding, m.dilation)
             C = m.out_channels
         elif pool_desc.is_pool(m):
             spec = pool_desc.pool_of(m, H, W)

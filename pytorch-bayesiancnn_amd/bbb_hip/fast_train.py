@@ -21,24 +21,19 @@ E forwards, KL, log_softmax / logmeanexp, ELBO, backward -- on the training path
 (ops.elbo_cb_autograd: bbb_elbo_cb_fwd / bbb_elbo_cb_bwd); the entry points that return log-probabilities keep it in torch.
 
 Four nodes -- _MCForward (fp32), _MCForwardBF16 (bf16 storage), _MCForwardLRT (local reparameterisation), _MCForwardLRTBF16 (its
-activation side in bf16 storage: input gradients with frozen parameters, no weight side) -- over one forward walk
-(_walk: layer / activation / pool pairing, the tape) and one backward schedule (_Schedule: which stream a layer's weight side runs
-on, the early fork, the join); _carry / _run_backward take the launch configuration and scratch scope from the forward to the
+activation side in bf16 storage: input gradients with frozen parameters, no weight side) -- over one layer plan (train_plan: _parse
+states the layer / activation / pool pairing, geometry and maps once per model and input shape; admission is that a plan exists), one
+forward walk over it (_walk: the tape, every launch's map held against the plan) and one backward schedule (_Schedule: which stream a
+layer's weight side runs on, the early fork, the join); _carry / _run_backward take the launch configuration and scratch scope to the
 backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weight side, its input gradient, its flips up front.
 """
+import collections
 import os
 
 import torch
 
 from . import _lib, ops, pool_desc
 from .conv_desc import out_map as _out_map
-
-
-def _layers():
-    from layers.bbb import _BBBLayer, BBBConv2d, BBBLinear
-    from layers.lrt import _LRTLayer
-    from layers.misc import FlattenLayer
-    return _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer
 
 
 def train_path_ok(net, x):
@@ -53,77 +48,106 @@ def train_path_ok(net, x):
     from . import ensemble
     if not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4 or x.dtype != torch.float32 or x.shape[0] % 4 != 0:
         return None
-    # what never changes for a given model and input shape is analysed once (ensemble._structure); what can change between
-    # calls (eps replay switched on, a layer moved off the device) is re-checked every time
-    cache = ensemble._structure(net)["train"]
-    key = tuple(x.shape)
-    if key not in cache:
-        cache[key] = _train_path_static(net, x)
-    kind = cache[key]
-    if kind is None:
+    # what never changes for a given model and input shape is analysed once (train_plan); what can change between calls (eps
+    # replay switched on, a layer moved off the device) is re-checked every time
+    plan = train_plan(net, x.shape)
+    if plan is None or any(m.eps_source is not None or not m.W_mu.is_cuda for m in ensemble.bayesian_layers(net)):
         return None
-    for m in ensemble.bayesian_layers(net):
-        if m.eps_source is not None or not m.W_mu.is_cuda:
-            return None
-    return kind
+    return plan.kind
 
 
 def _train_path_static(net, x):
+    return getattr(train_plan(net, x.shape), "kind", None)
+
+
+# One Bayesian layer with what follows it.  wshape: (Cout, Cin, kh, kw), a linear layer's (out, in, 1, 1); geom: (stride, padding,
+# dilation), a linear layer's (1, 0, 1); act: "relu" | "softplus" | None, fused into the layer's launch; pool: the PoolSpec of the
+# pool behind that, or None; in_chw: what the layer reads (a linear layer: (in_features, 1, 1) -- a flatten in front of a layer is
+# this reshape); conv_chw: what its launch writes; out_chw: behind the pool, what the next block meets.
+TrainBlock = collections.namedtuple("TrainBlock", "layer li is_conv wshape geom act pool in_chw conv_chw out_chw first last")
+TrainPlan = collections.namedtuple("TrainPlan", "kind blocks")              # kind: "bbb" | "lrt"; blocks: TrainBlocks, forward order
+
+
+def _parse(mods, x_shape):
+    """THE grammar of a model on the training path (train_path_ok states it in words): a flat module list (ensemble.flat_children)
+    and an input shape -> (TrainPlan, None), or (None, why it is not on the path).  No tensors, no device; the map is followed with
+    conv_desc.out_map and pool_desc.pool_of alone."""
     from . import ensemble
-    from layers.lrt import BBBConv2d as LRTConv2d, BBBLinear as LRTLinear
-    _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
-    mods = ensemble.flat_children(net)
+    from layers.bbb import _BBBLayer, BBBConv2d, BBBLinear
+    from layers.lrt import _LRTLayer, BBBConv2d as LRTConv2d, BBBLinear as LRTLinear
+    from layers.misc import FlattenLayer
     if not mods or not isinstance(mods[-1], (BBBLinear, LRTLinear)):
-        return None
-    first = True
-    pri = set()
-    kinds = set()
+        return None, "the model must be flat (ensemble.flat_children) and end in a Bayesian linear layer"
+    blocks, pri, kinds = [], set(), set()
+    chw = tuple(int(v) for v in x_shape[1:])                             # what the next module meets
     i = 0
-    after_layer = False                  # the previous module was a Bayesian layer (+ its fused activation): a pool may follow
-    H, W = int(x.shape[2]), int(x.shape[3])                # the map, followed for the pools (pool_desc.pool_of asks about it)
     while i < len(mods):
         m = mods[i]
-        poolable, after_layer = after_layer, False
         if isinstance(m, (_BBBLayer, _LRTLayer)):
             kinds.add("lrt" if isinstance(m, _LRTLayer) else "bbb")
             if not m.use_bias:
-                return None
+                return None, "every Bayesian layer needs a bias"
             pri.add((m.prior_mu, m.prior_sigma))
-            if isinstance(m, (BBBConv2d, LRTConv2d)):
+            is_conv = isinstance(m, (BBBConv2d, LRTConv2d))
+            if is_conv:
                 if min(ops._pair(m.stride)) < 1:
-                    return None
+                    return None, "a convolution's stride must be at least 1"
                 (ph, pw), (dh, dw) = ops._pair(m.padding), ops._pair(m.dilation)
                 if dh * (m.kernel_size[0] - 1) < ph or dw * (m.kernel_size[1] - 1) < pw:
-                    return None
-                H, W = _out_map(H, W, m.kernel_size, m.stride, m.padding, m.dilation)
-            elif m.in_features % 4 != 0:
-                return None              # (a first linear layer too: its weight gradient takes the 4-aligned channel path)
-            first = False
-            after_layer = True
-            if i + 1 < len(mods) and ensemble._act_name(mods[i + 1]) is not None:
+                    return None, "a convolution's padding must stay within the kernel reach (p <= d (k - 1))"
+                wshape, geom, in_chw = tuple(m.W_mu.shape), (m.stride, m.padding, m.dilation), chw
+                chw = (m.out_channels, *_out_map(chw[1], chw[2], m.kernel_size, *geom))
+            elif m.in_features % 4 != 0:         # (a first linear layer too: its weight gradient takes the 4-aligned channel path)
+                return None, "a linear layer's in_features must be a multiple of 4"
+            else:
+                wshape, geom, in_chw = (m.out_features, m.in_features, 1, 1), (1, 0, 1), (m.in_features, 1, 1)
+                chw = (m.out_features, 1, 1)
+            pool, conv_chw, last = None, chw, i == len(mods) - 1
+            act = ensemble._act_name(mods[i + 1]) if not last else None
+            i += act is not None
+            if i + 1 < len(mods) and pool_desc.is_pool(mods[i + 1]):
                 i += 1
+                pool = pool_desc.pool_of(mods[i], chw[1], chw[2])
+                if pool is None:
+                    return None, "a pool this path does not take on the map it meets (pool_desc.pool_of)"
+                chw = (chw[0], *pool.out)
+            blocks.append(TrainBlock(m, len(blocks), is_conv, wshape, geom, act, pool, in_chw, conv_chw, chw, not blocks, last))
         elif pool_desc.is_pool(m):
-            # (not poolable: a leading pool, or a pool after a pool / flatten -- the node's backward pairs pools with layers)
-            spec = pool_desc.pool_of(m, H, W) if poolable else None
-            if spec is None:
-                return None
-            H, W = spec.out
+            # a leading pool, or a pool after a pool / flatten: the node's backward pairs pools with layers
+            return None, "pooling must follow a Bayesian layer (and its activation) directly"
         elif isinstance(m, FlattenLayer):
-            H = W = 1
+            chw = (m.num_features, 1, 1)
         else:
-            return None                      # a stand-alone activation or anything else: not on this path
+            return None, "a stand-alone activation or a module this path does not know: " + type(m).__name__
         i += 1
-    if len(pri) != 1 or len(kinds) != 1 or len(ensemble.bayesian_layers(net)) * 2 > _lib.MAX_SEGMENTS:
-        return None
-    if ensemble.output_rows(net, tuple(x.shape)) != x.shape[0]:
-        return None
-    return next(iter(kinds))
+    if len(pri) != 1 or len(kinds) != 1 or len(blocks) * 2 > _lib.MAX_SEGMENTS:
+        return None, f"at most {_lib.MAX_SEGMENTS // 2} Bayesian layers, of one kind (all BBB or all LRT) and sharing one prior"
+    return TrainPlan(next(iter(kinds)), tuple(blocks)), None
+
+
+def _analysis(net, x_shape):
+    """(plan, why) of _parse for (net, x_shape), cached on the module with the rest of its analysis (ensemble._structure: dropped by
+    the registration hooks and ensemble.invalidate).  One rule is asked of ensemble, which owns it, not of the module list: the
+    model yields one output row per image (ensemble.output_rows)."""
+    from . import ensemble
+    cache = ensemble._structure(net)["train"]
+    if x_shape not in cache:
+        plan, why = _parse(ensemble.flat_children(net), x_shape)
+        if plan is not None and ensemble.output_rows(net, x_shape) != x_shape[0]:
+            plan, why = None, "a FlattenLayer that keeps one row per image"
+        cache[x_shape] = (plan, why)
+    return cache[x_shape]
+
+
+def train_plan(net, x_shape):
+    """The TrainPlan of `net` on an input of shape x_shape (what the nodes' forward walks), or None where the model is not on the
+    training path.  The plan is cached: after changing a layer's or a pool's geometry in place, call ensemble.invalidate(net)."""
+    return _analysis(net, tuple(x_shape))[0]
 
 
 def ws_shape(rec):
-    m = rec["layer"]
-    E = rec["w"].shape[0]
-    return (E,) + tuple(m.W_mu.shape)
+    """[E, *the layer's W_mu.shape]: the record's wshape, a linear layer's without its two unit taps."""
+    return (rec["w"].shape[0],) + rec["wshape"][:rec["layer"].W_mu.dim()]
 
 
 fold_lrt_combine = [True]       # an LRT layer's g1 + 2 x g2 is formed inside the pooling / activation backward of the layer below
@@ -184,51 +208,43 @@ def _param_lists(layers, leaf):
     return mus, rhos, ids
 
 
-def _walk(mods, h, is_layer, run_layer, pool, avgpool=None):
-    """The forward walk over a flat model (ensemble.flat_children), one copy for the three nodes: -> (tape, final h).
-    h: the batch-innermost input [1, C, H, W, B].  is_layer(m): m is a Bayesian layer of the node's kind.
-    run_layer(m, li, x_in, is_conv, geom, act, pooled) -> a record holding at least `y`, the activated output [E', Cout, Ho, Wo, B]
-    (x_in: h, for a linear layer reshaped to [*, in_features, 1, 1, B]; geom: (stride, padding, dilation); act: the activation
-    module behind the layer, fused and skipped; pooled: a pool follows that).  pool(y, kernel, stride): the node's max pooling;
-    avgpool(y, kernel, stride, padding, count_include_pad): its average pooling (None: the node has none) -- each called with the
-    spec of the pool behind the layer (pool_desc.pool_of) unpacked.
-    The walk completes the record -- layer, x, act, geom, pool (that spec: its kind, and as a tuple the arguments above; None without
-    a pool), first, out_shape (of what the next layer reads) -- and appends it to the tape."""
-    from . import ensemble
-    from layers.lrt import BBBConv2d as LRTConv2d
-    _BBBLayer, BBBConv2d, BBBLinear, _LRTLayer, FlattenLayer = _layers()
-    B = h.shape[-1]
+def _node_plan(cfg, x):
+    """A node's forward: the plan it walks; a model that is not on the path raises with the parser's reason."""
+    plan, why = _analysis(cfg["net"], tuple(x.shape))
+    if plan is None:
+        raise _lib.BBBHipError("fast_train: " + why)
+    return plan
+
+
+def _held(h, li, chw):                                                     # the walk's check of what a launch returned against the plan
+    if tuple(h.shape[1:4]) != chw:
+        raise _lib.BBBHipError(f"fast_train: layer {li} left a {tuple(h.shape[1:4])} map where the analysed model has {chw}: the "
+                               "model's geometry changed since it was analysed -- call ensemble.invalidate(net) after changing a "
+                               "stride, a padding or a pool in place")
+
+
+def _walk(plan, h, run_layer, pool, avgpool=None):
+    """The forward walk over a TrainPlan (train_plan), one copy for the four nodes: -> (tape, final h).
+    h: the batch-innermost input [1, C, H, W, B].  run_layer(blk, x_in) -> a record holding at least `y`, the activated output
+    [E', *blk.conv_chw, B], of the block's layer on x_in = h as [*, *blk.in_chw, B], with blk.geom and blk.act (fused).
+    pool(y, kernel, stride): the node's max pooling; avgpool(y, kernel, stride, padding, count_include_pad): its average pooling --
+    each called with blk.pool, the spec of the pool behind the layer, unpacked.
+    The walk completes the record from the block -- layer, x, act, geom, wshape, pool (that spec: its kind, and as a tuple the
+    arguments above; None without a pool), first, out_shape (of what the next layer reads) -- and appends it to the tape.  The plan is
+    an analysis cached on the model: what a launch returns is held against it, so a geometry changed in place since then raises
+    instead of running unadmitted."""
     tape = []                                                              # per Bayesian layer, in forward order
-    i = 0
-    while i < len(mods):
-        m = mods[i]
-        if is_layer(m):
-            is_conv = isinstance(m, (BBBConv2d, LRTConv2d))
-            geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
-            x_in = h if is_conv else h.reshape(h.shape[0], m.in_features, 1, 1, B)
-            act = ensemble._act_name(mods[i + 1]) if i + 1 < len(mods) else None
-            if act is not None:
-                i += 1
-            nxt = mods[i + 1] if i + 1 < len(mods) else None
-            pool_mod = nxt if pool_desc.is_pool(nxt) else None
-            rec = run_layer(m, len(tape), x_in, is_conv, geom, act, pool_mod is not None)
-            rec.update(layer=m, x=x_in, act=act, geom=geom, pool=None, first=not tape)
-            h = rec["y"]
-            if pool_mod is not None:
-                spec = pool_desc.pool_of(pool_mod, h.shape[-3], h.shape[-2])
-                run_pool = None if spec is None else pool if spec.kind == "max" else avgpool
-                if run_pool is None:
-                    raise _lib.BBBHipError("fast_train: a pool this path does not take (train_path_ok refuses it)")
-                h = run_pool(h, *spec)
-                rec["pool"] = spec
-                i += 1
-            rec["out_shape"] = tuple(h.shape)
-            tape.append(rec)
-        elif pool_desc.is_pool(m):                                                 # a pool that does not follow a Bayesian layer: on the input
-            raise _lib.BBBHipError("fast_train: pooling must follow a Bayesian layer")
-        elif isinstance(m, FlattenLayer):
-            h = h.reshape(h.shape[0], m.num_features, 1, 1, B)
-        i += 1
+    for blk in plan.blocks:
+        x_in = h.reshape(h.shape[0], *blk.in_chw, h.shape[-1])
+        rec = run_layer(blk, x_in)
+        rec.update(layer=blk.layer, x=x_in, act=blk.act, geom=blk.geom, wshape=blk.wshape, pool=blk.pool, first=blk.first)
+        h = rec["y"]
+        _held(h, blk.li, blk.conv_chw)
+        if blk.pool is not None:
+            h = (pool if blk.pool.kind == "max" else avgpool)(h, *blk.pool)
+            _held(h, blk.li, blk.out_chw)
+        rec["out_shape"] = tuple(h.shape)
+        tape.append(rec)
     return tape, h
 
 
@@ -310,22 +326,20 @@ class _MCForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, *params):
-        from . import ensemble
-        _BBBLayer = _layers()[0]
+        plan = _node_plan(cfg, x)
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-        mods = ensemble.flat_children(cfg["net"])
-        layers = [m for m in mods if isinstance(m, _BBBLayer)]
+        layers = [b.layer for b in plan.blocks]
         mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
         pm, ps = layers[0].prior_mu, layers[0].prior_sigma
         ws, _, kl = ops.reparam_kl_forward(mus, rhos, pm, ps, ids, seed, call0, draws=E)
 
-        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
-            w, b = ws[2 * li], ws[2 * li + 1]
-            w5 = w if is_conv else w.reshape(E, m.out_features, m.in_features, 1, 1)
-            return dict(w=w5, y=ops.conv2d_chwn_forward(x_in, w5, b, *geom, act=act))
+        def run_layer(blk, x_in):
+            w, b = ws[2 * blk.li], ws[2 * blk.li + 1]
+            w5 = w if blk.is_conv else w.reshape(E, *blk.wshape)
+            return dict(w=w5, y=ops.conv2d_chwn_forward(x_in, w5, b, *blk.geom, act=blk.act))
 
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)               # [1, C, H, W, B]
-        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn, ops.avgpool_chwn)
+        tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn, ops.avgpool_chwn)
         _carry(ctx, cfg, params)
         ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
         ctx.x_nchw = x.detach()
@@ -426,27 +440,21 @@ class _MCForwardBF16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, *params):
-        from . import ensemble
-        _BBBLayer = _layers()[0]
+        plan = _node_plan(cfg, x)
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-        mods = ensemble.flat_children(cfg["net"])
-        layers = [m for m in mods if isinstance(m, _BBBLayer)]
+        layers = [b.layer for b in plan.blocks]
         mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
         pm, ps = layers[0].prior_mu, layers[0].prior_sigma
         kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E)
 
-        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
-            w, b = ws[2 * li], ws[2 * li + 1]
-            wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
-            last = li == len(layers) - 1
-            if last and (act is not None or pooled):
-                raise _lib.BBBHipError("bf16 training: the logits layer (fp32 output) must not be followed by an activation or a pool")
-            y = ops.conv2d_chwn_bf16_forward(x_in, w, b, wshape[1:], *geom, act=act, out_f32=last,
-                                             tap_major=is_conv and ops.bf16_tap_major(wshape))
-            return dict(w=w, wshape=wshape, y=y)
+        def run_layer(blk, x_in):                          # (the logits layer, fp32 output: the plan ends in it, bare)
+            w, b = ws[2 * blk.li], ws[2 * blk.li + 1]
+            y = ops.conv2d_chwn_bf16_forward(x_in, w, b, blk.wshape[1:], *blk.geom, act=blk.act, out_f32=blk.last,
+                                             tap_major=blk.is_conv and ops.bf16_tap_major(blk.wshape))
+            return dict(w=w, y=y)
 
         h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
-        tape, h = _walk(mods, h, lambda m: isinstance(m, _BBBLayer), run_layer, ops.maxpool_chwn_bf16, ops.avgpool_chwn_bf16)
+        tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn_bf16, ops.avgpool_chwn_bf16)
         _carry(ctx, cfg, params)
         ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
         # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted); frozen parameters
@@ -544,16 +552,15 @@ class _MCForwardLRT(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cfg, x, *params):
-        from . import ensemble
-        _LRTLayer = _layers()[3]
+        plan = _node_plan(cfg, x)
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
 
-        def run_layer(m, li, x_in, is_conv, geom, act, pooled):
-            w_mu, w_var, b_mu, b_var = (t.detach() for t in params[4 * li:4 * li + 4])
-            if not is_conv:
-                shp = (m.out_features, m.in_features, 1, 1)
-                w_mu, w_var = w_mu.reshape(shp), w_var.reshape(shp)
-            sid = m._stream_base + 2
+        def run_layer(blk, x_in):
+            geom, act = blk.geom, blk.act
+            w_mu, w_var, b_mu, b_var = (t.detach() for t in params[4 * blk.li:4 * blk.li + 4])
+            if not blk.is_conv:
+                w_mu, w_var = w_mu.reshape(blk.wshape), w_var.reshape(blk.wshape)
+            sid = blk.layer._stream_base + 2
             if x_in.shape[0] == 1 and E > 1:              # the shared first layer: one pair of moments, E samples of it
                 _, am, av = ops.lrt_conv2d_chwn_forward(x_in, w_mu, w_var, b_mu, b_var, seed, call0, sid, *geom, sample=False,
                                                         want_moments=True, act=None)
@@ -564,8 +571,7 @@ class _MCForwardLRT(torch.autograd.Function):
             return dict(w_mu=w_mu, w_var=w_var, y=y, am=am, av=av)
 
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)
-        tape, h = _walk(ensemble.flat_children(cfg["net"]), h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn,
-                        ops.avgpool_chwn)
+        tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn, ops.avgpool_chwn)
         _carry(ctx, cfg, params)
         ctx.tape = tape
         ctx.x_nchw = x.detach()
@@ -675,37 +681,31 @@ def _lrt_bf16_forward(cfg, x, params):
     ops.maxpool_chwn_bf16 unfused), so the logits are that path's bit for bit, with the fp32 act_var of every layer kept beside them.
     params: per layer W_mu, sigma_W^2, bias_mu, sigma_b^2 (fp32).  A record of the tape: x (the bf16 input), y (the stored bf16
     activated output before the pool; the logits layer's is fp32), av (act_var: y's shape, or one draw's worth for the shared first
-    layer), w_mu / w_var (the bf16 rows), wshape, sid (the noise stream), and what _walk adds (geom, act, pool, first, out_shape)."""
-    from . import ensemble
-    _LRTLayer = _layers()[3]
+    layer), w_mu / w_var (the bf16 rows), sid (the noise stream), and what _walk adds (geom, act, wshape, pool, first, out_shape)."""
+    plan = _node_plan(cfg, x)
     E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-    mods = ensemble.flat_children(cfg["net"])
-    n_layers = sum(isinstance(m, _LRTLayer) for m in mods)
     params = [t.detach() for t in params]
-    rows = ops.lrt_weights_bf16([params[4 * li + j] for li in range(n_layers) for j in (0, 1)])
+    rows = ops.lrt_weights_bf16([params[4 * li + j] for li in range(len(plan.blocks)) for j in (0, 1)])
 
-    def run_layer(m, li, x_in, is_conv, geom, act, pooled):
+    def run_layer(blk, x_in):                              # (the logits layer, fp32 output: the plan ends in it, bare)
+        li, act, last = blk.li, blk.act, blk.last
         w_mu, w_var, b_mu, b_var = rows[2 * li], rows[2 * li + 1], params[4 * li + 2], params[4 * li + 3]
-        wshape = tuple(m.W_mu.shape) if is_conv else (m.out_features, m.in_features, 1, 1)
-        last = li == n_layers - 1
-        if last and (act is not None or pooled):
-            raise _lib.BBBHipError("bf16 LRT input gradients: the logits layer (fp32 output) must not be followed by an activation or a pool")
-        sid = m._stream_base + 2
-        tapm = is_conv and ops.bf16_tap_major(wshape)
-        args = (x_in, w_mu, w_var, b_mu, b_var, wshape[1:], seed, call0, sid, *geom)
+        sid = blk.layer._stream_base + 2
+        tapm = blk.is_conv and ops.bf16_tap_major(blk.wshape)
+        args = (x_in, w_mu, w_var, b_mu, b_var, blk.wshape[1:], seed, call0, sid, *blk.geom)
         if x_in.shape[0] == 1 and E > 1 and not last:        # the shared first layer: one pair of moments, E samples of it
             _, am, av = ops.lrt_conv2d_chwn_bf16_forward(*args, sample=False, moments_only=True, tap_major=tapm)
             y = ops.lrt_sample_chwn_bf16(am, av, E, seed, call0, sid, act=act)
         else:
             y, _, av = ops.lrt_conv2d_chwn_bf16_forward(*args, sample=True, want_moments=True, act=act, out_f32=last, tap_major=tapm,
                                                         n_slabs=E)
-        return dict(w_mu=w_mu, w_var=w_var, wshape=wshape, y=y, av=av, sid=sid)
+        return dict(w_mu=w_mu, w_var=w_var, y=y, av=av, sid=sid)
 
     def no_avgpool(*a):
         raise _lib.BBBHipError("bf16 LRT input gradients: no average pools (bf16_train_refusal refuses them)")
 
     h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)              # [1, C, H, W, B] bf16
-    tape, h = _walk(mods, h, lambda m: isinstance(m, _LRTLayer), run_layer, ops.maxpool_chwn_bf16, no_avgpool)
+    tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn_bf16, no_avgpool)
     return tape, h.reshape(E, -1, x.shape[0])
 
 

@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, pool_desc, _lib
-from .conv_desc import pooled_map          # (a query, not a launch: asked directly, as pool_desc is)
+from .conv_desc import out_map, pooled_map  # (queries, not launches: asked directly, as pool_desc is)
 from layers.bbb import _BBBLayer, BBBConv2d as _BBBConv
 from layers.lrt import _LRTLayer, BBBConv2d as _LRTConv
 from layers.misc import FlattenLayer
@@ -143,11 +143,6 @@ def _ckk(mod):
     return (mod.in_channels, *mod.kernel_size) if _is_conv(mod) else (mod.in_features, 1, 1)
 
 
-def _out_hw(H, W, ckk, geom):
-    (sh, sw), (ph, pw), (dh, dw) = (ops._pair(g) for g in geom)
-    return (H + 2 * ph - dh * (ckk[1] - 1) - 1) // sh + 1, (W + 2 * pw - dw * (ckk[2] - 1) - 1) // sw + 1
-
-
 def _chwn_modes(children, x_shape, draws, precision, cfg):
     """Which kernel family every Bayesian layer takes -> (layers on the MFMA-ready-operand kernel, the space-to-depth first layer or
     None, lrt_mode, split_mode).
@@ -253,7 +248,7 @@ class _Planner:
             raise _NoPlan
         if use_c8 and self.lay != "c8s3":
             self.emit("to_c8s3", i, mod, "c8s3", (C, H, W, self.B), 0)
-        ho, wo = _out_hw(H, W, ckk, geom)
+        ho, wo = out_map(H, W, ckk[1:], *geom)
         kw["out_f32"] = last if use_c8 else (last and self.tail_is_last and self.bf16)
         if isinstance(mod, _BBBLayer) and self.bf16:
             kw.update(self.bf16_bbb(i, mod, act, kw))
@@ -300,7 +295,7 @@ class _Planner:
         out_c8 = False
         nb = self.children[at + 1] if (fuse and at + 1 < len(self.children)) else None
         if isinstance(nb, _BBBConv) and (mod.out_channels if is_conv else mod.out_features) % 8 == 0 and not kw["logits"]:
-            hw = pooled_map(*_out_hw(H, W, ckk, geom), pool_ks)
+            hw = pooled_map(*out_map(H, W, ckk[1:], *geom), pool_ks)
             out_c8 = ops.bf16_c8_input_ok((nb.in_channels, *nb.kernel_size), (nb.stride, nb.padding, nb.dilation),
                                           ops.bf16_tap_major(tuple(nb.W_mu.shape)), at + 1 == self.last_bayes and self.tail_is_last,
                                           (hw[0], hw[1], B), self.Es)

@@ -1,9 +1,13 @@
-"""CPU-only checks of fast_train._walk, the forward walk the three training nodes share: over the module lists the other CPU tests
-build (test_strided_train_cpu.py, the zoo models of test_host_cpu.py) and the seeded families of the training fuzz suites, with
-stub callbacks that return CPU tensors of the right shape.  Whenever fast_train._train_path_static admits a model the walk yields
-one record per Bayesian layer with the activation, pool, `first`, geometry and out_shape the nodes' backward relies on (restated
-here from the module list and torch's own shape arithmetic); a linear layer receives [*, in_features, 1, 1, B]; a FlattenLayer
-reshapes to num_features; a pool that follows no layer raises."""
+"""CPU-only checks of fast_train.train_plan and fast_train._walk, the layer plan and the forward walk over it that the training nodes
+share: over the module lists the other CPU tests build (test_strided_train_cpu.py, the zoo models of test_host_cpu.py) and the seeded
+families of the training fuzz suites, with stub callbacks that return CPU tensors of the right shape.  Whenever
+fast_train._train_path_static admits a model the plan's blocks carry the maps and weight shape torch's own shape arithmetic gives,
+and the walk yields one record per Bayesian layer with the activation, pool, `first`, geometry and out_shape the nodes' backward
+relies on (restated here from the module list and torch's shapes); a linear layer receives [*, in_features, 1, 1, B]; a FlattenLayer
+reshapes to num_features; a pool that follows no layer is refused by the parser; a geometry changed in place on an analysed model
+raises in the walk until ensemble.invalidate."""
+import re
+
 import pytest
 import torch
 import torch.nn as nn
@@ -46,11 +50,13 @@ def _nchw(t5):                             # [E', C, H, W, B] -> [E' * B, C, H, 
 
 
 def _stubs(B, seen):
-    def run_layer(m, li, x_in, is_conv, geom, act, pooled):
-        seen.append(dict(li=li, x_shape=tuple(x_in.shape), is_conv=is_conv, act=act, pooled=pooled))
+    def run_layer(blk, x_in):                  # (convolves with the LIVE module's geometry, as a node's launch of a mutated model would)
+        m, li, is_conv = blk.layer, blk.li, blk.is_conv
+        seen.append(dict(li=li, x_shape=tuple(x_in.shape), is_conv=is_conv, act=blk.act, pooled=blk.pool is not None))
         assert is_conv == hasattr(m, "kernel_size")
         cout, cin = (m.out_channels, m.in_channels) if is_conv else (m.out_features, m.in_features)
         k = tuple(m.kernel_size) if is_conv else (1, 1)
+        geom = (m.stride, m.padding, m.dilation) if is_conv else (1, 0, 1)
         y = F.conv2d(_nchw(x_in[:1]), torch.zeros(cout, cin, *k), None, *geom)                    # [B, Cout, Ho, Wo]
         return dict(y=y.permute(1, 2, 3, 0).unsqueeze(0).expand(E, -1, -1, -1, -1), mine=li)
 
@@ -62,7 +68,8 @@ def _stubs(B, seen):
 
 
 def _expected(mods, x_shape):
-    """Per Bayesian layer (act, pool, geom, out_shape), from the module list and torch's shapes alone."""
+    """Per Bayesian layer (act, pool, geom, out_shape; in_chw, conv_chw, out_chw, wshape), from the module list and torch's shapes
+    alone."""
     from layers.misc import FlattenLayer
     B = x_shape[0]
     h = torch.zeros(x_shape)
@@ -73,8 +80,11 @@ def _expected(mods, x_shape):
         if hasattr(m, "W_mu"):
             conv = hasattr(m, "kernel_size")
             geom = (m.stride, m.padding, m.dilation) if conv else (1, 0, 1)
-            h = F.conv2d(h, torch.zeros(m.W_mu.shape), None, *geom) if conv else torch.zeros(B, m.out_features)
-            ent = dict(layer=m, act=None, pool=None, geom=geom, first=not out)
+            w = torch.zeros(m.W_mu.shape) if conv else torch.zeros(m.out_features, m.in_features, 1, 1)
+            x4 = h if conv else h.reshape(B, m.in_features, 1, 1)
+            h = F.conv2d(x4, w, None, *geom)
+            ent = dict(layer=m, act=None, pool=None, geom=geom, first=not out, in_chw=tuple(x4.shape[1:]), conv_chw=tuple(h.shape[1:]),
+                       wshape=tuple(w.shape))
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             if isinstance(nxt, (nn.ReLU, nn.Softplus)):
                 ent["act"] = "relu" if isinstance(nxt, nn.ReLU) else "softplus"
@@ -84,7 +94,8 @@ def _expected(mods, x_shape):
                 ent["pool"] = (nxt.kernel_size, nxt.stride)
                 h = F.max_pool2d(h, nxt.kernel_size, nxt.stride)
                 i += 1
-            ent["out_shape"] = (E, h.shape[1]) + (tuple(h.shape[2:]) if h.dim() == 4 else (1, 1)) + (B,)
+            ent["out_chw"] = tuple(h.shape[1:])
+            ent["out_shape"] = (E,) + ent["out_chw"] + (B,)
             out.append(ent)
         elif isinstance(m, FlattenLayer):
             h = h.reshape(B, -1)
@@ -97,7 +108,7 @@ def _walk(net, x_shape, seen):
     from bbb_hip import ensemble, fast_train
     mods = ensemble.flat_children(net)
     run_layer, pool = _stubs(x_shape[0], seen)
-    tape, h = fast_train._walk(mods, _chwn(torch.zeros(x_shape)), lambda m: hasattr(m, "W_mu"), run_layer, pool)
+    tape, h = fast_train._walk(fast_train.train_plan(net, x_shape), _chwn(torch.zeros(x_shape)), run_layer, pool)
     return mods, tape, h
 
 
@@ -119,6 +130,11 @@ def test_walk_records_what_the_backward_reads(name):
     want = _expected(mods, x_shape)
     assert len(tape) == len(want) == len([m for m in mods if hasattr(m, "W_mu")])
     B = x_shape[0]
+    plan = fast_train.train_plan(net, x_shape)
+    assert plan.kind == fast_train._train_path_static(net, torch.zeros(x_shape)) and len(plan.blocks) == len(want)
+    for li, (blk, w) in enumerate(zip(plan.blocks, want)):                          # the plan against torch's own shapes
+        assert blk.layer is w["layer"] and blk.li == li and (blk.first, blk.last) == (li == 0, li == len(want) - 1)
+        assert (blk.in_chw, blk.conv_chw, blk.out_chw, blk.wshape) == (w["in_chw"], w["conv_chw"], w["out_chw"], w["wshape"])
     for li, (rec, w, s) in enumerate(zip(tape, want, seen)):
         assert rec["layer"] is w["layer"] and rec["mine"] == li == s["li"]          # the node's own keys stay in the record
         assert (rec["act"], rec["pool"], rec["geom"], rec["first"]) == (w["act"], w["pool"], w["geom"], w["first"])
@@ -150,7 +166,7 @@ def test_flatten_reshapes_to_num_features():
 
 @pytest.mark.parametrize("where", ["leading", "after_pool", "after_flatten"])
 def test_a_pool_that_follows_no_layer_raises(where):
-    from bbb_hip import _lib
+    from bbb_hip import _lib, ensemble, fast_train
     from layers import BBB_Conv2d, BBB_Linear, FlattenLayer, ModuleWrapper
     net = ModuleWrapper()
     if where == "leading":
@@ -164,5 +180,46 @@ def test_a_pool_that_follows_no_layer_raises(where):
     if where == "after_flatten":
         net.add_module("p3", nn.MaxPool2d(1, 1))
     net.add_module("f1", BBB_Linear(512, 10, bias=True, priors=P.CONFIG_PRIORS))
-    with pytest.raises(_lib.BBBHipError, match="fast_train: pooling must follow a Bayesian layer"):
-        _walk(net, (8, 3, 16, 16), [])
+    assert fast_train.train_plan(net, (8, 3, 16, 16)) is None
+    plan, why = fast_train._parse(ensemble.flat_children(net), (8, 3, 16, 16))
+    assert plan is None and re.search("pooling must follow a Bayesian layer", why)
+    with pytest.raises(_lib.BBBHipError, match="fast_train: pooling must follow a Bayesian layer"):    # what a node's forward raises
+        fast_train._node_plan(dict(net=net), torch.zeros(8, 3, 16, 16))
+
+
+def test_a_geometry_changed_in_place_raises_until_invalidate():
+    """The plan is an analysis cached on the model (ensemble._structure).  A stride changed in place afterwards: the walk holds what
+    the layer's launch returns (the stubs convolve with the live module's geometry) against the plan and raises, naming
+    ensemble.invalidate; after it the plan carries the new geometry and the walk passes."""
+    from bbb_hip import _lib, ensemble, fast_train
+    from layers import BBB_Conv2d, BBB_Linear, FlattenLayer, ModuleWrapper
+    net = ModuleWrapper()
+    net.add_module("conv1", BBB_Conv2d(3, 8, 3, padding=1, bias=True, priors=P.CONFIG_PRIORS))
+    net.add_module("act1", nn.ReLU())
+    net.add_module("conv2", BBB_Conv2d(8, 8, 3, padding=1, bias=True, priors=P.CONFIG_PRIORS))
+    net.add_module("act2", nn.ReLU())
+    net.add_module("gap", nn.AdaptiveAvgPool2d(1))                   # (one feature per channel at either stride)
+    net.add_module("flatten", FlattenLayer(8))
+    net.add_module("fc", BBB_Linear(8, 10, bias=True, priors=P.CONFIG_PRIORS))
+    x_shape = (8, 3, 8, 8)
+    run_layer, pool = _stubs(x_shape[0], [])
+
+    def avgpool(y, k, s, p, count_include_pad):
+        q = F.avg_pool2d(_nchw(y), k, s, p, count_include_pad=count_include_pad)
+        return q.reshape(y.shape[0], x_shape[0], *q.shape[1:]).permute(0, 2, 3, 4, 1)
+
+    def walk():
+        return fast_train._walk(fast_train.train_plan(net, x_shape), _chwn(torch.zeros(x_shape)), run_layer, pool, avgpool)
+
+    before = fast_train.train_plan(net, x_shape)
+    assert before.blocks[1].geom[0] == 1 and (before.blocks[1].conv_chw, before.blocks[1].out_chw) == ((8, 8, 8), (8, 1, 1))
+    assert tuple(walk()[1].shape) == (E, 10, 1, 1, 8)
+    net.conv2.stride = 2                                              # in place: no hook sees it, the cached plan stays
+    assert fast_train.train_plan(net, x_shape) is before
+    with pytest.raises(_lib.BBBHipError, match=r"geometry changed since it was analysed.*ensemble\.invalidate\(net\)"):
+        walk()
+    ensemble.invalidate(net)
+    after = fast_train.train_plan(net, x_shape)
+    assert after.blocks[1].geom[0] == 2 and (after.blocks[1].conv_chw, after.blocks[1].out_chw) == ((8, 4, 4), (8, 1, 1))
+    assert tuple(after.blocks[1].pool[0]) == (4, 4) and tuple(before.blocks[1].pool[0]) == (8, 8)
+    assert tuple(walk()[1].shape) == (E, 10, 1, 1, 8)

@@ -293,6 +293,26 @@ def test_lenet_is_eligible_and_odd_batches_fall_back(env):
     assert env["ens"].stats["path"] == "nchw" and lo.requires_grad
 
 
+def test_a_model_off_the_path_raises_the_parsers_reason_in_the_node(env):
+    """mc_logits_autograd is to be called when train_path_ok: on a model the parser refuses (a pool that follows no layer) the node's
+    forward raises the parser's reason before its first launch."""
+    import torch.nn as nn
+    from bbb_hip import _lib
+    from layers import BBB_Conv2d, BBB_Linear, FlattenLayer, ModuleWrapper
+    net = ModuleWrapper()
+    net.add_module("p0", nn.MaxPool2d(2, 2))
+    net.add_module("c1", BBB_Conv2d(3, 8, 3, padding=1, bias=True, priors=P.CONFIG_PRIORS))
+    net.add_module("a1", nn.ReLU())
+    net.add_module("fl", FlattenLayer(8 * 4 * 4))
+    net.add_module("f1", BBB_Linear(8 * 4 * 4, 10, bias=True, priors=P.CONFIG_PRIORS))
+    net = net.cuda()
+    env["rng"].assign_stream_ids(net)
+    x = torch.rand(8, 3, 8, 8, device="cuda")
+    assert env["ft"].train_path_ok(net, x) is None and env["ft"].train_plan(net, x.shape) is None
+    with pytest.raises(_lib.BBBHipError, match="fast_train: pooling must follow a Bayesian layer"):
+        env["ft"].mc_logits_autograd(net, x, 2, 7, 0)
+
+
 def test_dropin_forward_with_autograd_uses_the_fast_kernels(env):
     ens = env["ens"]
     torch.manual_seed(2)
