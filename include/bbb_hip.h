@@ -159,6 +159,65 @@ int bbb_adam_step_plan(const bbb_adam_segment_t* segs, int nseg, double lr, doub
                        int64_t step, const float* step_dev, const float* lr_dev, int32_t* chunks, int32_t* chunk_begin,
                        float* scalars, int32_t* vec);
 
+/*
+ * Global gradient norm for clipping and for the non-finite guard (training extension, additive to ABI 13; csrc/grad_norm.hip).
+ *   norm = fp32(sqrt(sum over every element of every tensor of double(g)^2)): every square and every partial sum is float64, the
+ *   root is float64, ONE rounding to fp32.  Range-free: 1537 gradients of 1e30 give 3.9e31, of 1e-30 give 3.9e-29.  Any NaN gives
+ *   NaN; +-Inf without a NaN gives +Inf.
+ * bbb_grad_sumsq: up to BBB_MAX_SEGMENTS segments, of which ONLY grad and n are read (the other pointers may be anything).  One
+ *   256-thread block per 4096-element chunk of a segment writes that chunk's sum of squares to partials[first + chunk] (device
+ *   float64, 8-byte aligned).  A tensor list longer than 16 takes several launches with `first` advanced by the chunks before it.
+ *   A chunk's partial is a fixed tree over its elements and does not depend on the alignment of grad (the 16-byte path differs in
+ *   the loads only).  Nothing else is written.  Checks: BBB_EINVAL (null segs / partials / grad, nseg outside 1..16, n <= 0,
+ *   first < 0), BBB_EALIGN (partials not 8-byte, grad not 4-byte aligned), BBB_ESHAPE (first + chunks above 2^31 - 1).
+ * bbb_grad_norm_finish: ONE block sums partials[0 .. npartials) in index order as a fixed tree in float64 and writes
+ *   *norm_out = the fp32 norm;
+ *   *coef_out = fp32(min(1, max_norm / (double(norm) + 1e-6))) -- torch.nn.utils.clip_grad_norm_'s coefficient, evaluated in double on
+ *               the fp32 norm and rounded once; the comparison is written out, so a NaN norm gives NaN (not 1), an Inf norm 0, and
+ *               the value is exactly 1.0f when nothing is clipped.  max_norm = +inf is "norm only": 1 unless the norm is NaN;
+ *   *ok_out   = 0.0f when skip != 0 and the norm is not finite, else 1.0f;
+ *   *skipped_out += 1 (device int32) when skip != 0 and the norm is not finite.
+ *   coef_out, ok_out and skipped_out may be NULL.  Checks: BBB_EINVAL (null partials / norm_out, npartials <= 0), BBB_EALIGN
+ *   (partials not 8-byte, an output not 4-byte aligned), BBB_EINVAL (max_norm <= 0 or NaN), BBB_ESHAPE (npartials above 2^31 - 1).
+ * The reduction across workgroups happens at the launch boundary between the two: no ticket, counter, spin or atomic, so neither
+ * launch can wait on anything, and the result is bitwise reproducible -- it depends on the values and the ORDER of the tensors only,
+ * not on how they are dealt to launches.  Both launches are legal inside a stream capture.
+ * The _plan entries are host only and need no device: the sumsq plan reports *chunks, chunk_begin[17] and vec[16] (1: grad 16-byte
+ * aligned and n >= 4) and writes zeros on a refusal; the finish plan returns the finish launch's code and, when `coef` is not NULL,
+ * the coefficient it would write for the fp32 norm `norm` (0 on a refusal).
+ */
+int bbb_grad_sumsq(const bbb_adam_segment_t* segs, int nseg, double* partials, int64_t first, void* stream);
+int bbb_grad_sumsq_plan(const bbb_adam_segment_t* segs, int nseg, const double* partials, int64_t first, int32_t* chunks,
+                        int32_t* chunk_begin, int32_t* vec);
+int bbb_grad_norm_finish(const double* partials, int64_t npartials, double max_norm, int skip, float* norm_out, float* coef_out,
+                         float* ok_out, int32_t* skipped_out, void* stream);
+int bbb_grad_norm_finish_plan(const double* partials, int64_t npartials, double max_norm, const float* norm_out, const float* coef_out,
+                              const float* ok_out, const int32_t* skipped_out, float norm, float* coef);
+
+/*
+ * bbb_adam_step with weight decay, a clip coefficient and a skip flag (additive to ABI 13).  Per element, each line of bbb_adam_step
+ * in its own operation order, preceded by
+ *   g1 = coef * g                        one fp32 rounding; only with coef_dev (DEVICE float, e.g. bbb_grad_norm_finish's coef_out)
+ *   decoupled != 0:  p0 = p * decay      decay = fp32(1 - lr * weight_decay) formed in double (torch: param.mul_(1 - lr * wd));
+ *                                        with lr_dev the kernel forms it from the device rate, as it does step_size
+ *   decoupled == 0:  g1 = g1 + wd32 * p  wd32 = fp32(weight_decay), two roundings (torch: grad.add(param, alpha = wd))
+ * and then m' = m + (g1 - m)(1 - beta1), v' = v beta2 + (1 - beta2) g1 g1, p' = p0 - step_size (m' / (sqrt(v') / sqrt_bc2 + eps)).
+ * weight_decay == 0 applies neither form.  ok_dev (DEVICE float, optional): when it holds 0 the launch stores NOTHING -- parameters
+ * and both moments stay bit for bit (a skipped step; the caller keeps the step count).  grad is never written: unlike
+ * torch.nn.utils.clip_grad_norm_, clipping scales the gradient on its way into the update and leaves the tensor as it is.
+ * With weight_decay = 0, coef_dev = NULL and ok_dev = NULL -- or with both pointing at 1.0f -- the results are bbb_adam_step's bits
+ * (one kernel body, compile-time switches).  Checks: all of bbb_adam_step's in its order, then coef_dev / ok_dev 4-byte aligned
+ * (BBB_EALIGN), then weight_decay >= 0 and not NaN (BBB_EINVAL).
+ * bbb_adam_step_ex_plan: as bbb_adam_step_plan; scalars[9] = its seven, then wd32 and decay; *mode = 0 (no decay), 1 (L2), 2 (decoupled).
+ */
+int bbb_adam_step_ex(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, int decoupled, int64_t step, const float* step_dev, const float* lr_dev,
+                     const float* coef_dev, const float* ok_dev, void* stream);
+int bbb_adam_step_ex_plan(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int decoupled, int64_t step, const float* step_dev, const float* lr_dev,
+                          const float* coef_dev, const float* ok_dev, int32_t* chunks, int32_t* chunk_begin, float* scalars,
+                          int32_t* vec, int32_t* mode);
+
 /* Test entry: materialise n elements of a noise stream starting at element `start`. */
 int bbb_eps_dump(float* out, int64_t n, int64_t start, uint64_t seed, uint32_t call, uint32_t stream_id, void* stream);
 

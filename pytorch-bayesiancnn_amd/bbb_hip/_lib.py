@@ -71,6 +71,18 @@ _SIGNATURES = {
     "bbb_adam_step_plan": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, c_i64, c_void_p, c_void_p, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
                                    ctypes.POINTER(c_float), ctypes.POINTER(c_i32)]),
+    "bbb_grad_sumsq": (c_int, [ctypes.POINTER(AdamSegment), c_int, c_void_p, c_i64, c_void_p]),
+    "bbb_grad_sumsq_plan": (c_int, [ctypes.POINTER(AdamSegment), c_int, c_void_p, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                    ctypes.POINTER(c_i32)]),
+    "bbb_grad_norm_finish": (c_int, [c_void_p, c_i64, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bbb_grad_norm_finish_plan": (c_int, [c_void_p, c_i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                          ctypes.POINTER(c_float)]),
+    "bbb_adam_step_ex": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_double, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bbb_adam_step_ex_plan": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_float), ctypes.POINTER(c_i32),
+                                      ctypes.POINTER(c_i32)]),
     "bbb_eps_dump": (c_int, [c_void_p, c_i64, c_i64, c_u64, c_u32, c_u32, c_void_p]),
     "bbb_conv2d_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "bbb_lrt_conv2d_fwd": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -237,6 +237,61 @@ def adam_plan(segs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, step=1, step_dev=0, l
     return plan
 
 
+def _adam_segments(segs, nseg):
+    """adam_plan's segment forms -> (ctypes array, nseg)."""
+    if isinstance(segs, ctypes.Array):
+        return segs, (len(segs) if nseg is None else nseg)
+    arr = (_lib.AdamSegment * max(len(segs), 1))()
+    for s, item in zip(arr, segs):
+        s.param = s.grad = s.exp_avg = s.exp_avg_sq = 4096
+        for k, v in ({"n": item} if isinstance(item, int) else dict(item)).items():
+            setattr(s, k, v)
+    return arr, (len(segs) if nseg is None else nseg)
+
+
+ADAM_PLAN_EX_SCALARS = ADAM_PLAN_SCALARS + ("wd32", "decay")
+ADAM_EX_MODES = ("none", "l2", "decoupled")
+
+
+def adam_plan_ex(segs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, step=1, step_dev=0, lr_dev=0,
+                 coef_dev=0, ok_dev=0, nseg=None):
+    """What bbb_adam_step_ex launches (bbb_adam_step_ex_plan; host only).  As adam_plan, plus the fp32 scalars wd32 and decay and
+    `mode`: "none" (weight_decay == 0), "l2" or "decoupled".  A refusal is reported in `status` and leaves every other field zero
+    (mode "none")."""
+    arr, nseg = _adam_segments(segs, nseg)
+    chunks, begin = ctypes.c_int32(0), (ctypes.c_int32 * (_lib.MAX_SEGMENTS + 1))()
+    sc, vec, mode = (ctypes.c_float * len(ADAM_PLAN_EX_SCALARS))(), (ctypes.c_int32 * _lib.MAX_SEGMENTS)(), ctypes.c_int32(0)
+    rc = _lib.lib().bbb_adam_step_ex_plan(arr, nseg, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                          int(bool(decoupled)), int(step), step_dev or None, lr_dev or None, coef_dev or None,
+                                          ok_dev or None, ctypes.byref(chunks), begin, sc, vec, ctypes.byref(mode))
+    plan = {"status": rc, "chunks": chunks.value, "chunk_begin": list(begin), "vec": [bool(v) for v in vec[:max(min(nseg, len(vec)), 0)]],
+            "mode": ADAM_EX_MODES[mode.value]}
+    plan.update(zip(ADAM_PLAN_EX_SCALARS, sc))
+    return plan
+
+
+GRAD_NORM_CHUNK = 4096
+
+
+def grad_norm_plan(segs, partials=4096, first=0, nseg=None, max_norm=None, norm=0.0, outs=(4096, 4096, 4096, 4096), npartials=None):
+    """What the gradient-norm launches do for these arguments (bbb_grad_sumsq_plan and bbb_grad_norm_finish_plan; host only, needs no
+    device).  segs as adam_plan's (only grad and n matter); partials: the address of the float64 buffer; first: index of this
+    launch's first partial.  Returns status, chunks (= partials written), chunk_begin (17), vec (grad 16-byte aligned and n >= 4).
+    With max_norm: also finish_status -- the finish launch's code for (partials, npartials or first + chunks, max_norm, outs = the
+    addresses of norm / coef / ok / skipped) -- and coef, the coefficient it writes for the fp32 norm `norm`."""
+    arr, nseg = _adam_segments(segs, nseg)
+    chunks, begin, vec = ctypes.c_int32(0), (ctypes.c_int32 * (_lib.MAX_SEGMENTS + 1))(), (ctypes.c_int32 * _lib.MAX_SEGMENTS)()
+    rc = _lib.lib().bbb_grad_sumsq_plan(arr, nseg, partials or None, int(first), ctypes.byref(chunks), begin, vec)
+    plan = {"status": rc, "chunks": chunks.value, "chunk_begin": list(begin), "vec": [bool(v) for v in vec[:max(min(nseg, len(vec)), 0)]]}
+    if max_norm is not None:
+        coef = ctypes.c_float(0.0)
+        n = int(first) + chunks.value if npartials is None else int(npartials)
+        plan["finish_status"] = _lib.lib().bbb_grad_norm_finish_plan(partials or None, n, float(max_norm), *[o or None for o in outs],
+                                                                     float(norm), ctypes.byref(coef))
+        plan["coef"] = coef.value
+    return plan
+
+
 def eps_dump(n, seed, call, stream_id, device, start=0):
     out = torch.empty(n, dtype=torch.float32, device=device)
     with on_device(out.device):

@@ -15,20 +15,73 @@ from ._lib import AdamSegment, check, cur_stream
 
 
 class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam(params, lr, betas, eps) semantics (amsgrad off, no weight decay) with the update of up to 16
-    parameter tensors per HIP launch (`bbb_adam_step`).  State layout matches torch's ('step', 'exp_avg', 'exp_avg_sq'),
-    so state_dicts are interchangeable with torch.optim.Adam.
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay, decoupled_weight_decay) semantics (amsgrad off) with the update of up
+    to 16 parameter tensors per HIP launch (`bbb_adam_step`; `bbb_adam_step_ex` as soon as an option below is in use).  State layout
+    matches torch's ('step', 'exp_avg', 'exp_avg_sq') and param_groups hold torch.optim.Adam's keys only, so state_dicts are
+    interchangeable with torch.optim.Adam / AdamW.
     capturable=True keeps 'step' on the device (torch's capturable convention) and lets the kernel derive the bias
     corrections from it, so the step can be part of a captured hipGraph (GraphedTrainStep).  The learning rate of a
     capturable group also lives on the device (a private per-group scalar, kept OUT of param_groups so that state_dict() holds
     exactly what torch.optim.Adam's does): `sync_lr()` copies group['lr'] there, which is how a scheduler's change reaches a
-    step that was captured earlier."""
+    step that was captured earlier.
+    weight_decay / decoupled_weight_decay (per group): Adam's L2 form g + wd p, or AdamW's p (1 - lr wd) before the update.
+    max_grad_norm (an attribute of the optimizer, global over ALL groups, not part of state_dict()): clip by the global L2 norm as
+    torch.nn.utils.clip_grad_norm_(all parameters, max_grad_norm) would before the step -- coef = min(1, max / (norm + 1e-6)) -- with
+    ONE deliberate difference: `p.grad` is never written.  The coefficient scales the gradient on its way into the update, inside the
+    Adam launch; the tensors in .grad stay as backward left them.  The norm is accumulated in float64 (`bbb_grad_sumsq`, then
+    `bbb_grad_norm_finish`), so it does not overflow or vanish where torch's fp32 norm does.
+    skip_nonfinite (attribute; implies capturable=True): a step whose gradient norm is NaN or Inf stores nothing -- parameters,
+    moments and step counts stay bit for bit -- and `skipped_steps` goes up by one.  Without it a non-finite norm does what torch does.
+    `grad_norm`, `clip_coef`, `skipped_steps`: device scalars of the last step, read without a synchronisation (None before the first
+    step with max_grad_norm or skip_nonfinite).  With neither option and no weight decay, step() launches exactly what it always did."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
-        if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, capturable=False, *,
+                 max_grad_norm=None, skip_nonfinite=False):
+        if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0) or not 0.0 <= weight_decay:
             raise ValueError("invalid Adam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, capturable=bool(capturable)))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=float(weight_decay),
+                                      decoupled_weight_decay=bool(decoupled_weight_decay),
+                                      capturable=bool(capturable) or bool(skip_nonfinite)))
         self._lr_dev = {}          # group index -> [device scalar, last value pushed]
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._norm = None          # {"partials": float64 [chunks], "scalars": fp32 [norm, coef, ok], "skipped": int32 []}
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for k, v in (("max_grad_norm", None), ("skip_nonfinite", False), ("_norm", None)):      # pickled before the options existed
+            self.__dict__.setdefault(k, v)
+
+    @property
+    def grad_norm(self):
+        return None if self._norm is None else self._norm["scalars"][0]
+
+    @property
+    def clip_coef(self):
+        return None if self._norm is None else self._norm["scalars"][1]
+
+    @property
+    def skipped_steps(self):
+        return None if self._norm is None else self._norm["skipped"]
+
+    def _norm_launches(self, grads):
+        """sumsq over `grads` (every gradient of every group, in param_groups order), then the finish launch into our scalars."""
+        dev = grads[0].device
+        chunks = sum(_norm_chunks(g) for g in grads)
+        if self._norm is None or self._norm["partials"].numel() < chunks or self._norm["partials"].device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.BBBHipError("FusedAdam's gradient-norm buffers must exist before a capture: run one step eagerly first")
+            skipped = self._norm["skipped"] if self._norm is not None and self._norm["skipped"].device == dev else \
+                torch.zeros((), dtype=torch.int32, device=dev)
+            if self._norm is not None:               # a step captured earlier reads the buffers this replaces: drop it (train._auto_key)
+                self._state_generation = getattr(self, "_state_generation", 0) + 1
+            self._norm = {"partials": torch.zeros(chunks, dtype=torch.float64, device=dev),
+                          "scalars": torch.tensor([0.0, 1.0, 1.0], dtype=torch.float32, device=dev), "skipped": skipped}
+        sc = self._norm["scalars"]
+        _grad_norm_into(grads, self._norm["partials"], self.max_grad_norm, self.skip_nonfinite, sc.data_ptr(), sc.data_ptr() + 4,
+                        sc.data_ptr() + 8, self._norm["skipped"].data_ptr())
 
     def make_capturable(self):
         """Switch every group to the capturable convention in place: 'step' counts move to the device (same values)."""
@@ -68,8 +121,24 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         L = _lib.lib()
         touched = []
+        guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        coef_dev = ok_dev = 0
+        if guarded:
+            if self.skip_nonfinite and any(not g.get("capturable", False) for g in self.param_groups):
+                self.make_capturable()
+            grads = [p.grad for group in self.param_groups for p in group["params"] if p.grad is not None]
+            if grads:
+                for g in grads:
+                    _lib.require_device(g)
+                    if not g.is_contiguous() or g.device != grads[0].device:
+                        raise _lib.BBBHipError("FusedAdam needs contiguous gradients on one device")
+                self._norm_launches(grads)
+                sc = self._norm["scalars"]
+                coef_dev = sc.data_ptr() + 4 if self.max_grad_norm is not None else 0
+                ok_dev = sc.data_ptr() + 8 if self.skip_nonfinite else 0
         for gi, group in enumerate(self.param_groups):
             cap = group.get("capturable", False)
+            wd, decoupled = float(group.get("weight_decay", 0.0)), bool(group.get("decoupled_weight_decay", False))
             by_step = {}
             for p in group["params"]:
                 if p.grad is None:
@@ -92,7 +161,12 @@ class FusedAdam(torch.optim.Optimizer):
                 steps = [st["step"] for _, st in by_step[0]]
                 if any(not t.is_cuda for t in steps):
                     raise _lib.BBBHipError("capturable FusedAdam needs its 'step' state on the device")
-                torch._foreach_add_(steps, 1.0)              # one launch; all tensors of a group step together
+                # one launch; all tensors of a group step together (a guarded step adds `ok`: 0 when it is skipped)
+                # (the tensor-LIST overload: a tensor given as the scalar would be read on the host, which a capture forbids)
+                if ok_dev:
+                    torch._foreach_add_(steps, [self._norm["scalars"][2]] * len(steps))
+                else:
+                    torch._foreach_add_(steps, 1.0)
                 # the device-side learning rate lives in a private dict keyed by group index, NOT in param_groups: state_dict()
                 # stays interchangeable with torch.optim.Adam's, and load_state_dict / map_location cannot swap or move the
                 # scalar a captured step reads
@@ -101,6 +175,7 @@ class FusedAdam(torch.optim.Optimizer):
                 elif not torch.cuda.is_current_stream_capturing():
                     self.sync_lr()
                 lr_dev = self._lr_dev[gi][0].data_ptr()
+            ex = wd != 0.0 or coef_dev != 0 or ok_dev != 0
             for step, items in by_step.items():
                 for s0 in range(0, len(items), _lib.MAX_SEGMENTS):
                     part = items[s0:s0 + _lib.MAX_SEGMENTS]
@@ -110,14 +185,66 @@ class FusedAdam(torch.optim.Optimizer):
                         segs[i].exp_avg, segs[i].exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                         segs[i].n = p.numel()
                     dev = part[0][0].device
+                    step_dev = part[0][1]["step"].data_ptr() if cap else 0
                     with torch.cuda.device(dev):
-                        check(L.bbb_adam_step(segs, len(part), float(group["lr"]), float(group["betas"][0]),
-                                              float(group["betas"][1]), float(group["eps"]), step,
-                                              part[0][1]["step"].data_ptr() if cap else 0, lr_dev, cur_stream(dev)),
-                              "bbb_adam_step")
+                        if ex:
+                            check(L.bbb_adam_step_ex(segs, len(part), float(group["lr"]), float(group["betas"][0]),
+                                                     float(group["betas"][1]), float(group["eps"]), wd, int(decoupled), step, step_dev,
+                                                     lr_dev, coef_dev, ok_dev, cur_stream(dev)), "bbb_adam_step_ex")
+                        else:
+                            check(L.bbb_adam_step(segs, len(part), float(group["lr"]), float(group["betas"][0]),
+                                                  float(group["betas"][1]), float(group["eps"]), step, step_dev, lr_dev, cur_stream(dev)),
+                                  "bbb_adam_step")
                     touched += [p for p, _ in part]
         _bump_versions(touched)
         return loss
+
+
+class FusedAdamW(FusedAdam):
+    """FusedAdam with decoupled weight decay: torch.optim.AdamW's defaults (weight_decay 1e-2)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, *, max_grad_norm=None,
+                 skip_nonfinite=False):
+        super().__init__(params, lr, betas, eps, weight_decay, True, capturable, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+
+
+def _norm_chunks(t):
+    return (t.numel() - 1) // ops.GRAD_NORM_CHUNK + 1
+
+
+def _grad_norm_into(grads, partials, max_norm, skip, norm_ptr, coef_ptr, ok_ptr, skipped_ptr):
+    """bbb_grad_sumsq over `grads` in launches of 16, then ONE bbb_grad_norm_finish: the documented launch order."""
+    L = _lib.lib()
+    dev = grads[0].device
+    first = 0
+    with torch.cuda.device(dev):
+        stream = cur_stream(dev)
+        for s0 in range(0, len(grads), _lib.MAX_SEGMENTS):
+            part = grads[s0:s0 + _lib.MAX_SEGMENTS]
+            segs = (AdamSegment * len(part))()
+            for i, g in enumerate(part):
+                segs[i].grad, segs[i].n = g.data_ptr(), g.numel()
+            check(L.bbb_grad_sumsq(segs, len(part), partials.data_ptr(), first, stream), "bbb_grad_sumsq")
+            first += sum(_norm_chunks(g) for g in part)
+        check(L.bbb_grad_norm_finish(partials.data_ptr(), first, float("inf") if max_norm is None else float(max_norm), int(bool(skip)),
+                                     norm_ptr, coef_ptr, ok_ptr, skipped_ptr, stream), "bbb_grad_norm_finish")
+
+
+def grad_norm(params):
+    """The global L2 norm of gradients as FusedAdam(max_grad_norm=...) takes it -- float64 accumulation, one rounding to fp32 -- without
+    an optimizer, for logging: a 0-d device tensor, no synchronisation.  params: tensors whose .grad is taken (one that requires a
+    gradient and has none is left out), or gradient tensors themselves (no .grad, no requires_grad)."""
+    grads = [g for g in ((t.grad if (t.grad is not None or t.requires_grad) else t) for t in params) if g is not None]
+    if not grads:
+        raise _lib.BBBHipError("grad_norm: no gradients")
+    for g in grads:
+        _lib.require_device(g)
+        if not g.is_contiguous() or g.device != grads[0].device:
+            raise _lib.BBBHipError("grad_norm needs contiguous gradients on one device")
+    partials = torch.empty(sum(_norm_chunks(g) for g in grads), dtype=torch.float64, device=grads[0].device)
+    out = torch.empty((), dtype=torch.float32, device=grads[0].device)
+    _grad_norm_into(grads, partials, None, False, out.data_ptr(), 0, 0, 0)
+    return out
 
 
 def _bump_versions(params):
@@ -247,7 +374,8 @@ def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
         return None
     # parameter STORAGE and optimizer-state identity are baked into a captured step too: net.to(...), `p.data = ...` or
     # optimizer.load_state_dict(...) after the capture must drop it (the replay would read and write freed buffers)
-    groups = tuple((tuple(g["betas"]), float(g["eps"]), tuple((id(p), p.requires_grad, p.data_ptr()) for p in g["params"]))
+    groups = tuple((tuple(g["betas"]), float(g["eps"]), float(g.get("weight_decay", 0.0)), bool(g.get("decoupled_weight_decay", False)),
+                    tuple((id(p), p.requires_grad, p.data_ptr()) for p in g["params"]))
                    for g in optimizer.param_groups)
     from . import rng
     return (id(optimizer), getattr(optimizer, "_state_generation", 0), tuple(x.shape), x.dtype, tuple(target.shape), target.dtype,
@@ -255,7 +383,8 @@ def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
             ensemble._epoch[0], groups, rng.next_calls(0)[0],               # the noise seed is a constant of the captured kernels
             ops.current_config().bf16_strided_train,                        # (what bf16_train_refusal admits: switched off, it must refuse again)
             ops.current_config().bf16_avgpool,                              # (likewise)
-            precision)
+            getattr(optimizer, "max_grad_norm", None), getattr(optimizer, "skip_nonfinite", False),   # constants of the captured norm and Adam launches
+            precision)                                                      # (the precision stays the LAST field: callers read key[-1])
 
 
 def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=None, graph=None, precision="fp32"):

@@ -3,6 +3,8 @@
 // rounded to fp32 ONCE -- and, per segment, whether any thread can take the 16-byte path.  Plain C++17, no HIP headers: bbb_adam_step
 // takes its launch shape and scalars from here, bbb_adam_step_plan reports them, and tests/host/adam_plan_check.cpp walks the plan
 // under the sanitizers.
+// plan_ex (bbb_adam_step_ex, bbb_adam_step_ex_plan) is plan() plus the weight-decay scalars and the checks of the two device scalars;
+// tests/host/grad_norm_plan_check.cpp walks it.
 #ifndef BBB_ADAM_PLAN_H
 #define BBB_ADAM_PLAN_H
 
@@ -59,6 +61,34 @@ inline int plan(const bbb_adam_segment_t* segs, int nseg, double lr, double beta
     q.beta1 = (float)beta1; q.beta2 = (float)beta2; q.omb1 = (float)(1.0 - beta1); q.omb2 = (float)(1.0 - beta2);
     q.eps = (float)eps;
     *p = q;
+    return 0;
+}
+
+// The extended step (bbb_adam_step_ex): the same plan -- checks, chunk walk, vector rule and scalars are plan()'s own -- plus weight
+// decay and the two optional device scalars of a clipped / guarded step.  mode 0: no decay (weight_decay == 0, either form: torch
+// skips it too); 1: L2, g <- g + wd32 p; 2: decoupled, p <- p decay before the update.  wd32 = fp32(weight_decay); decay =
+// fp32(1 - lr weight_decay) formed in double and rounded once (torch: param.mul_(1 - lr * weight_decay)); with lr_dev the kernel forms
+// decay itself from the device rate.  Checks in this order: everything plan() checks, then coef_dev / ok_dev 4-byte aligned
+// (BBB_EALIGN), then weight_decay >= 0 and not NaN (BBB_EINVAL).
+struct PlanEx {
+    Plan base;
+    int32_t mode;
+    float wd32, decay;
+};
+
+inline int plan_ex(const bbb_adam_segment_t* segs, int nseg, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   int decoupled, int64_t step, const void* step_dev, const void* lr_dev, const void* coef_dev, const void* ok_dev,
+                   PlanEx* p) {
+    *p = PlanEx{};
+    Plan base;
+    const int rc = plan(segs, nseg, lr, beta1, beta2, eps, step, step_dev, lr_dev, &base);
+    if (rc != 0) return rc;
+    if ((((uintptr_t)coef_dev | (uintptr_t)ok_dev) & 3u) != 0) return BBB_EALIGN;
+    if (!(weight_decay >= 0.0)) return BBB_EINVAL;
+    p->base = base;
+    p->mode = weight_decay == 0.0 ? 0 : (decoupled ? 2 : 1);
+    p->wd32 = (float)weight_decay;
+    p->decay = (float)(1.0 - lr * weight_decay);
     return 0;
 }
 
