@@ -301,6 +301,16 @@ int bbb_lrt_conv2d_fwd(const bbb_conv_desc_t* d, const float* x, const float* w_
                        uint64_t seed, uint32_t call0, uint32_t stream_id, int sample,
                        const uint32_t* call_dev, void* stream);
 
+/* What bbb_conv2d_fwd (lrt == 0) or bbb_lrt_conv2d_fwd (lrt != 0) launches for d (additive to ABI 13; host only, needs no device:
+ * tests, profiling): the entries' own plan (csrc/conv_gemm_plan.h).  *bm: output pixels per workgroup, 128 when
+ * ceil(batch ho wo / 128) * ceil(cout / 64) * draws >= 768, else 64; *linear: 1 for 1 x 1 taps on a 1 x 1 map without padding (x is
+ * read as the row-major [batch][cin] matrix it is); *bk: k per staged tile, 32 | 16 (LRT); *k_tiles = ceil(cin kh kw / bk);
+ * grid = (ceil(batch ho wo / bm), ceil(cout / 64), draws).  Returns the code the launch entry returns for d and valid, 4-byte
+ * aligned operands: 0, BBB_EINVAL or BBB_ESHAPE (LRT: a weight or bias draw stride is BBB_EINVAL); a refusal writes nothing.  Any
+ * out-pointer may be NULL. */
+int bbb_conv2d_fwd_plan(const bbb_conv_desc_t* d, int lrt, int32_t* bm, int32_t* linear, int32_t* bk, int32_t* k_tiles,
+                        int32_t grid[3]);
+
 /*
  * Batch-innermost ("CHWN") variants used by the batched Monte-Carlo ensemble path.
  *   x: [draws|1][cin][h][w][B]   y: [draws][cout][ho][wo][B]   (B = d->batch, B % 4 == 0, 16-byte aligned)

@@ -25,7 +25,7 @@
 
 #include "../../include/bbb_hip.h"
 #include "bbb_common.cuh"
-#include "conv_desc_check.h"
+#include "conv_gemm_plan.h"
 
 namespace {
 
@@ -35,6 +35,7 @@ typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int kThreads = 256;
 constexpr int BN = 64;    // output channels per block
 constexpr int LDW = BN + 1;
+static_assert(BN == conv_gemm_plan::kTileN, "the plan's grid counts this kernel's channel tiles");
 
 struct ConvArgs {
     const float* x;
@@ -57,6 +58,7 @@ struct ConvArgs {
 template <int BM, bool LRT, bool LINEAR>
 __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const ConvArgs p) {
     constexpr int BK = LRT ? 16 : 32;                    // k per LDS tile (LRT stages two weight tiles)
+    static_assert(BK == (LRT ? conv_gemm_plan::kBkLrt : conv_gemm_plan::kBkBbb), "the plan reports this tile's k");
     constexpr int LDX = BM + 1;
     constexpr int NT = (BM == 128) ? 2 : 1;              // 32x32 MFMA tiles per wave (along n)
     constexpr int XPT = BK * BM / kThreads;              // gathered x elements per thread per tile
@@ -294,49 +296,25 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const ConvArgs p) {
     }
 }
 
-int check_desc(const bbb_conv_desc_t* d, ConvArgs& a) {
-    if (d == nullptr) return BBB_EINVAL;
-    using namespace conv_desc_check;
-    if (!positive_geometry(d) || d->act < 0 || d->act > 2) return BBB_EINVAL;
-    if (unit_fields(d, kNothing) != 0 || d->w_row_pitch != 0 || d->pool != 0 || d->w_tap_major != 0) return BBB_EINVAL;   // batch-innermost entries only
-    int32_t ho = 0, wo = 0;
-    if (const int rc = out_map(d, &ho, &wo)) return rc;
-    const int64_t M = mul_cap(d->batch, ho, wo);
-    const int64_t K = mul_cap(d->cin, d->kh, d->kw);
-    if (M > 0x7fffffffLL || K > 0x7fffffffLL) return BBB_ESHAPE;
-    if (mul_cap(d->cin, d->h, d->w) > 0x7fffffffLL) return BBB_ESHAPE;     // per-image offsets are int32
-    if ((int64_t)d->h + d->pad_h + (int64_t)d->dil_h * d->kh >= 0x7000 || (int64_t)d->w + d->pad_w + (int64_t)d->dil_w * d->kw >= 0x7000) return BBB_ESHAPE;
+// The geometry half of the kernel's argument block, from the descriptor and its plan (csrc/conv_gemm_plan.h).
+void geometry_args(const bbb_conv_desc_t* d, const conv_gemm_plan::Plan& pl, ConvArgs& a) {
     a.B = d->batch; a.Cin = d->cin; a.H = d->h; a.W = d->w; a.Cout = d->cout; a.kh = d->kh; a.kw = d->kw;
     a.sh = d->stride_h; a.sw = d->stride_w; a.ph = d->pad_h; a.pw = d->pad_w; a.dh = d->dil_h; a.dw = d->dil_w;
-    a.Ho = ho; a.Wo = wo; a.M = (int32_t)M; a.K = (int32_t)K; a.HoWo = ho * wo; a.khkw = d->kh * d->kw;
+    a.Ho = pl.ho; a.Wo = pl.wo; a.M = pl.M; a.K = pl.K; a.HoWo = pl.ho * pl.wo; a.khkw = d->kh * d->kw;
     a.act = d->act;
     a.x_ds = d->x_draw_stride; a.w_ds = d->w_draw_stride; a.b_ds = d->b_draw_stride;
-    a.y_ds = (int64_t)d->batch * d->cout * ho * wo;
-    return 0;
-}
-
-bool is_linear(const ConvArgs& a) {
-    return a.H == 1 && a.W == 1 && a.kh == 1 && a.kw == 1 && a.ph == 0 && a.pw == 0;
-}
-
-// Smaller pixel tile when the 128-wide grid would not give every CU a few blocks.
-int pick_bm(const ConvArgs& a, int draws) {
-    const int64_t nb = (int64_t)((a.Cout + BN - 1) / BN) * draws;
-    const int64_t blocks128 = ((a.M + 127) / 128) * nb;
-    return blocks128 >= 3 * 256 ? 128 : 64;
+    a.y_ds = pl.y_ds;
 }
 
 template <bool LRT>
-int launch(const ConvArgs& a, int draws, hipStream_t st) {
-    const int bm = pick_bm(a, draws);
-    const dim3 grid((a.M + bm - 1) / bm, (a.Cout + BN - 1) / BN, draws);
-    const bool lin = is_linear(a);
-    if (bm == 128) {
-        if (lin) hipLaunchKernelGGL((conv_gemm_kernel<128, LRT, true>), grid, dim3(kThreads), 0, st, a);
-        else     hipLaunchKernelGGL((conv_gemm_kernel<128, LRT, false>), grid, dim3(kThreads), 0, st, a);
+int launch(const ConvArgs& a, const conv_gemm_plan::Plan& pl, hipStream_t st) {
+    const dim3 grid((uint32_t)pl.grid[0], (uint32_t)pl.grid[1], (uint32_t)pl.grid[2]);
+    if (pl.bm == 128) {
+        if (pl.linear) hipLaunchKernelGGL((conv_gemm_kernel<128, LRT, true>), grid, dim3(kThreads), 0, st, a);
+        else           hipLaunchKernelGGL((conv_gemm_kernel<128, LRT, false>), grid, dim3(kThreads), 0, st, a);
     } else {
-        if (lin) hipLaunchKernelGGL((conv_gemm_kernel<64, LRT, true>), grid, dim3(kThreads), 0, st, a);
-        else     hipLaunchKernelGGL((conv_gemm_kernel<64, LRT, false>), grid, dim3(kThreads), 0, st, a);
+        if (pl.linear) hipLaunchKernelGGL((conv_gemm_kernel<64, LRT, true>), grid, dim3(kThreads), 0, st, a);
+        else           hipLaunchKernelGGL((conv_gemm_kernel<64, LRT, false>), grid, dim3(kThreads), 0, st, a);
     }
     return (int)hipGetLastError();
 }
@@ -345,32 +323,49 @@ int launch(const ConvArgs& a, int draws, hipStream_t st) {
 
 extern "C" int bbb_conv2d_fwd(const bbb_conv_desc_t* d, const float* x, const float* w, const float* bias, float* y,
                               void* stream) {
-    ConvArgs a = {};
-    const int rc = check_desc(d, a);
+    conv_gemm_plan::Operands o;
+    o.null_operand = x == nullptr || w == nullptr || y == nullptr;
+    o.address_bits = (uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)y;
+    conv_gemm_plan::Plan pl;
+    const int rc = conv_gemm_plan::plan(d, false, o, &pl);
     if (rc != 0) return rc;
-    if (x == nullptr || w == nullptr || y == nullptr) return BBB_EINVAL;
-    if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)y) & 3u) != 0) return BBB_EALIGN;
+    ConvArgs a = {};
+    geometry_args(d, pl, a);
     a.x = x; a.w = w; a.bias = bias; a.y = y;
-    return launch<false>(a, d->draws, (hipStream_t)stream);
+    return launch<false>(a, pl, (hipStream_t)stream);
 }
 
 extern "C" int bbb_lrt_conv2d_fwd(const bbb_conv_desc_t* d, const float* x, const float* w_mu, const float* w_var,
                                   const float* b_mu, const float* b_var, float* y, float* act_mu_out, float* act_var_out,
                                   const float* eps_ext, uint64_t seed, uint32_t call0, uint32_t stream_id, int sample,
                                   const uint32_t* call_dev, void* stream) {
-    ConvArgs a = {};
-    const int rc = check_desc(d, a);
+    conv_gemm_plan::Operands o;
+    o.null_operand = x == nullptr || w_mu == nullptr || w_var == nullptr || y == nullptr;
+    o.half_a_bias = (b_mu == nullptr) != (b_var == nullptr);
+    o.address_bits = (uintptr_t)x | (uintptr_t)w_mu | (uintptr_t)w_var | (uintptr_t)b_mu | (uintptr_t)b_var | (uintptr_t)y |
+                     (uintptr_t)act_mu_out | (uintptr_t)act_var_out | (uintptr_t)eps_ext;
+    conv_gemm_plan::Plan pl;
+    const int rc = conv_gemm_plan::plan(d, true, o, &pl);
     if (rc != 0) return rc;
-    if (x == nullptr || w_mu == nullptr || w_var == nullptr || y == nullptr) return BBB_EINVAL;
-    if ((b_mu == nullptr) != (b_var == nullptr)) return BBB_EINVAL;
-    if (d->w_draw_stride != 0 || d->b_draw_stride != 0) return BBB_EINVAL;
-    if ((((uintptr_t)x | (uintptr_t)w_mu | (uintptr_t)w_var | (uintptr_t)b_mu | (uintptr_t)b_var | (uintptr_t)y |
-          (uintptr_t)act_mu_out | (uintptr_t)act_var_out | (uintptr_t)eps_ext) & 3u) != 0)
-        return BBB_EALIGN;
+    ConvArgs a = {};
+    geometry_args(d, pl, a);
     a.x = x; a.w = w_mu; a.w2 = w_var; a.bias = b_mu; a.bias2 = b_var; a.y = y;
     a.y_mu = act_mu_out; a.y_var = act_var_out; a.eps_ext = eps_ext;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.call0 = call0; a.stream_id = stream_id;
     a.sample = sample ? 1 : 0;
     a.call_dev = call_dev;
-    return launch<true>(a, d->draws, (hipStream_t)stream);
+    return launch<true>(a, pl, (hipStream_t)stream);
+}
+
+extern "C" int bbb_conv2d_fwd_plan(const bbb_conv_desc_t* d, int lrt, int32_t* bm, int32_t* linear, int32_t* bk, int32_t* k_tiles,
+                                   int32_t grid[3]) {
+    conv_gemm_plan::Plan pl;
+    const int rc = conv_gemm_plan::plan(d, lrt != 0, conv_gemm_plan::Operands(), &pl);
+    if (rc != 0) return rc;
+    if (bm) *bm = pl.bm;
+    if (linear) *linear = pl.linear;
+    if (bk) *bk = pl.bk;
+    if (k_tiles) *k_tiles = pl.k_tiles;
+    if (grid) for (int i = 0; i < 3; ++i) grid[i] = pl.grid[i];
+    return 0;
 }

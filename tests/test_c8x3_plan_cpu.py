@@ -292,6 +292,8 @@ def test_an_over_reaching_kernel_is_eshape_in_every_entry(lib):
         "bbb_im2col_pbj": lambda: h.bbb_im2col_pbj(P, P, dp, None),
         "bbb_input_grad_col2im": lambda: h.bbb_input_grad_col2im(P, 64, 0, None, P, dp, None),
         # the plan queries
+        "bbb_conv2d_fwd_plan": lambda: h.bbb_conv2d_fwd_plan(dp, 0, None, None, None, None, None),
+        "bbb_conv2d_fwd_plan (lrt)": lambda: h.bbb_conv2d_fwd_plan(dp, 1, None, None, None, None, None),
         "bbb_conv2d_chwn_plan": lambda: h.bbb_conv2d_chwn_plan(dp, 0, 1, 0, None, None, None, None, None),
         "bbb_conv2d_chwn_plan (lrt)": lambda: h.bbb_conv2d_chwn_plan(dp, 1, 1, 0, None, None, None, None, None),
         "bbb_conv2d_chwn_bf16_plan": lambda: h.bbb_conv2d_chwn_bf16_plan(dp, 0, i32(), i32(), i32(), i32()),

@@ -965,3 +965,22 @@ def test_bf16_train_fuzz_branch_coverage():
     assert ops.wgrad_batch_chunks_bf16(1, 128, 128, 5, 5, 4096) == 16 and ops.wgrad_batch_chunks_bf16(10, 384, 256, 3, 3, 512) == 1
     assert ops.bf16_tap_major((16, 8, 3, 3)) and not ops.bf16_tap_major((16, 8, 1, 1)) and not ops.bf16_tap_major((16, 12, 3, 3))
     assert ops.bf16_row_pitch(84) == 88 and ops.bf16_row_pitch(96) == 96 and ops.bf16_row_pitch(1) == 8
+
+
+def test_conv_gemm_plan_walk_under_the_sanitizers(tmp_path):
+    """tests/host/conv_gemm_plan_check.cpp (csrc/conv_gemm_plan.h alone: no device code, not loaded into Python) under
+    -fsanitize=address,undefined: layers next to the pixel tile's 768-workgroup threshold with every refusal mixed in, descriptors
+    at the integer limits, the order of the checks; all eight instantiations of conv_gemm_kernel are planned."""
+    import shutil
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "conv_gemm_plan_check")
+    subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "host", "conv_gemm_plan_check.cpp"), "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
+    got = dict(zip(out[:10:2], out[1:10:2]))
+    forms = [int(v) for v in out[11:19]]
+    assert out[10] == "forms" and out[19] == "checksum" and len(out[20]) == 16
+    assert int(got["cases"]) >= 200000 and min(int(got[k]) for k in ("ok", "einval", "ealign", "eshape")) > 1000
+    assert len(forms) == 8 and min(forms) > 1000, forms
