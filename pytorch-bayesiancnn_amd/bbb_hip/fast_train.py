@@ -23,9 +23,11 @@ E forwards, KL, log_softmax / logmeanexp, ELBO, backward -- on the training path
 Four nodes -- _MCForward (fp32), _MCForwardBF16 (bf16 storage), _MCForwardLRT (local reparameterisation), _MCForwardLRTBF16 (its
 activation side in bf16 storage: input gradients with frozen parameters, no weight side) -- over one layer plan (train_plan: _parse
 states the layer / activation / pool pairing, geometry and maps once per model and input shape; admission is that a plan exists), one
-forward walk over it (_walk: the tape, every launch's map held against the plan) and one backward schedule (_Schedule: which stream a
-layer's weight side runs on, the early fork, the join); _carry / _run_backward take the launch configuration and scratch scope to the
-backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weight side, its input gradient, its flips up front.
+forward walk over it (_walk: the tape, every launch's map held against the plan), one backward walk down that tape (_walk_back: the
+incoming gradient shaped to each record, the node's passes in their order, the first layer's dx, the join) and one backward schedule
+(_Schedule: which stream a layer's weight side runs on, the early fork, the join); _carry / _run_backward take the launch
+configuration and scratch scope to the backward.  A node keeps its arithmetic: how it runs a layer, its g_pre, its weight side, its
+input gradient, its flips up front -- the backward walk gets them as callables and knows no node.
 """
 import collections
 import os
@@ -194,7 +196,8 @@ def _check_versions(versions):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# what the three nodes share: the parameter lists, the forward walk, the context they carry to the backward, the backward schedule
+# what the four nodes share: the parameter lists, the forward walk, the context they carry to the backward, the backward schedule,
+# the backward walk, how the outputs are packed
 # ---------------------------------------------------------------------------------------------------------------------------
 def _param_lists(layers, leaf):
     """(mus, rhos, stream ids) of the layers in forward order -- per layer (W, bias) -- each parameter passed through `leaf`
@@ -249,7 +252,7 @@ def _walk(plan, h, run_layer, pool, avgpool=None):
 
 
 def _pool_pass(rec, max_pass, avg_pass, *tensors, **kw):
-    """The pooling / activation backward of a record, one place for the three nodes: the node's wrapper of the record's pool on
+    """The pooling / activation backward of a record, one place for the four nodes: the node's wrapper of the record's pool on
     `tensors` -- max_pass(*tensors, k, s, act, **kw) behind a max pool or, as k = 0, behind the activation alone;
     avg_pass(*tensors, kernel, stride, padding, count_include_pad, act, **kw) behind an average pool."""
     spec = rec["pool"]
@@ -278,14 +281,22 @@ class _Schedule:
     """Where the launches of one backward go.  A layer's weight / bias gradients and its input gradient are independent: the former
     run on a side stream beside the latter (both are launches that leave the chip partly idle on their own), the streams taken
     round robin, last layer first; the first layer's weight side runs on the main stream (nothing is left to run beside it); all
-    are joined before the parameter pass's backward.  Tensors a side stream reads stay referenced in `keep` until the join (the
-    allocator must not hand them out again before).  Eager launches only: inside a captured step the forks cost more than the
-    overlap gains -- 4.8 against 3.05 ms per step.
+    are joined before the parameter pass's backward.  Eager launches only: inside a captured step the forks cost more than the
+    overlap gains -- 4.8 against 3.05 ms per step.  A side-stream count below 1 (n_side_streams, BBB_TRAIN_SIDE_STREAMS) means no side
+    streams: the schedule of overlap_wgrad off.
+    The invariant the code rests on, and why no tensor needs a record_stream (which would change what the allocator does):
+      * every launch on a side stream is preceded by that stream's wait_stream(main), so it sees what main has written;
+      * every tensor a side stream reads is referenced in `keep` until join() (the allocator, which knows main as their stream, must
+        not hand them out again while a side stream still reads them);
+      * every tensor a side stream allocates is consumed on main only after main has waited for that stream -- the weight gradients
+        gws after join(), the early im2col xk_first after the first layer's wait on fork_early's stream, and held in `keep` until
+        join() -- and a side stream that is handed the block again waits for main (the first point) before it writes there.
     g: the incoming gradient (None: nothing to schedule); weight_side: the node runs weight sides at all."""
 
     def __init__(self, g, weight_side):
         self.run_weights = weight_side
-        forks = g is not None and weight_side and overlap_wgrad[0] and not torch.cuda.is_current_stream_capturing()
+        forks = (g is not None and weight_side and overlap_wgrad[0] and n_side_streams[0] >= 1
+                 and not torch.cuda.is_current_stream_capturing())
         self.side = _side_stream(g.device) if forks else None
         self.main = torch.cuda.current_stream(g.device) if forks else None
         self.keep = []
@@ -321,6 +332,63 @@ class _Schedule:
         self.keep = []
 
 
+def _walk_back(tape, g, sched, g_pre_of, weight_side, input_grad, first_dx):
+    """The backward walk down a tape (_walk's), one copy for the four nodes, mirror of _walk: -> dx, or None.
+    g: the gradient of the last record's output (None: nothing to walk); sched: the node's _Schedule.  What passes from layer to layer
+    is a tuple of tensors, each of which the walk shapes to the record's out_shape: one tensor, or what an LRT layer hands down
+    (_lrt_incoming).  The node's arithmetic, per record from the last one:
+      g_pre_of(rec, *gs) -> (g_pre, reads)    its pooling / activation pass: g_pre in whatever form the other three take it, and the
+                                              tensors of it the weight side reads (a side stream keeps them alive);
+      weight_side(li, rec, g_pre)             the layer's parameter gradients, run where and if the schedule says (a node that
+                                              runs none: its _Schedule has weight_side False, and this is None);
+      input_grad(li, rec, g_pre) -> gs        below the first layer: what the layer underneath receives;
+      first_dx(rec, g_pre) -> dx              the first layer, when x takes a gradient (None when it does not).
+    The streams are joined at the end."""
+    dx = None
+    gs = () if g is None else (g,)
+    for li in range(len(tape) - 1, -1, -1):
+        if not gs:
+            break
+        rec = tape[li]
+        g_pre, reads = g_pre_of(rec, *(t.reshape(rec["out_shape"]) for t in gs))
+        sched.weight_side(rec["first"], lambda: weight_side(li, rec, g_pre), reads=reads)
+        if not rec["first"]:
+            gs = input_grad(li, rec, g_pre)
+        else:
+            if first_dx is not None:
+                dx = first_dx(rec, g_pre)
+            gs = ()
+    sched.join()
+    return dx
+
+
+def _pack(dx, grads):
+    """What a node's backward returns: a gradient per forward argument -- cfg (none), x, the parameters."""
+    return (None, dx, *grads)
+
+
+def _pack_bbb(ctx, dx, gws, g_kl):
+    """_pack for the two BBB nodes: the gradients of the sampled weights gws (per layer W, bias) + d loss / d KL through the parameter
+    pass's backward -> per layer W_mu, W_rho, bias_mu, bias_rho; frozen parameters: no pass, no gradients."""
+    mus, rhos, ids, pm, ps, _ = ctx.meta
+    if not any(ctx.needs_input_grad[2:]):
+        return _pack(dx, [None] * (2 * len(mus)))
+    gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, ctx.cfg["seed"], ctx.cfg["call0"], ctx.cfg["draws"])
+    grads = []
+    for a, b in zip(gmu, grho):
+        grads += [a, b]
+    return _pack(dx, grads)
+
+
+def _lrt_incoming(g, x_out=None, g2=None):
+    """What an LRT layer receives from _walk_back -> (g, combine=) of its pooling / activation pass: the logits' gradient alone, or
+    the triple (g1, x_out, g2) the layer above hands down under fold_lrt_combine -- its two input gradients and its input, this
+    layer's output -- which that pass combines (g1 + 2 x_out g2) instead of a launch of its own.  (All three arrive shaped to this
+    record's out_shape: x_out is the output behind the pool as the layer above read it, draws included -- only a first layer's input
+    has a single draw, and a first layer hands nothing down.)"""
+    return g, (None if g2 is None else (x_out, g2))
+
+
 class _MCForward(torch.autograd.Function):
     """(x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (logits [E, C, B] batch-innermost, kl of one forward)."""
 
@@ -351,14 +419,11 @@ class _MCForward(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, g_logits, g_kl):
-        cfg, tape = ctx.cfg, ctx.tape
-        mus, rhos, ids, pm, ps, x_shape = ctx.meta
-        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
+        tape, x_shape = ctx.tape, ctx.meta[5]
         # need_w False (frozen parameters: saliency maps, adversarial steps): no weight side at all -- no bias sums, weight gradients,
         # im2col, parameter pass or side-stream forks; need_x: the first layer's input gradient (first_layer_input_grad) at the end
         need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        gws = [None] * len(mus)
-        dx = None
+        gws = [None] * (2 * len(tape))
         g = g_logits.contiguous() if g_logits is not None else None
         sched = _Schedule(g, weight_side=need_w)
         # the first layer's im2col depends on the batch alone: on a side stream NOW, beside the small last layers' launches, instead of
@@ -376,44 +441,35 @@ class _MCForward(torch.autograd.Function):
         if flips_up_front[0] and sched.side is None and g is not None and len(tape) > 1:
             outs = ops.flip_transpose_w_multi([tape[li]["w"] for li in range(1, len(tape))])
             w_flipped = {li: o for li, o in zip(range(1, len(tape)), outs)}
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            y, w5, x_in, act = rec["y"], rec["w"], rec["x"], rec["act"]
-            stride, padding, dilation = rec["geom"]
-            if g is None:
-                break
-            g = g.reshape(rec["out_shape"])
-            pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
-            if rec["pool"] is None and act is None:
+
+        def g_pre_of(rec, g):
+            pad = rec["first"] and rec["x"].shape[1] % 4 != 0            # feeds conv2d_chwn_weight_grad_shared_input
+            if rec["pool"] is None and rec["act"] is None:
                 g_pre = g
             else:
-                g_pre = _pool_pass(rec, ops.pool_act_backward_chwn, ops.avgpool_act_backward_chwn, g, y, pad_planes=pad)
+                g_pre = _pool_pass(rec, ops.pool_act_backward_chwn, ops.avgpool_act_backward_chwn, g, rec["y"], pad_planes=pad)
+            return g_pre, [g_pre]
 
-            def weight_side():
-                gws[2 * li + 1] = ops.plane_sums(g_pre)                   # bias gradient [E, Cout]
-                if x_in.shape[1] % 4 == 0 or not rec["first"]:           # (6-channel inputs etc.: padded to 8 inside)
-                    gw = ops.conv2d_chwn_weight_grad(g_pre, x_in, tuple(w5.shape), stride, padding, dilation)
-                else:
-                    # 3-channel first layer: its input is shared by all draws, so the draws stack into the GEMM's row dimension
-                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, tuple(w5.shape), stride, padding, dilation, xk=xk_first)
-                gws[2 * li] = gw.reshape(ws_shape(rec))
-
-            sched.weight_side(rec["first"], weight_side, reads=[g_pre])
-            if not rec["first"]:
-                g = ops.conv2d_chwn_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), padding, dilation, w_flipped=w_flipped.get(li),
-                                               stride=stride)
+        def weight_side(li, rec, g_pre):
+            x_in, wsh = rec["x"], tuple(rec["w"].shape)
+            gws[2 * li + 1] = ops.plane_sums(g_pre)                       # bias gradient [E, Cout]
+            if x_in.shape[1] % 4 == 0 or not rec["first"]:               # (6-channel inputs etc.: padded to 8 inside)
+                gw = ops.conv2d_chwn_weight_grad(g_pre, x_in, wsh, *rec["geom"])
             else:
-                if need_x:
-                    dx = ops.first_layer_input_grad(g_pre, w5, (x_in.shape[2], x_in.shape[3]), stride, padding, dilation).view(x_shape)
-                g = None
-        sched.join()
-        out = [None, dx]
-        if not need_w:
-            return tuple(out + [None] * (2 * len(mus)))
-        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        for a, b in zip(gmu, grho):
-            out += [a, b]
-        return tuple(out)
+                # 3-channel first layer: its input is shared by all draws, so the draws stack into the GEMM's row dimension
+                gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, *rec["geom"], xk=xk_first)
+            gws[2 * li] = gw.reshape(ws_shape(rec))
+
+        def input_grad(li, rec, g_pre):
+            stride, padding, dilation = rec["geom"]
+            return (ops.conv2d_chwn_input_grad(g_pre, rec["w"], tuple(rec["x"].shape[2:4]), padding, dilation, w_flipped=w_flipped.get(li),
+                                               stride=stride),)
+
+        def first_dx(rec, g_pre):
+            return ops.first_layer_input_grad(g_pre, rec["w"], tuple(rec["x"].shape[2:4]), *rec["geom"]).view(x_shape)
+
+        dx = _walk_back(tape, g, sched, g_pre_of, weight_side, input_grad, first_dx if need_x else None)
+        return _pack_bbb(ctx, dx, gws, g_kl)
 
 
 class _MCForwardBF16(torch.autograd.Function):
@@ -421,8 +477,7 @@ class _MCForwardBF16(torch.autograd.Function):
     (x, W_mu0, W_rho0, b_mu0, b_rho0, W_mu1, ...) -> (fp32 logits [E, C, B] batch-innermost, fp32 kl of one forward).
     Forward = the bf16 inference kernels with the pooling left unfused (the tape keeps every layer's pre-pool output): sampled
     weights, the input and every hidden activated / pooled output stored as bf16, fp32 accumulation, fp32 logits and KL.  Tape:
-    each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: the walk of _MCForward._backward on the same
-    _Schedule with
+    each layer's bf16 input, bf16 activated output and bf16 weight rows.  Backward: _walk_back on a _Schedule as _MCForward's, with
       * ops.pool_act_backward_chwn_bf16   g_pre = act'(y) * route(g) in fp32, rounded once to bf16 (the logits' fp32 gradient too),
       * ops.avgpool_act_backward_chwn_bf16   the same behind an average pool (LaunchConfig.bf16_avgpool): every window's gradient over
         its divisor to each of its taps,
@@ -469,69 +524,55 @@ class _MCForwardBF16(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, g_logits, g_kl):
-        cfg, tape = ctx.cfg, ctx.tape
-        mus, rhos, ids, pm, ps, x_shape = ctx.meta
-        E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
-        # (as in _MCForward) need_w False -- frozen parameters, reached under LaunchConfig.bf16_input_grad alone: no weight side at all;
-        # need_x: the first layer's input gradient (first_layer_input_grad_bf16) at the end.  Without the switch this mode refuses
-        # x.requires_grad (bf16_train_refusal): every backward is then one for the parameters alone, enqueued as it always was
+        tape, E, x_shape = ctx.tape, ctx.cfg["draws"], ctx.meta[5]
+        # need_w False -- frozen parameters, reached under LaunchConfig.bf16_input_grad alone: no weight side at all; need_x: the first
+        # layer's input gradient (first_layer_input_grad_bf16) at the end.  Without the switch this mode refuses x.requires_grad
+        # (bf16_train_refusal): every backward is then one for the parameters alone, enqueued as it always was
         need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        gws = [None] * len(mus)
-        dx = None
+        gws = [None] * (2 * len(tape))
         g = g_logits.contiguous() if g_logits is not None else None
         sched = _Schedule(g, weight_side=need_w)
         r0 = tape[0]
         shared0 = need_w and r0["x"].shape[1] % 4 != 0                    # (no weight side: the first layer's g_pre stays bf16)
-        xk_first = None                                                   # (as in _MCForward: the first layer's im2col forked up front)
+        xk_first = None                                                   # the first layer's im2col, forked up front beside the last layers
         if sched.side is not None and shared0:
             xk_first = sched.fork_early(lambda: ops.im2col_pbj(ctx.x_nchw, (E,) + r0["wshape"], *r0["geom"]))
-        # every layer's flipped input-gradient weight rows up front (captured / launch-bound steps, as in _MCForward; one launch per
-        # layer: the rows have no multi-layer form)
+        # every layer's flipped input-gradient weight rows up front, for captured / launch-bound steps (no side streams); one launch
+        # per layer: the rows have no multi-layer form
         w_flipped = {}
         if flips_up_front[0] and sched.side is None and g is not None:
             w_flipped = {li: ops.flip_transpose_w_bf16(tape[li]["w"], tape[li]["wshape"]) for li in range(1, len(tape))}
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            if g is None:
-                break
-            y, w, x_in, act, wshape = rec["y"], rec["w"], rec["x"], rec["act"], rec["wshape"]
-            stride, padding, dilation = rec["geom"]
-            g = g.reshape(rec["out_shape"])
+
+        def g_pre_of(rec, g):
+            y = rec["y"]
             shared = rec["first"] and shared0                             # feeds conv2d_chwn_weight_grad_shared_input (fp32)
-            if rec["pool"] is None and act is None and g.dtype == torch.bfloat16 and not shared:
+            if rec["pool"] is None and rec["act"] is None and g.dtype == torch.bfloat16 and not shared:
                 g_pre = g                                                 # already the bf16 output gradient
             else:                                                         # (the logits layer's fp32 y: no pool, no activation -- a rounding)
                 g_pre = _pool_pass(rec, ops.pool_act_backward_chwn_bf16, ops.avgpool_act_backward_chwn_bf16,
                                    g, y if y.dtype == torch.bfloat16 else None, out_f32=shared, pad_planes=shared)
+            return g_pre, [g_pre]
 
-            def weight_side():
-                wsh = (E,) + wshape
-                if shared:
-                    gws[2 * li + 1] = ops.plane_sums(g_pre)
-                    gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, stride, padding, dilation, xk=xk_first)
-                else:
-                    gws[2 * li + 1] = ops.plane_sums_bf16(g_pre)
-                    gw = ops.conv2d_chwn_weight_grad_bf16(g_pre, x_in, wsh, stride, padding, dilation)
-                gws[2 * li] = gw.reshape(ws_shape(rec))
-
-            sched.weight_side(rec["first"], weight_side, reads=[g_pre])
-            if not rec["first"]:
-                g = ops.conv2d_chwn_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), padding, dilation,
-                                                    w_flipped=w_flipped.get(li), stride=stride)
+        def weight_side(li, rec, g_pre):
+            wsh = (E,) + rec["wshape"]
+            if rec["first"] and shared0:
+                gws[2 * li + 1] = ops.plane_sums(g_pre)
+                gw = ops.conv2d_chwn_weight_grad_shared_input(g_pre, ctx.x_nchw, wsh, *rec["geom"], xk=xk_first)
             else:
-                if need_x:
-                    # on the sampled rows and g_pre where they are: bf16, or the fp32 form the weight side above reads
-                    dx = ops.first_layer_input_grad_bf16(g_pre, w, wshape, (x_in.shape[2], x_in.shape[3]), stride, padding,
-                                                         dilation).view(x_shape)
-                g = None
-        sched.join()
-        if not need_w:
-            return tuple([None, dx] + [None] * (2 * len(mus)))
-        gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, seed, call0, E)
-        out = [None, dx]
-        for a, b in zip(gmu, grho):
-            out += [a, b]
-        return tuple(out)
+                gws[2 * li + 1] = ops.plane_sums_bf16(g_pre)
+                gw = ops.conv2d_chwn_weight_grad_bf16(g_pre, rec["x"], wsh, *rec["geom"])
+            gws[2 * li] = gw.reshape(ws_shape(rec))
+
+        def input_grad(li, rec, g_pre):
+            stride, padding, dilation = rec["geom"]
+            return (ops.conv2d_chwn_input_grad_bf16(g_pre, rec["w"], rec["wshape"], tuple(rec["x"].shape[2:4]), padding, dilation,
+                                                    w_flipped=w_flipped.get(li), stride=stride),)
+
+        def first_dx(rec, g_pre):                          # on the sampled rows and g_pre where they are: bf16, or the fp32 form the weight side reads
+            return ops.first_layer_input_grad_bf16(g_pre, rec["w"], rec["wshape"], tuple(rec["x"].shape[2:4]), *rec["geom"]).view(x_shape)
+
+        dx = _walk_back(tape, g, sched, g_pre_of, weight_side, input_grad, first_dx if need_x else None)
+        return _pack_bbb(ctx, dx, gws, g_kl)
 
 
 def _inverse_act(y, act):
@@ -584,37 +625,28 @@ class _MCForwardLRT(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, g_logits):
         tape = ctx.tape
-        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])         # (as in _MCForward)
+        need_x, need_w = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])         # (frozen parameters: no weight side at all)
         grads = [None] * (4 * len(tape))
-        dx = None
         g = g_logits.contiguous()
         sched = _Schedule(g, weight_side=need_w)
-        # (as in _MCForward: the flipped input-gradient weights of every layer -- mean and variance sets -- in one launch up front;
-        # here whether or not there are side streams, there without them only)
+        # the flipped input-gradient weights of every layer -- mean and variance sets -- in one launch up front, whether or not there are
+        # side streams (the BBB nodes: without them only)
         w_flipped = {}
         if flips_up_front[0] and len(tape) > 1:
             pairs = [(tape[li]["w_mu"].unsqueeze(0), tape[li]["w_var"].unsqueeze(0)) for li in range(1, len(tape))]
             outs = ops.flip_transpose_w_multi(pairs)                     # [2, Cin, Cout, kh, kw] each: the mean set, then the variance set
             w_flipped = {li: o for li, o in zip(range(1, len(tape)), outs)}
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            y, am, av, x_in, act = rec["y"], rec["am"], rec["av"], rec["x"], rec["act"]
-            w_mu, w_var = rec["w_mu"], rec["w_var"]
-            stride, padding, dilation = rec["geom"]
-            # the incoming gradient: a tensor (the logits' gradient), or the layer above's two input gradients + this layer's output,
-            # combined (g1 + 2 x g2) inside the pass below instead of by a launch of its own
-            comb = None
-            if isinstance(g, tuple):
-                g, comb = g[0].reshape(rec["out_shape"]), (g[1].reshape((-1,) + tuple(rec["out_shape"][1:])), g[2].reshape(rec["out_shape"]))
-            else:
-                g = g.reshape(rec["out_shape"])
+
+        def g_pre_of(rec, *incoming):                      # -> ((g_mu, g_var, g_pair | None), what the weight side reads)
+            g, comb = _lrt_incoming(*incoming)
+            am = rec["am"]
             # one pass: pooling / activation backward AND the split into d/d act_mu, d/d act_var (was ~10 ATen kernels per layer)
-            pad = rec["first"] and x_in.shape[1] % 4 != 0                # feeds conv2d_chwn_weight_grad_shared_input
+            pad = rec["first"] and rec["x"].shape[1] % 4 != 0            # feeds conv2d_chwn_weight_grad_shared_input
             # below the first layer the pair (d/d act_mu, d/d act_var) stays ONE buffer: its two weight gradients (with x, x^2) and,
             # for a single draw, its two input gradients (with W_mu, W_var) run as the draws of one launch each
             g_pair = None
             def pool_pass(**kw):
-                return _pool_pass(rec, ops.lrt_pool_act_backward_chwn, ops.lrt_avgpool_act_backward_chwn, g, y, am, av, **kw)
+                return _pool_pass(rec, ops.lrt_pool_act_backward_chwn, ops.lrt_avgpool_act_backward_chwn, g, rec["y"], am, rec["av"], **kw)
             if pair_lrt_backward[0] and not rec["first"]:
                 g_pair = pool_pass(stacked=True, combine=comb)                                 # [2, E, Cout, Ho, Wo, B]
                 g_mu, g_var = g_pair[0], g_pair[1]
@@ -624,54 +656,63 @@ class _MCForwardLRT(torch.autograd.Function):
                 # (the two sums one set apart in one buffer: the input gradient reads them as the two draws of one launch)
                 both = torch.empty((2, 1) + tuple(g_mu.shape[1:]), dtype=torch.float32, device=g_mu.device)
                 g_mu, g_var = ops.sum_over_draws(g_mu, keepdim=True, out=both[0]), ops.sum_over_draws(g_var, keepdim=True, out=both[1])
+            return (g_mu, g_var, g_pair), [g_mu, g_var]
 
-            def weight_side():
-                wshape = (1,) + tuple(w_mu.shape)
-                Ed = g_mu.shape[0]
-                if g_pair is not None and Ed == 1:
-                    gb = ops.plane_sums(g_pair.reshape((2,) + tuple(g_mu.shape[1:])))               # [2, Cout]
-                    grads[4 * li + 2], grads[4 * li + 3] = gb[0], gb[1]
-                else:
-                    grads[4 * li + 2] = ops.plane_sums(g_mu, over_draws=True)
-                    grads[4 * li + 3] = ops.plane_sums(g_var, over_draws=True)
-                if g_pair is not None and x_in.shape[0] == Ed:
-                    gw = ops.conv2d_chwn_weight_grad(g_pair.reshape((2 * Ed,) + tuple(g_mu.shape[1:])), x_in,
-                                                     (2 * Ed,) + tuple(w_mu.shape), stride, padding, dilation, x_squares=True)
-                    gw_mu, gw_var = ops.sum_over_draws(gw[:Ed]), ops.sum_over_draws(gw[Ed:])
-                elif x_in.shape[1] % 4 == 0 or not rec["first"]:
-                    gw_mu = ops.conv2d_chwn_weight_grad(g_mu, x_in, wshape, stride, padding, dilation)
-                    gw_var = ops.conv2d_chwn_weight_grad(g_var, ops.square(x_in), wshape, stride, padding, dilation)
-                    gw_mu, gw_var = ops.sum_over_draws(gw_mu), ops.sum_over_draws(gw_var)
-                else:
-                    # (built inside the weight side, on the main stream: this node forks no early im2col, _MCForward does)
-                    xk = ops.im2col_pbj(ctx.x_nchw, wshape, stride, padding, dilation)      # (its square = the im2col of x^2)
-                    gw_mu = ops.conv2d_chwn_weight_grad_shared_input(g_mu, None, wshape, stride, padding, dilation, xk=xk)[0]
-                    gw_var = ops.conv2d_chwn_weight_grad_shared_input(g_var, None, wshape, stride, padding, dilation, xk=ops.square(xk))[0]
-                m = rec["layer"]
-                grads[4 * li] = gw_mu.reshape(m.W_mu.shape)
-                grads[4 * li + 1] = gw_var.reshape(m.W_mu.shape)
+        def weight_side(li, rec, g_pre):
+            g_mu, g_var, g_pair = g_pre
+            x_in, w_mu = rec["x"], rec["w_mu"]
+            stride, padding, dilation = rec["geom"]
+            wshape = (1,) + tuple(w_mu.shape)
+            Ed = g_mu.shape[0]
+            if g_pair is not None and Ed == 1:
+                gb = ops.plane_sums(g_pair.reshape((2,) + tuple(g_mu.shape[1:])))               # [2, Cout]
+                grads[4 * li + 2], grads[4 * li + 3] = gb[0], gb[1]
+            else:
+                grads[4 * li + 2] = ops.plane_sums(g_mu, over_draws=True)
+                grads[4 * li + 3] = ops.plane_sums(g_var, over_draws=True)
+            if g_pair is not None and x_in.shape[0] == Ed:
+                gw = ops.conv2d_chwn_weight_grad(g_pair.reshape((2 * Ed,) + tuple(g_mu.shape[1:])), x_in,
+                                                 (2 * Ed,) + tuple(w_mu.shape), stride, padding, dilation, x_squares=True)
+                gw_mu, gw_var = ops.sum_over_draws(gw[:Ed]), ops.sum_over_draws(gw[Ed:])
+            elif x_in.shape[1] % 4 == 0 or not rec["first"]:
+                gw_mu = ops.conv2d_chwn_weight_grad(g_mu, x_in, wshape, stride, padding, dilation)
+                gw_var = ops.conv2d_chwn_weight_grad(g_var, ops.square(x_in), wshape, stride, padding, dilation)
+                gw_mu, gw_var = ops.sum_over_draws(gw_mu), ops.sum_over_draws(gw_var)
+            else:
+                # (built inside the weight side, on the main stream: this node forks no early im2col, _MCForward does)
+                xk = ops.im2col_pbj(ctx.x_nchw, wshape, stride, padding, dilation)      # (its square = the im2col of x^2)
+                gw_mu = ops.conv2d_chwn_weight_grad_shared_input(g_mu, None, wshape, stride, padding, dilation, xk=xk)[0]
+                gw_var = ops.conv2d_chwn_weight_grad_shared_input(g_var, None, wshape, stride, padding, dilation, xk=ops.square(xk))[0]
+            m = rec["layer"]
+            grads[4 * li] = gw_mu.reshape(m.W_mu.shape)
+            grads[4 * li + 1] = gw_var.reshape(m.W_mu.shape)
 
-            sched.weight_side(rec["first"], weight_side, reads=[g_mu, g_var])
-            if rec["first"] and need_x:
-                dx = ops.first_layer_input_grad((g_mu, g_var), (w_mu, w_var), (x_in.shape[2], x_in.shape[3]), stride, padding, dilation,
-                                                x_lrt=ctx.x_nchw).view(ctx.x_nchw.shape)
-            if not rec["first"]:
-                hw = (x_in.shape[2], x_in.shape[3])
-                w_t = w_flipped.get(li)
-                if g_pair is not None and g_mu.shape[0] == 1:
-                    if w_t is None:
-                        w_t = ops.flip_transpose_w_pair(w_mu.unsqueeze(0), w_var.unsqueeze(0))
-                    gx = ops.conv2d_chwn_input_grad(g_pair.reshape((2,) + tuple(g_mu.shape[1:])), w_mu.unsqueeze(0), hw, padding, dilation,
-                                                    w_flipped=w_t, stride=stride)
-                    g1, g2 = gx[0:1], gx[1:2]
-                else:
-                    t_mu, t_var = (w_t[0:1], w_t[1:2]) if w_t is not None else (None, None)
-                    g1 = ops.conv2d_chwn_input_grad(g_mu, w_mu.unsqueeze(0), hw, padding, dilation, w_flipped=t_mu, stride=stride)
-                    g2 = ops.conv2d_chwn_input_grad(g_var, w_var.unsqueeze(0), hw, padding, dilation, w_flipped=t_var, stride=stride)
-                # (g1 + 2 x g2 is formed by the layer below's pooling / activation pass)
-                g = (g1, x_in, g2) if fold_lrt_combine[0] else ops.lrt_input_grad_combine(g1, x_in, g2)
-        sched.join()
-        return (None, dx, *grads)
+        def input_grad(li, rec, g_pre):
+            g_mu, g_var, g_pair = g_pre
+            x_in, w_mu, w_var = rec["x"], rec["w_mu"], rec["w_var"]
+            stride, padding, dilation = rec["geom"]
+            hw = (x_in.shape[2], x_in.shape[3])
+            w_t = w_flipped.get(li)
+            if g_pair is not None and g_mu.shape[0] == 1:
+                if w_t is None:
+                    w_t = ops.flip_transpose_w_pair(w_mu.unsqueeze(0), w_var.unsqueeze(0))
+                gx = ops.conv2d_chwn_input_grad(g_pair.reshape((2,) + tuple(g_mu.shape[1:])), w_mu.unsqueeze(0), hw, padding, dilation,
+                                                w_flipped=w_t, stride=stride)
+                g1, g2 = gx[0:1], gx[1:2]
+            else:
+                t_mu, t_var = (w_t[0:1], w_t[1:2]) if w_t is not None else (None, None)
+                g1 = ops.conv2d_chwn_input_grad(g_mu, w_mu.unsqueeze(0), hw, padding, dilation, w_flipped=t_mu, stride=stride)
+                g2 = ops.conv2d_chwn_input_grad(g_var, w_var.unsqueeze(0), hw, padding, dilation, w_flipped=t_var, stride=stride)
+            # (g1 + 2 x g2 is formed by the layer below's pooling / activation pass: _lrt_incoming)
+            return (g1, x_in, g2) if fold_lrt_combine[0] else (ops.lrt_input_grad_combine(g1, x_in, g2),)
+
+        def first_dx(rec, g_pre):
+            x_in = rec["x"]
+            return ops.first_layer_input_grad(g_pre[:2], (rec["w_mu"], rec["w_var"]), (x_in.shape[2], x_in.shape[3]), *rec["geom"],
+                                              x_lrt=ctx.x_nchw).view(ctx.x_nchw.shape)
+
+        dx = _walk_back(tape, g, sched, g_pre_of, weight_side, input_grad, first_dx if need_x else None)
+        return _pack(dx, grads)
 
 
 def _lrt_bf16_forward(cfg, x, params):
@@ -712,8 +753,8 @@ def _lrt_bf16_forward(cfg, x, params):
 class _MCForwardLRTBF16(torch.autograd.Function):
     """Input gradients of all-LRT models in bf16 storage, frozen parameters (LaunchConfig.bf16_lrt + bf16_lrt_input_grad; the arithmetic
     contract is DESIGN.md section 4.5b): (x, W_mu0, sigma_W0^2, b_mu0, sigma_b0^2, ...) -> fp32 logits [E, C, B] batch-innermost.
-    Forward = _lrt_bf16_forward.  Backward = _MCForwardLRT._backward with the weight side removed -- no _Schedule weight side, no side
-    streams, no parameter gradient -- on bf16 storage, per layer from the top:
+    Forward = _lrt_bf16_forward.  Backward = _walk_back as _MCForwardLRT runs it, without a weight side -- a _Schedule that forks
+    nothing and waits on nothing, no parameter gradient -- on bf16 storage, per layer from the top:
       * ops.lrt_pool_act_backward_chwn_bf16   pooling / activation backward and the split into (g_mu, g_var) in one pass, eps
         regenerated from the counter (the stored y is rounded: the fp32 kernel's y - act_mu would cancel rounded values), the layer
         above's g1 + 2 x g2 combined on the fly; each of the pair rounded once to bf16,
@@ -740,31 +781,31 @@ class _MCForwardLRTBF16(torch.autograd.Function):
         if any(ctx.needs_input_grad[2:]):
             raise _lib.BBBHipError("bf16 LRT has input gradients only: no parameter gradient (bf16_train_refusal refuses trainable parameters)")
         seed, call0 = cfg["seed"], cfg["call0"]
-        dx = None
         g = g_logits.contiguous()
-        for li in range(len(tape) - 1, -1, -1):
-            rec = tape[li]
-            y, x_in, wshape = rec["y"], rec["x"], rec["wshape"]
-            stride, padding, dilation = rec["geom"]
-            # the incoming gradient: the logits' fp32 gradient, or the layer above's two bf16 input gradients + this layer's output,
-            # combined (d1 + 2 x d2) inside the pass
-            comb = None
-            if isinstance(g, tuple):
-                g, comb = g[0].reshape(rec["out_shape"]), (g[1].reshape(rec["out_shape"]), g[2].reshape(rec["out_shape"]))
-            else:
-                g = g.reshape(rec["out_shape"])
+        sched = _Schedule(g, weight_side=False)            # no weight side: nothing forks, nothing waits
+
+        def g_pre_of(rec, *incoming):                      # the logits' fp32 gradient, or the layer above's bf16 (d1, x_out, d2)
+            g, comb = _lrt_incoming(*incoming)
+            y = rec["y"]
             g_pair = _pool_pass(rec, ops.lrt_pool_act_backward_chwn_bf16, None, g, y if y.dtype == torch.bfloat16 else None, rec["av"],
                                 noise=(seed, call0, rec["sid"]), combine=comb)            # [2, E, Cout, Ho, Wo, B] bf16
+            return g_pair, []
+
+        def input_grad(li, rec, g_pair):
+            x_in, wshape = rec["x"], rec["wshape"]
+            stride, padding, dilation = rec["geom"]
             hw = (x_in.shape[2], x_in.shape[3])
-            if rec["first"]:
-                if ctx.needs_input_grad[1]:
-                    dx = ops.first_layer_input_grad_bf16_lrt(g_pair, rec["w_mu"], rec["w_var"], wshape, hw, stride, padding,
-                                                             dilation, ctx.x_b).view(ctx.x_b.shape)
-            else:
-                d1 = ops.conv2d_chwn_input_grad_bf16(g_pair[0], rec["w_mu"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
-                d2 = ops.conv2d_chwn_input_grad_bf16(g_pair[1], rec["w_var"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
-                g = (d1, x_in, d2)                         # (d1 + 2 x d2 is formed by the layer below's pass)
-        return (None, dx) + (None,) * (4 * len(tape))
+            d1 = ops.conv2d_chwn_input_grad_bf16(g_pair[0], rec["w_mu"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
+            d2 = ops.conv2d_chwn_input_grad_bf16(g_pair[1], rec["w_var"].unsqueeze(0), wshape, hw, padding, dilation, stride=stride)
+            return (d1, x_in, d2)                          # (d1 + 2 x d2 is formed by the layer below's pass)
+
+        def first_dx(rec, g_pair):
+            x_in = rec["x"]
+            return ops.first_layer_input_grad_bf16_lrt(g_pair, rec["w_mu"], rec["w_var"], rec["wshape"], (x_in.shape[2], x_in.shape[3]),
+                                                       *rec["geom"], ctx.x_b).view(ctx.x_b.shape)
+
+        dx = _walk_back(tape, g, sched, g_pre_of, None, input_grad, first_dx if ctx.needs_input_grad[1] else None)
+        return _pack(dx, [None] * (4 * len(tape)))
 
 
 def _strided_later_conv(net):

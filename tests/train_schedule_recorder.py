@@ -2,6 +2,8 @@
 which order, on which stream (`main`, `side0`, `side1`, ...), with tensors of which shape and dtype, and every wait_stream edge
 (who waits on whom).  The placement is value-neutral -- no gradient moves when a launch lands on another stream -- so the value
 suites cannot see it; tests/test_gpu_train_schedule.py compares these traces with tests/golden/train_schedule.json.
+Every case, the frozen bf16 LRT ones included, is driven through train.forward_loss + loss.backward() (the entry
+tests/test_gpu_bf16_lrt_input_grad.py calls "forward_loss"), under the case's LaunchConfig fields.
 
     python tests/train_schedule_recorder.py --write tests/golden/train_schedule.json --commit <the commit that is recorded>
 
@@ -127,18 +129,28 @@ class Recorder:
 B, HW, CLASSES = 8, 8, 4
 MODELS = {"cin3": dict(cin=3, stride2=1),          # first layer: the shared-input im2col path (forked early under side streams)
           "cin4": dict(cin=4, stride2=1),          # no im2col fork; the first layer on conv2d_chwn_weight_grad
-          "cin3_s2": dict(cin=3, stride2=2)}       # the transposed dgrad launch (fp32 and LRT nodes only)
+          "cin3_s2": dict(cin=3, stride2=2)}       # the transposed dgrad launch (the bf16 nodes: under bf16_strided_train)
 DEFAULT = dict(overlap_wgrad=True, flips_up_front=True, pair_lrt_backward=True, fold_lrt_combine=True)
+# node -> (the layers it is built from, the precision it runs at, the ensemble.stats["path"] it must take)
+NODES = {"fp32": ("bbb", "fp32", "chwn-autograd"), "bf16": ("bbb", "bf16", "chwn-autograd-bf16"),
+         "lrt": ("lrt", "fp32", "chwn-autograd"), "lrt_bf16": ("lrt", "bf16", "chwn-autograd-bf16-lrt")}
 
 
-def _variants(node):
+def _variants(model, node):
+    """{variant: settings}.  Settings: the fast_train switches of DEFAULT; frozen (frozen parameters, x.requires_grad: no weight
+    side, no side streams); config (LaunchConfig fields, applied with ops.use_config around the forward and the backward);
+    side_streams (fast_train.n_side_streams, 2 unless set)."""
+    strided = dict(bf16_strided_train=True) if MODELS[model]["stride2"] != 1 else {}
+    if node == "lrt_bf16":                         # input gradients with frozen parameters are all this node has
+        return {"frozen_dx": dict(frozen=True, config=dict(bf16_lrt=True, bf16_lrt_input_grad=True, **strided))}
+    if node == "bf16" and strided:
+        return {"default": dict(config=strided), "frozen_dx": dict(frozen=True, config=dict(bf16_input_grad=True, **strided))}
     out = {"default": {}, "overlap_off": dict(overlap_wgrad=False), "flips_off": dict(flips_up_front=False),
            "overlap_off_flips_off": dict(overlap_wgrad=False, flips_up_front=False)}
     if node == "lrt":
         out["pair_off"] = dict(pair_lrt_backward=False)
         out["fold_off"] = dict(fold_lrt_combine=False)
-    if node != "bf16":
-        out["frozen_dx"] = dict(frozen=True)       # frozen parameters, x.requires_grad: no weight side, no side streams
+    out["frozen_dx"] = dict(frozen=True, config=dict(bf16_input_grad=True)) if node == "bf16" else dict(frozen=True)
     return out
 
 
@@ -146,10 +158,8 @@ def cases():
     """{case id: (model, node, draws, variant settings)}."""
     out = {}
     for model in MODELS:
-        for node, draws in (("fp32", 2), ("bf16", 2), ("lrt", 2), ("lrt", 1)):
-            if node == "bf16" and model == "cin3_s2":
-                continue
-            for vname, v in _variants(node).items():
+        for node, draws in (("fp32", 2), ("bf16", 2), ("lrt", 2), ("lrt", 1), ("lrt_bf16", 2), ("lrt_bf16", 1)):
+            for vname, v in _variants(model, node).items():
                 out[f"{model}-{node}-e{draws}-{vname}"] = (model, node, draws, v)
     return out
 
@@ -157,7 +167,7 @@ def cases():
 def build(model, node):
     import ref_port_torch as P
     from layers import BBB_Conv2d, BBB_LRT_Conv2d, BBB_Linear, BBB_LRT_Linear, FlattenLayer, ModuleWrapper
-    Conv, Linear = (BBB_LRT_Conv2d, BBB_LRT_Linear) if node == "lrt" else (BBB_Conv2d, BBB_Linear)
+    Conv, Linear = (BBB_LRT_Conv2d, BBB_LRT_Linear) if NODES[node][0] == "lrt" else (BBB_Conv2d, BBB_Linear)
     spec = MODELS[model]
     torch.manual_seed(5)
     net = ModuleWrapper()
@@ -175,10 +185,12 @@ def build(model, node):
     return net
 
 
-def record(case, monkeypatch):
-    """One forward + backward of the case under the recorder -> the trace.  Every switch is restored."""
-    from bbb_hip import ensemble, fast_train, rng, train
+def record(case, monkeypatch, grads=None):
+    """One forward + backward of the case under the recorder -> the trace.  Every switch is restored.
+    grads: a dict that receives the gradients the backward left, "x" and every parameter's by name (None where there is none)."""
+    from bbb_hip import ensemble, fast_train, ops, rng, train
     model, node, draws, variant = case
+    _, precision, path = NODES[node]
     net = build(model, node).cuda()
     rng.assign_stream_ids(net)
     frozen = variant.get("frozen", False)
@@ -193,13 +205,13 @@ def record(case, monkeypatch):
     try:
         for k, v in switches.items():
             getattr(fast_train, k)[0] = v
-        fast_train.n_side_streams[0] = 2
-        fast_train._side_stream(device).i = 0                 # the round robin starts where a fresh process starts it
+        fast_train.n_side_streams[0] = variant.get("side_streams", 2)
+        if fast_train.n_side_streams[0] >= 1:
+            fast_train._side_stream(device).i = 0             # the round robin starts where a fresh process starts it
         torch.cuda.synchronize()
-        with Recorder(monkeypatch, device) as rec:
-            loss, _, _ = train.forward_loss(net, x, y, draws, 0.0 if frozen else 0.1, 100.0, seed_call=(7, 3),
-                                            precision="bf16" if node == "bf16" else "fp32")
-            assert ensemble.stats["path"] == ("chwn-autograd-bf16" if node == "bf16" else "chwn-autograd"), ensemble.stats["path"]
+        with Recorder(monkeypatch, device) as rec, ops.use_config(**variant.get("config", {})):
+            loss, _, _ = train.forward_loss(net, x, y, draws, 0.0 if frozen else 0.1, 100.0, seed_call=(7, 3), precision=precision)
+            assert ensemble.stats["path"] == path, ensemble.stats["path"]
             loss.backward()
         torch.cuda.synchronize()
     finally:
@@ -210,6 +222,8 @@ def record(case, monkeypatch):
         assert x.grad is not None and all(p.grad is None for p in net.parameters())
     else:
         assert all(p.grad is not None for p in net.parameters())
+    if grads is not None:
+        grads.update({"x": x.grad}, **{n: p.grad for n, p in net.named_parameters()})
     return rec.events
 
 
