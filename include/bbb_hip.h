@@ -883,6 +883,65 @@ int bbb_mc_uncertainty_cb_bwd_plan(const float* logits, const float* p_mean, int
                                    const float* w_expected_entropy, const float* w_mutual_info, const float* d_logits, int32_t* rows,
                                    int32_t* blocks, int32_t* lds_bytes);
 
+/*
+ * Regression with a Gaussian likelihood on batch-innermost logits (additive to ABI 13; csrc/gauss_tail.hip): logits [draws][C][B] fp32
+ * as the batched ensemble path and the training nodes leave them, targets y [B][dims] fp32.  channels == 2 * dims (heteroscedastic):
+ * channel d is the mean mu, channel dims + d the log-variance s; channels == dims (homoscedastic): s = 2 log(noise_sigma), rounded to
+ * fp32 once (noise_sigma is not read in the heteroscedastic form).  With s_c = clamp(s, log_var_min, log_var_max) and r = y - mu:
+ *   ll[e][d][b] = -0.5 (log 2 pi + s_c + r^2 exp(-s_c)),   L[e][b] = sum_d ll (d ascending),
+ *   LL[b] = logsumexp_e L[e][b] - log(mean_over > 0 ? mean_over : draws)   (mc = 0: the log of the mixture predictive density; the
+ *           log-sum-exp is an online one over e ascending and subtracts the running maximum first, so a draw 1e4 below the best one
+ *           weighs exactly 0)   or   (1 / draws) sum_e L[e][b]   (mc = 1: the ELBO's expected log-likelihood),
+ *   loss = -(train_size / B) sum_b LL[b] + beta * kl   (beta_dev != NULL: the KL weight is read from the device, as bbb_elbo_cb_fwd).
+ * bbb_gauss_elbo_cb_fwd: two launches that meet at the launch boundary -- LL [B] by 64-image blocks (ll_out), then ONE 256-thread block
+ * adds LL in a fixed order (thread t: b = t, t + 256, ...; then a fixed tree) into loss_out: the loss does not depend on the number of
+ * workgroups, every sum has a fixed order, there are no atomics.  y is staged through LDS (coalesced reads of the row-major targets).
+ * A NaN in a logit or target of image b makes LL[b] and the loss NaN (the clamp keeps a NaN).
+ * Limits (csrc/gauss_tail_plan.h): draws <= 512, channels <= 1024, batch <= INT32_MAX - 63.  Checks of all three entries, in this order:
+ * BBB_EINVAL (a required pointer that is NULL; a size that is not positive; channels neither dims nor 2 * dims; log_var_min >
+ * log_var_max; homoscedastic with a noise_sigma that is not finite and positive; mc outside {0, 1}; mean_over < 0), BBB_EALIGN (a
+ * pointer, optional ones included, that is not 4-byte aligned), BBB_ESHAPE (the limits).
+ */
+int bbb_gauss_elbo_cb_fwd(const float* logits, const float* y, const float* kl, float beta, const float* beta_dev, float train_size,
+                          int draws, int batch, int channels, int dims, double noise_sigma, float log_var_min, float log_var_max,
+                          int mc, int mean_over, float* ll_out, float* loss_out, void* stream);
+
+/* What bbb_gauss_elbo_cb_fwd launches first for these arguments, without the launch (host only, needs no device): the same checks and
+ * return codes; *threads: lanes of a block, 64 (one image each); *blocks: ceil(batch / 64); *lds_bytes: the staged tile of y,
+ * 64 x 17 floats = 4352.  The second launch is always one block of 256 threads.  Each of the three may be NULL. */
+int bbb_gauss_elbo_cb_fwd_plan(const float* logits, const float* y, const float* kl, const float* beta_dev, int draws, int batch,
+                               int channels, int dims, double noise_sigma, float log_var_min, float log_var_max, int mc, int mean_over,
+                               const float* ll_out, const float* loss_out, int32_t* threads, int32_t* blocks, int32_t* lds_bytes);
+
+/* Its backward in ONE launch: g_logits [draws][C][B] (every element written) and g_kl (device scalar, may be NULL) = beta * g_loss.
+ * L[e][b] is RECOMPUTED from the logits by the forward's own code (nothing is kept from the forward), then per (e, b):
+ *   w = exp(L[e][b] - logsumexp_e L[.][b])  (mc = 0)  or  1 / draws  (mc = 1),      c = -(train_size / B) * g_loss,
+ *   g_mu = c w r exp(-s_c),   g_s = c w 0.5 (r^2 exp(-s_c) - 1) for log_var_min <= s <= log_var_max, exactly 0 outside
+ * (torch.clamp's gradient).  A NaN of image b makes image b's columns NaN and no other's.  Same limits, same order of the checks;
+ * required: logits, y, g_loss, g_logits. */
+int bbb_gauss_elbo_cb_bwd(const float* logits, const float* y, const float* g_loss, float beta, const float* beta_dev, float train_size,
+                          int draws, int batch, int channels, int dims, double noise_sigma, float log_var_min, float log_var_max,
+                          int mc, int mean_over, float* g_logits, float* g_kl, void* stream);
+
+/* What bbb_gauss_elbo_cb_bwd launches, without the launch (host only): outputs as bbb_gauss_elbo_cb_fwd_plan's. */
+int bbb_gauss_elbo_cb_bwd_plan(const float* logits, const float* y, const float* g_loss, const float* beta_dev, int draws, int batch,
+                               int channels, int dims, double noise_sigma, float log_var_min, float log_var_max, int mc, int mean_over,
+                               const float* g_logits, const float* g_kl, int32_t* threads, int32_t* blocks, int32_t* lds_bytes);
+
+/* Predictive moments of a regression model in ONE launch: mean [B][dims] = (1 / draws) sum_e mu, epistemic = (1 / draws) sum_e
+ * (mu - mean)^2 (a second pass over the draws, never E[mu^2] - mean^2), aleatoric = (1 / draws) sum_e exp(s_c), total = epistemic +
+ * aleatoric, and log_density [B] = LL[b] in the mc = 0 form with mean_over = draws (needs y; y may be NULL otherwise).  Any output
+ * pointer may be NULL: that output is not written, the others keep their bits.  Checks as above: BBB_EINVAL also for all five outputs
+ * NULL and for log_density without y. */
+int bbb_gauss_moments_cb(const float* logits, const float* y, int draws, int batch, int channels, int dims, double noise_sigma,
+                         float log_var_min, float log_var_max, float* mean, float* epistemic, float* aleatoric, float* total,
+                         float* log_density, void* stream);
+
+/* What bbb_gauss_moments_cb launches, without the launch (host only): outputs as bbb_gauss_elbo_cb_fwd_plan's. */
+int bbb_gauss_moments_cb_plan(const float* logits, const float* y, int draws, int batch, int channels, int dims, double noise_sigma,
+                              float log_var_min, float log_var_max, const float* mean, const float* epistemic, const float* aleatoric,
+                              const float* total, const float* log_density, int32_t* threads, int32_t* blocks, int32_t* lds_bytes);
+
 /* [rows][cols] -> [cols][rows] (e.g. an NCHW batch [B][C*H*W] into the batch-innermost [C*H*W][B] layout). */
 int bbb_transpose2d(const float* in, float* out, int64_t rows, int64_t cols, void* stream);
 

@@ -152,6 +152,19 @@ _SIGNATURES = {
     "bbb_mc_uncertainty_cb_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_void_p, c_void_p]),
     "bbb_mc_uncertainty_cb_bwd_plan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 7 + [c_void_p]
                                        + [ctypes.POINTER(c_i32)] * 3),
+    # (shared middle of the six Gaussian-tail entries: draws, batch, channels, dims, noise_sigma, log_var_min, log_var_max)
+    "bbb_gauss_elbo_cb_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                      c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bbb_gauss_elbo_cb_fwd_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_float,
+                                           c_float, c_int, c_int, c_void_p, c_void_p] + [ctypes.POINTER(c_i32)] * 3),
+    "bbb_gauss_elbo_cb_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                      c_float, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "bbb_gauss_elbo_cb_bwd_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_float,
+                                           c_float, c_int, c_int, c_void_p, c_void_p] + [ctypes.POINTER(c_i32)] * 3),
+    "bbb_gauss_moments_cb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_float, c_float] + [c_void_p] * 5
+                             + [c_void_p]),
+    "bbb_gauss_moments_cb_plan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_float, c_float]
+                                  + [c_void_p] * 5 + [ctypes.POINTER(c_i32)] * 3),
     "bbb_transpose2d": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p]),
     "bbb_flip_transpose_w": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
     "bbb_flip_transpose_w_multi": (c_int, [ctypes.POINTER(FlipSeg), c_int, c_void_p]),

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops, pool_desc, rng, _lib
+from . import likelihood, ops, pool_desc, rng, _lib
 from .conv_desc import out_map
 from .infer_walk import (BAYES_FORMS, ChwnPartition, ChwnPlan, ChwnStep, chwn_partition, conv_flops,  # noqa: F401
                          _act_name, _chwn_steps, _chwn_walk, _run)
@@ -726,7 +726,14 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
     precision="bf16" with elbo (train.forward_loss(precision="bf16")) and autograd on: the bf16 training mode
     (fast_train.mc_logits_autograd -> _MCForwardBF16), which raises for what it does not cover; the forward-only entry points keep refusing
     autograd -- except, under LaunchConfig.bf16_input_grad, on an input that requires a gradient (_bf16_x_grad): the same node, or a
-    BBBHipError that names what it does not cover."""
+    BBBHipError that names what it does not cover.
+    elbo = [y, beta, train_size, None, likelihood] (train.forward_loss(likelihood=GaussianLikelihood)): the same walk, and whichever
+    way the logits come -- an autograd node, the batch-innermost inference path with autograd off, or mc_logits transposed once, as
+    mc_logits_cb_autograd provides them -- they end in _autograd_tail's Gaussian branch: -> (LL [B], kl), the loss in elbo[3]."""
+    gauss = _gauss_request(elbo)
+    if gauss and (units is not None or int(groups) > 1 or share is not None or b_offset or step_end is not None or timers is not None):
+        raise _lib.BBBHipError("a Gaussian likelihood covers whole local steps only: group= sharding of a Gaussian step (work units, "
+                               "groups of steps, shares of a group, batch offsets), captured inference steps and timers are out of scope")
     if precision == "bf16" and elbo is not None and torch.is_grad_enabled():
         if not (fuse_act and fast_autograd) or timers is not None or units is not None or int(groups) > 1 or share is not None or b_offset:
             raise _lib.BBBHipError("bf16 training runs on the batch-innermost autograd node only")
@@ -769,6 +776,8 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
         if out is None and need is not None:
             raise _lib.BBBHipError(need)
         if out is not None:
+            if gauss:
+                return _autograd_tail(out[0], out[1], mean_over, elbo)
             if step_end is not None and timers is None:
                 lse, klf = tail(out[0], step_end=(out[1], step_end[0], step_end[1], step_end[2]))
                 step_end[3] = True
@@ -786,6 +795,8 @@ def _local_lse(net, x, draws, seed, call0, mean_over, fuse_act=True, timers=None
             stats["path"] = "chwn-autograd"
             return _autograd_tail(logits_cb, kl1, mean_over, elbo)
     logits, kl1 = mc_logits(net, x, draws, seed, call0, fuse_act=fuse_act, timers=timers, layout="nchw")
+    if gauss:
+        return _autograd_tail(logits.permute(0, 2, 1).contiguous(), kl1, mean_over, elbo)
     if torch.is_grad_enabled() and logits.requires_grad:
         # training extension: differentiable tail through torch ops
         lse = torch.logsumexp(F.log_softmax(logits, dim=2), dim=0) - (math.log(mean_over) if mean_over > 0 else 0.0)
@@ -848,7 +859,18 @@ def _x_grad_node_ok(net, x, fuse_act, timers):
 
 
 def _autograd_tail(logits_cb, kl1, mean_over, elbo):
-    """The loss tail of the batch-innermost autograd node's logits [E, C, B] (fp32 in either training precision)."""
+    """The loss tail of the batch-innermost autograd node's logits [E, C, B] (fp32 in either training precision).
+    elbo with a fifth entry, a likelihood.GaussianLikelihood (train.forward_loss(likelihood=...)): elbo[0] is y [B, D] and the result is
+    (LL [B], kl) with the loss always left in elbo[3] -- by the tail's own launches (ops.gauss_elbo_cb_autograd), or by the torch
+    expression (likelihood.gaussian_elbo) under hip_gauss_tail[0] = False and for what ops.gauss_elbo_cb_ok refuses."""
+    if _gauss_request(elbo):
+        lik = elbo[4]
+        likelihood.check_target(logits_cb, elbo[0], lik, "forward_loss")
+        if hip_gauss_tail[0] and ops.gauss_elbo_cb_ok(logits_cb, kl1, elbo[0], elbo[1], lik):
+            elbo[3], ll = ops.gauss_elbo_cb_autograd(logits_cb, kl1, elbo[0], elbo[1], elbo[2], lik, mean_over)
+        else:
+            elbo[3], ll = likelihood.gaussian_elbo(logits_cb, elbo[0], kl1, elbo[1], elbo[2], lik, mean_over)
+        return ll, kl1
     if elbo is not None and hip_loss_tail[0] and ops.elbo_cb_ok(logits_cb, kl1, elbo[0], elbo[1]):
         elbo[3], lse = ops.elbo_cb_autograd(logits_cb, kl1, elbo[0], elbo[1], elbo[2], mean_over)
         return lse, kl1
@@ -861,6 +883,12 @@ def _autograd_tail(logits_cb, kl1, mean_over, elbo):
 
 
 hip_loss_tail = [True]      # training: the loss tail's log_softmax + logmeanexp on the HIP kernels (False: torch ops, as until round 5)
+hip_gauss_tail = [True]     # regression: the Gaussian loss tail on the HIP kernels (False: likelihood.gaussian_elbo, the torch expression)
+
+
+def _gauss_request(elbo):
+    """A training request list that carries a Gaussian likelihood: [y, beta, train_size, None, likelihood]."""
+    return elbo is not None and len(elbo) > 4 and elbo[4] is not None
 
 
 def group_share(num_ens, steps, rank, world):

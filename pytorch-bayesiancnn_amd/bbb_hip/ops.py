@@ -1746,6 +1746,108 @@ def mc_uncertainty_cb_autograd(logits_cb, normalized=False, want=None):
     return Uncertainty(*[outs.get(f) for f in Uncertainty._fields])
 
 
+# ---- regression with a Gaussian likelihood (csrc/gauss_tail.hip; the likelihood object: likelihood.GaussianLikelihood) ----
+GAUSS_MAX_DRAWS = 512
+GAUSS_MAX_CHANNELS = 1024
+GAUSS_MC_CODE = {"logmeanexp": 0, "mean": 1}
+Moments = collections.namedtuple("Moments", "mean epistemic aleatoric total log_density")
+
+
+def _gauss_shape(logits, y_dims, lik):
+    """The shared middle of the six C entries: draws, batch, channels, dims, noise_sigma, log_var_min, log_var_max."""
+    E, C, B = logits.shape
+    return (E, B, C, int(y_dims), 0.0 if lik.noise_sigma is None else float(lik.noise_sigma), float(lik.log_var_min),
+            float(lik.log_var_max))
+
+
+class _GaussElboCB(torch.autograd.Function):
+    """(loss, LL) = the whole loss tail of a regression step: LL [B] in one launch and the loss in a one-block launch behind it
+    (bbb_gauss_elbo_cb_fwd); backward in ONE launch (bbb_gauss_elbo_cb_bwd: d loss / d logits and d loss / d kl), which recomputes
+    the per-draw log-likelihoods from the logits -- about 30 ATen launches forward and backward as torch ops."""
+
+    @staticmethod
+    def forward(ctx, logits, kl, y, beta, train_size, lik, mean_over):
+        logits = logits.contiguous()
+        E, C, B = logits.shape
+        klc = kl.detach().reshape(()).contiguous()
+        ll = torch.empty((B,), dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        beta_t = beta if torch.is_tensor(beta) else None
+        with on_device(logits.device):
+            check(_lib.lib().bbb_gauss_elbo_cb_fwd(logits.data_ptr(), y.data_ptr(), klc.data_ptr(),
+                                                   0.0 if beta_t is not None else float(beta), ptr(beta_t), float(train_size),
+                                                   *_gauss_shape(logits, y.shape[1], lik), GAUSS_MC_CODE[lik.mc], int(mean_over),
+                                                   ll.data_ptr(), loss.data_ptr(), cur_stream(logits.device)), "bbb_gauss_elbo_cb_fwd")
+        ctx.save_for_backward(logits, y)
+        ctx.beta, ctx.beta_t, ctx.train_size, ctx.mean_over = (None if beta_t is not None else float(beta)), beta_t, float(train_size), int(mean_over)
+        ctx.lik, ctx.kl_shape = lik, tuple(kl.shape)
+        ctx.mark_non_differentiable(ll)
+        return loss, ll
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_ll):
+        logits, y = ctx.saved_tensors
+        g_loss = g_loss.to(dtype=torch.float32).reshape(()).contiguous()
+        out = torch.empty_like(logits)
+        g_kl = torch.empty(ctx.kl_shape, dtype=torch.float32, device=logits.device)
+        with on_device(logits.device):
+            check(_lib.lib().bbb_gauss_elbo_cb_bwd(logits.data_ptr(), y.data_ptr(), g_loss.data_ptr(),
+                                                   0.0 if ctx.beta_t is not None else ctx.beta, ptr(ctx.beta_t), ctx.train_size,
+                                                   *_gauss_shape(logits, y.shape[1], ctx.lik), GAUSS_MC_CODE[ctx.lik.mc], ctx.mean_over,
+                                                   out.data_ptr(), g_kl.data_ptr(), cur_stream(logits.device)), "bbb_gauss_elbo_cb_bwd")
+        return out, g_kl, None, None, None, None, None
+
+
+def gauss_elbo_cb_ok(logits, kl, y, beta, lik):
+    """The fused Gaussian loss tail takes: logits [E <= 512, C <= 1024, B] fp32 on the device, a one-element fp32 kl there too, fp32
+    contiguous targets y [B, D] there too with C == 2 D (lik.noise_sigma None) or C == D, beta a Python number or a one-element fp32
+    device tensor."""
+    return (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3
+            and logits.shape[0] <= GAUSS_MAX_DRAWS and logits.shape[1] <= GAUSS_MAX_CHANNELS
+            and torch.is_tensor(kl) and kl.device == logits.device and kl.dtype == torch.float32 and kl.numel() == 1
+            and torch.is_tensor(y) and y.device == logits.device and y.dtype == torch.float32 and y.dim() == 2
+            and y.shape[0] == logits.shape[2] and y.shape[1] > 0 and y.is_contiguous() and not y.requires_grad
+            and logits.shape[1] == y.shape[1] * (2 if lik.noise_sigma is None else 1) and lik.mc in GAUSS_MC_CODE
+            and (not torch.is_tensor(beta) or (beta.device == logits.device and beta.dtype == torch.float32 and beta.numel() == 1
+                                               and not beta.requires_grad)))
+
+
+def gauss_elbo_cb_autograd(logits, kl, y, beta, train_size, lik, mean_over=0):
+    """Differentiable (loss, LL [B]) of one Monte-Carlo regression step from its logits [E, C, B], its targets y [B, D] and the KL of
+    one forward under a likelihood.GaussianLikelihood; LL carries no gradient.  The arithmetic: train.gaussian_elbo's."""
+    require_device(logits)
+    if not gauss_elbo_cb_ok(logits, kl, y, beta, lik):
+        raise _lib.BBBHipError("gauss_elbo_cb_autograd: see gauss_elbo_cb_ok for the accepted operands")
+    return _GaussElboCB.apply(logits, kl, y, beta, float(train_size), lik, int(mean_over))
+
+
+def gauss_moments_cb(logits, lik, y=None, want=None):
+    """Batch-innermost logits [T <= 512, C, B] of a regression model -> ops.Moments in one launch (bbb_gauss_moments_cb): mean,
+    epistemic, aleatoric, total [B, D] and, with targets y [B, D], log_density [B] (the log of the mixture predictive density at y),
+    device tensors.  want: the field names to compute (None: all that the arguments allow); the other fields are None, and a field's
+    bits do not depend on what else was asked for."""
+    require_device(logits, y)
+    fields = Moments._fields if y is not None else Moments._fields[:4]
+    want = fields if want is None else tuple(want)
+    unknown = [w for w in want if w not in fields]
+    if unknown or not want:
+        raise _lib.BBBHipError(f"want must name at least one of {fields}" + ("" if y is not None else " (log_density needs y)")
+                               + f", got {want!r}")
+    logits = logits.contiguous()
+    T, C, B = logits.shape
+    per = 2 if lik.noise_sigma is None else 1
+    if C % per != 0 or (y is not None and (y.dim() != 2 or tuple(y.shape) != (B, C // per))):
+        raise _lib.BBBHipError(f"gauss_moments_cb: logits {tuple(logits.shape)} do not fit this likelihood / y")
+    D = C // per
+    y = y.contiguous() if y is not None else None
+    outs = [torch.empty((B, D) if i < 4 else (B,), dtype=torch.float32, device=logits.device) if f in want else None
+            for i, f in enumerate(Moments._fields)]
+    with on_device(logits.device):
+        check(_lib.lib().bbb_gauss_moments_cb(logits.data_ptr(), ptr(y), *_gauss_shape(logits, D, lik), *[ptr(t) for t in outs],
+                                              cur_stream(logits.device)), "bbb_gauss_moments_cb")
+    return Moments(*outs)
+
+
 def to_batch_innermost(x):
     """[B, C, H, W] -> [C, H, W, B] (LDS-tiled transpose)."""
     require_device(x)

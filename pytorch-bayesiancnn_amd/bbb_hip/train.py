@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from . import _lib, ensemble, ops, rng
 from ._lib import AdamSegment, check, cur_stream
+from .likelihood import GaussianLikelihood, gaussian_elbo  # noqa: F401  (train.GaussianLikelihood, train.gaussian_elbo)
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -292,15 +293,30 @@ def _check_train_precision(precision):
         raise _lib.BBBHipError(f"training precision must be 'fp32' or 'bf16', got {precision!r}")
 
 
-def forward_loss(net, x, target, num_ens, beta, train_size, seed_call=None, param_alias=None, precision="fp32"):
+def _check_likelihood(likelihood, x, target):
+    if not isinstance(likelihood, GaussianLikelihood):
+        raise _lib.BBBHipError(f"likelihood must be a train.GaussianLikelihood or None, got {type(likelihood).__name__}")
+    _lib.require_device(x)
+    if not torch.is_tensor(target) or target.dim() != 2 or target.shape[0] != x.shape[0] or target.dtype != torch.float32:
+        raise _lib.BBBHipError("with a Gaussian likelihood the target is y [B, D], fp32")
+    _lib.require_device(target)
+
+
+def forward_loss(net, x, target, num_ens, beta, train_size, seed_call=None, param_alias=None, precision="fp32", likelihood=None):
     """The forward half of a training iteration (main_bayesian.py:43-56): num_ens stochastic forwards batched over the draws,
     kl of one forward (= the reference's kl / num_ens), logmeanexp, ELBO -> (loss, log_outputs, kl).  On the batch-innermost
     autograd path the loss tail is two HIP launches forward and one backward (ops.elbo_cb_autograd); elsewhere torch ops.
     seed_call: (seed, call0) reserved by the caller (a captured step); default: num_ens fresh call indices.
     precision: "fp32" (the reference's arithmetic) or "bf16" -- sampled weights, activations and the gradients passed between
     layers stored as bf16, parameters, their gradients, KL and the loss fp32; BBB models on the
-    batch-innermost training path with B % 8 == 0 only, anything else raises BBBHipError."""
+    batch-innermost training path with B % 8 == 0 only, anything else raises BBBHipError.
+    likelihood: None (the categorical path above) or a GaussianLikelihood -- regression: target is y [B, D] fp32, the model's last
+    Bayesian linear layer has 2 D (heteroscedastic) or D outputs, and the return is (loss, LL [B], kl) with LL the per-image
+    log-likelihood of gaussian_elbo.  The logits come from the same forward (the same autograd nodes, in either precision); the tail
+    is two HIP launches forward and one backward (ops.gauss_elbo_cb_autograd), or gaussian_elbo for what it refuses."""
     _check_train_precision(precision)
+    if likelihood is not None:
+        _check_likelihood(likelihood, x, target)
     if precision == "bf16" and torch.is_grad_enabled():
         from . import fast_train
         why = fast_train.bf16_train_refusal(net, x) if ensemble.fast_autograd else "the batch-innermost autograd path"
@@ -309,9 +325,11 @@ def forward_loss(net, x, target, num_ens, beta, train_size, seed_call=None, para
     if seed_call is None:
         rng.assign_stream_ids(net)
         seed_call = rng.next_calls(int(num_ens))
-    req = [target, beta, float(train_size), None]
+    req = [target, beta, float(train_size), None] + ([likelihood] if likelihood is not None else [])
     log_outputs, kl = ensemble._local_lse(net, x, int(num_ens), seed_call[0], seed_call[1], int(num_ens), param_alias=param_alias, elbo=req,
                                           precision=precision)
+    if likelihood is not None:
+        return req[3], log_outputs, kl                # (ensemble._autograd_tail: a Gaussian request always leaves with its loss)
     loss = req[3] if req[3] is not None else elbo(log_outputs, target, kl, beta, train_size)
     return loss, log_outputs, kl
 
@@ -367,7 +385,7 @@ def _python_hooks(net, optimizer):
     return any(getattr(p, "_backward_hooks", None) for p in net.parameters())
 
 
-def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
+def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32", likelihood=None):
     """What a captured step bakes in; None = this call cannot be a graph replay (-> eager)."""
     if not (auto_graph["enabled"] and isinstance(optimizer, FusedAdam) and torch.is_tensor(x) and x.is_cuda and target.is_cuda
             and torch.is_grad_enabled() and not x.requires_grad and not torch.cuda.is_current_stream_capturing()):
@@ -384,10 +402,11 @@ def _auto_key(net, optimizer, x, target, num_ens, train_size, precision="fp32"):
             ops.current_config().bf16_strided_train,                        # (what bf16_train_refusal admits: switched off, it must refuse again)
             ops.current_config().bf16_avgpool,                              # (likewise)
             getattr(optimizer, "max_grad_norm", None), getattr(optimizer, "skip_nonfinite", False),   # constants of the captured norm and Adam launches
+            likelihood.key() if likelihood is not None else None,           # (a categorical and a Gaussian step never replay each other)
             precision)                                                      # (the precision stays the LAST field: callers read key[-1])
 
 
-def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=None, graph=None, precision="fp32"):
+def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=None, graph=None, precision="fp32", likelihood=None):
     """One iteration of train_model's batch loop (main_bayesian.py:40-58): zero_grad, num_ens stochastic forwards
     (batched over draws), kl / num_ens, logmeanexp, ELBO, backward, [gradient all-reduce], optimizer.step.
     dp_group: data-parallel process group whose ranks hold different shards of the batch (parameters replicated).
@@ -400,10 +419,14 @@ def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=No
     rate stay run-time values; a non-capturable FusedAdam is switched to capturable in place).  Any change of the key drops the
     graph and returns to launch-by-launch steps.  graph=False: never capture.  Same noise calls, same results as the eager
     sequence (tests/test_gpu_train.py).
-    precision: "fp32" or "bf16" (forward_loss); part of the self-capture key, so fp32 and bf16 calls never replay each other's graph."""
+    precision: "fp32" or "bf16" (forward_loss); part of the self-capture key, so fp32 and bf16 calls never replay each other's graph.
+    likelihood: None or a GaussianLikelihood (forward_loss): target is then y [B, D] and the return (loss, LL [B], kl); its fields are
+    part of the self-capture key too.  dp_group works as for the categorical loss (the loss is local)."""
     _check_train_precision(precision)
+    if likelihood is not None:
+        _check_likelihood(likelihood, x, target)
     small = graph is True or x.shape[0] * int(num_ens) < int(auto_graph.get("max_rows", 1 << 62))     # (graph=True: capture whatever the size)
-    key = _auto_key(net, optimizer, x, target, num_ens, train_size, precision) if (graph is not False and dp_group is None and small) else None
+    key = _auto_key(net, optimizer, x, target, num_ens, train_size, precision, likelihood) if (graph is not False and dp_group is None and small) else None
     st = _auto.get(net)
     if key is None or st is None or st["key"] != key:
         if key is not None:
@@ -419,14 +442,14 @@ def train_step(net, optimizer, x, target, num_ens, beta, train_size, dp_group=No
         if st["streak"] > int(auto_graph["after"]) and not _python_hooks(net, optimizer):
             optimizer.make_capturable()
             g = GraphedTrainStep(net, optimizer, x, target, num_ens, beta, train_size, warmup=1, weak_net=True,   # the warm-up IS this iteration
-                                 precision=precision)
+                                 precision=precision, likelihood=likelihood)
             if g.graph is not None:
                 st["graphed"] = g
             else:
                 st["streak"] = -(1 << 60)            # capture refused (stale gradient accumulators): launch by launch from here on
             return g.warm_loss.clone(), g.warm_log_outputs.clone(), g.warm_kl.clone()
     optimizer.zero_grad()
-    loss, log_outputs, kl = forward_loss(net, x, target, num_ens, beta, train_size, precision=precision)
+    loss, log_outputs, kl = forward_loss(net, x, target, num_ens, beta, train_size, precision=precision, likelihood=likelihood)
     loss.backward()
     if dp_group is not None:
         allreduce_gradients([p for g in optimizer.param_groups for p in g["params"]], dp_group)
@@ -445,14 +468,18 @@ class GraphedTrainStep:
     step(beta=...) sets the former, optimizer.param_groups[i]['lr'] is pushed before every replay.
     `warmup` real training iterations run eagerly on the capture stream first.
     The optimizer must be FusedAdam(capturable=True) (or another capturable optimizer that keeps lr on the device).
-    precision: "fp32" or "bf16" (forward_loss), a constant of the captured graph."""
+    precision: "fp32" or "bf16" (forward_loss), a constant of the captured graph; likelihood: None or a GaussianLikelihood
+    (forward_loss), a constant of the captured graph too -- step() then takes y [B, D] as its target and returns (loss, LL [B], kl)."""
 
     def __init__(self, net, optimizer, x, target, num_ens, beta, train_size, warmup=3, weak_net=False, launch_config=None,
-                 precision="fp32"):
+                 precision="fp32", likelihood=None):
         from . import rng
         _lib.require_device(x)
         _check_train_precision(precision)
         self.precision = precision
+        if likelihood is not None:
+            _check_likelihood(likelihood, x, target)
+        self.likelihood = likelihood
         self.launch_config = (launch_config if launch_config is not None else ops.current_config()).copy()
         # weak_net (train_step's self-capture keeps this object ON the net): no net -> state -> step -> net cycle, so dropping the
         # net frees the graph then and there instead of whenever the cyclic collector runs (possibly inside another capture)
@@ -515,7 +542,7 @@ class GraphedTrainStep:
             alias = {id(p): p.detach().requires_grad_(True) for p in params}
         loss, log_outputs, kl = forward_loss(self.net, self.x, self.target, self.num_ens, self.beta, self.train_size,   # kl of one forward
                                              seed_call=(self.seed, self.call0), param_alias=alias,           # = kl / num_ens of the sum
-                                             precision=self.precision)
+                                             precision=self.precision, likelihood=self.likelihood)
         leaves = params if alias is None else [alias[id(p)] for p in params]
         grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         for p, g in zip(params, grads):

@@ -52,6 +52,23 @@ def mc_uncertainty(net, batch, T=15, normalized=False, precision="fp32", grad=Fa
     return ops.mc_uncertainty_cb_autograd(logits_cb, normalized=normalized, want=want)
 
 
+def mc_regression(net, batch, T=15, likelihood=None, y=None, precision="fp32", want=None):
+    """The regression counterpart of mc_uncertainty: T stochastic forwards of the batch under a train.GaussianLikelihood ->
+    ops.Moments (mean, epistemic, aleatoric, total [B, D]; with targets y [B, D] also log_density [B], the log of the mixture
+    predictive density at y), all on the device and without a synchronisation.  The forwards run on ensemble.mc_logits_cb under
+    no_grad, the reduction is ONE launch on the batch-innermost logits (ops.gauss_moments_cb).  Consumes T noise calls, as
+    mc_uncertainty does.  precision: as mc_logits.  want: the fields to compute (None: all that y allows).
+    Out of scope: a captured class (as GraphedUncertainty) and a differentiable form (as mc_uncertainty(grad=True))."""
+    from .likelihood import GaussianLikelihood
+    if not isinstance(likelihood, GaussianLikelihood):
+        raise _lib.BBBHipError(f"mc_regression needs likelihood=train.GaussianLikelihood(...), got {type(likelihood).__name__}")
+    with torch.no_grad():
+        seed, call0 = rng.next_calls(T)
+        dev = next(net.parameters()).device
+        logits_cb, _ = ensemble.mc_logits_cb(net, batch.to(dev), T, seed, call0, precision=precision)
+        return ops.gauss_moments_cb(logits_cb, likelihood, y=None if y is None else y.to(dev), want=want)
+
+
 SCORES = ("entropy", "expected_entropy", "mutual_info")
 
 
