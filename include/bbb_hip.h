@@ -126,6 +126,50 @@ int bbb_reparam_kl_bwd(const bbb_segment_t* segs, int nseg, int draws,
                        const float* gkl, float* const* grad_mu, float* const* grad_rho,
                        const uint32_t* call_dev, void* stream);
 
+/*
+ * Per-weight Gaussian priors (additive to ABI 13): the same pass against N(mu0_i, sigma0_i^2) per element instead of one scalar
+ * pair for the whole launch -- the posterior of an earlier task as the prior of the next (variational continual learning), or an
+ * empirical-Bayes prior centred on pretrained weights (MOPED).  pri: host array of nseg entries, pri[s] for segs[s]; both pointers
+ * are DEVICE fp32 [segs[s].n] in the tensor's own order, 4-byte aligned (else BBB_EALIGN), and either may be NULL independently:
+ * that quantity of that segment is then the launch-wide scalar (prior_mu / prior_sigma).  pri == NULL, or no pointer set: the
+ * launch IS bbb_reparam_kl_fwd / _bwd's, same kernels, same bits.
+ *   KL term, reference form (metrics.py:28 in the call-site argument order; a_i = sigma0_i / sigma_i, b_i = (mu_i - mu0_i) / sigma_i):
+ *       0.5 * (2 ln(sigma_i / sigma0_i) - 1 + a_i^2 + b_i^2)
+ *   BBB_KL_TEXTBOOK (a_i = sigma_i / sigma0_i, b_i = (mu0_i - mu_i) / sigma0_i):
+ *       0.5 * (-2 ln(sigma_i / sigma0_i) - 1 + a_i^2 + b_i^2)
+ *   backward, reference form:  grad_mu  += gkl * (mu_i - mu0_i) / sigma_i^2
+ *                              grad_rho += gkl * (1/sigma_i - (sigma0_i^2 + (mu_i - mu0_i)^2) / sigma_i^3) * sigmoid(rho_i)
+ *             textbook form:   grad_mu  += gkl * (mu_i - mu0_i) / sigma0_i^2
+ *                              grad_rho += gkl * (sigma_i / sigma0_i^2 - 1/sigma_i) * sigmoid(rho_i)
+ *   Nothing flows to the prior.  With mu0 = mu and sigma0 = softplus(rho) the true KL is 0 and the fp32 sum may come out slightly
+ *   negative.
+ * The prior reaches the KL only: w, sigma / sigma^2, the noise, tap-major and bf16 outputs are the scalar launch's, bit for bit, and
+ * the launch shape (kernel, grid, chunks, split, summing block: bbb_reparam_kl_tp_plan) does not depend on the prior.  HBM traffic
+ * per element: (8 + 4 per prior tensor + 4 E) B for E draws.
+ * prior_sigma > 0 is checked on the host whether or not a segment falls back to it.  Tensor ELEMENTS are not checked: a
+ * sigma0_i <= 0 or a non-finite element follows IEEE and stays in the sum, so the KL is NaN or Inf; no other output changes.
+ * Every other argument is bbb_reparam_kl_fwd's / _bwd's / _plan's.  bbb_reparam_kl_tp_plan returns what bbb_reparam_kl_tp_fwd returns
+ * for the same segments and priors, and reports the same eight fields as bbb_reparam_kl_plan.
+ */
+typedef struct bbb_prior_segment {
+    const float* mu0;      /* [n] prior means, NULL = prior_mu */
+    const float* sigma0;   /* [n] prior standard deviations (> 0), NULL = prior_sigma */
+} bbb_prior_segment_t;
+
+int bbb_reparam_kl_tp_fwd(const bbb_segment_t* segs, const bbb_prior_segment_t* pri, int nseg, int draws,
+                          float prior_mu, float prior_sigma,
+                          uint64_t seed, uint32_t call0, uint32_t flags,
+                          double* kl_partials, float* kl_out, double* kl_out64,
+                          const uint32_t* call_dev, void* stream);
+int bbb_reparam_kl_tp_bwd(const bbb_segment_t* segs, const bbb_prior_segment_t* pri, int nseg, int draws,
+                          float prior_mu, float prior_sigma,
+                          uint64_t seed, uint32_t call0, uint32_t flags,
+                          const float* gkl, float* const* grad_mu, float* const* grad_rho,
+                          const uint32_t* call_dev, void* stream);
+int bbb_reparam_kl_tp_plan(const bbb_segment_t* segs, const bbb_prior_segment_t* pri, int nseg, int draws, int slots,
+                           int32_t* kernel, int32_t* gpt, int32_t* nt, int32_t* chunks, int32_t* n_small, int32_t* small_chunk0,
+                           int32_t* tm_blocks, int32_t* grid);
+
 /* One parameter tensor of an Adam step: all four arrays hold n fp32 elements on the device. */
 typedef struct bbb_adam_segment {
     float* param;        /* updated in place */

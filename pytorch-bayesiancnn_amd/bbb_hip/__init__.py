@@ -8,6 +8,7 @@
   fast_train  one autograd node for the batched forward on the inference kernels (training extension)
   train     train_step / FusedAdam / GraphedTrainStep / data-parallel gradient averaging
   metrics   ELBO, get_beta, device-side accuracy (metrics.py upstream, without the per-step host sync)
+  priors    per-weight Gaussian priors for whole models: from_posterior (continual learning), moped, clear, state_dict
   zoo       BBBLeNet / BBBAlexNet / BBB3Conv3FC built from a topology table (same constructor surface as
             the reference's models/BayesianModels/*.py, for hosts without the reference checkout)
 The drop-in boundary itself is the sibling package ``layers``.
@@ -48,5 +49,5 @@ def nccl_event_cache_known_off():
         return False
     return _event_cache_off_before_import or not _dist_initialized_before_import
 
-from . import _lib, rng, ops  # noqa: E402,F401
+from . import _lib, rng, ops, priors  # noqa: E402,F401
 from ._lib import BBBHipError, LIB_PATH  # noqa: E402,F401

@@ -29,6 +29,10 @@ class Segment(ctypes.Structure):
                 ("n", c_i64), ("draw_stride", c_i64), ("stream_id", c_u32), ("w_row_len", c_u32), ("w_taps", c_u32), ("w_tm_cin", c_u32)]
 
 
+class PriorSegment(ctypes.Structure):
+    _fields_ = [("mu0", c_void_p), ("sigma0", c_void_p)]
+
+
 class AdamSegment(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("n", c_i64)]
 
@@ -66,6 +70,12 @@ _SIGNATURES = {
     "bbb_reparam_kl_plan": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_int] + [ctypes.POINTER(c_i32)] * 8),
     "bbb_reparam_kl_bwd": (c_int, [ctypes.POINTER(Segment), c_int, c_int, c_float, c_float, c_u64, c_u32, c_u32,
                                    c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
+    "bbb_reparam_kl_tp_fwd": (c_int, [ctypes.POINTER(Segment), ctypes.POINTER(PriorSegment), c_int, c_int, c_float, c_float, c_u64, c_u32,
+                                      c_u32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "bbb_reparam_kl_tp_plan": (c_int, [ctypes.POINTER(Segment), ctypes.POINTER(PriorSegment), c_int, c_int, c_int]
+                               + [ctypes.POINTER(c_i32)] * 8),
+    "bbb_reparam_kl_tp_bwd": (c_int, [ctypes.POINTER(Segment), ctypes.POINTER(PriorSegment), c_int, c_int, c_float, c_float, c_u64, c_u32,
+                                      c_u32, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
     "bbb_adam_step": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                             c_i64, c_void_p, c_void_p, c_void_p]),
     "bbb_adam_step_plan": (c_int, [ctypes.POINTER(AdamSegment), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -204,6 +204,23 @@ class Timers:
         return agg
 
 
+def _prior_lists(layers):
+    """Tensor priors of a launch over `layers`, in _param_lists() order; None when no layer has any (layers/_base.py: prior_lists)."""
+    per = [l._prior_lists() for l in layers]
+    if all(p is None for p in per):
+        return None
+    out = []
+    for l, p in zip(layers, per):
+        out += p if p is not None else [(None, None)] * (2 if l.use_bias else 1)
+    return out
+
+
+def _prior_kw(tp):
+    """The `priors` keyword of an ops call, given only when the launch has tensor priors: a model without them makes the calls it
+    always made (the recorded launch schedules list every argument)."""
+    return {} if tp is None else {"priors": tp}
+
+
 def _sample_all(layers, draws, seed, call0, timers=None, eps=None, tm=()):
     """One fused launch (per <=16 tensors) for every BBB layer: -> ({layer: (w, b)}, kl).  tm: layers whose conv weights come out
     TAP-MAJOR, [draws, Cout, kh * kw, Cin] (ops.sample_weights_tm: the operand layout of ops.conv2d_c8x3_forward; inference)."""
@@ -215,7 +232,8 @@ def _sample_all(layers, draws, seed, call0, timers=None, eps=None, tm=()):
         ids += i
         owners += [l] * len(m)
         tmf += [l in tm and t.dim() == 4 and t.shape[2] * t.shape[3] > 1 for t in m]
-    pri = {(l.prior_mu, l.prior_sigma) for l in layers}
+    pri = {(l.prior_mu, l.prior_sigma) for l in layers}        # only the scalar fallbacks must agree within a launch:
+    tp = _prior_lists(layers)                                   # tensor priors ride along per segment and never split one
     out, kl_total = {}, None
     ws_all = []
     if len(pri) == 1:
@@ -223,13 +241,14 @@ def _sample_all(layers, draws, seed, call0, timers=None, eps=None, tm=()):
         for s in range(0, len(mus), _lib.MAX_SEGMENTS):
             sl = slice(s, s + _lib.MAX_SEGMENTS)
             n_el = sum(m.numel() for m in mus[sl])
+            tps = None if tp is None else tp[sl]
             if any(tmf[sl]):
                 kl, ws = _run(timers, "reparam_kl", n_el,
-                              lambda: ops.sample_weights_tm(mus[sl], rhos[sl], pm, ps, ids[sl], seed, call0, draws, tmf[sl]))
+                              lambda: ops.sample_weights_tm(mus[sl], rhos[sl], pm, ps, ids[sl], seed, call0, draws, tmf[sl], **_prior_kw(tps)))
             else:
                 kl, ws = _run(timers, "reparam_kl", n_el,
                               lambda: ops.sample_weights(mus[sl], rhos[sl], pm, ps, ids[sl], seed, call0, draws,
-                                                         eps=None if eps is None else eps[sl]))
+                                                         eps=None if eps is None else eps[sl], **_prior_kw(tps)))
             kl_total = kl if kl_total is None else kl_total + kl
             ws_all += ws
     else:  # layers with different priors: one launch per layer
@@ -237,10 +256,11 @@ def _sample_all(layers, draws, seed, call0, timers=None, eps=None, tm=()):
         for l in layers:
             m, r, i = l._param_lists()
             if any(tmf[k:k + len(m)]):
-                kl, ws = ops.sample_weights_tm(m, r, l.prior_mu, l.prior_sigma, i, seed, call0, draws, tmf[k:k + len(m)])
+                kl, ws = ops.sample_weights_tm(m, r, l.prior_mu, l.prior_sigma, i, seed, call0, draws, tmf[k:k + len(m)],
+                                               **_prior_kw(l._prior_lists()))
             else:
                 kl, ws = ops.sample_weights(m, r, l.prior_mu, l.prior_sigma, i, seed, call0, draws,
-                                            eps=None if eps is None else eps[k:k + len(m)])
+                                            eps=None if eps is None else eps[k:k + len(m)], **_prior_kw(l._prior_lists()))
             k += len(m)
             kl_total = kl if kl_total is None else kl_total + kl
             ws_all += ws
@@ -265,11 +285,13 @@ def _sample_all_bf16(layers, draws, seed, call0, timers=None):
     if len(pri) != 1:
         raise _lib.BBBHipError("bf16 path: all layers must share one prior")
     pm, ps = next(iter(pri))
+    tp = _prior_lists(layers)
     kl_total, ws_all = None, []
     for s in range(0, len(mus), _lib.MAX_SEGMENTS):
         sl = slice(s, s + _lib.MAX_SEGMENTS)
         kl, ws = _run(timers, "reparam_kl", sum(m.numel() for m in mus[sl]),
-                      lambda: ops.sample_weights_bf16(mus[sl], rhos[sl], pm, ps, ids[sl], seed, call0, draws))
+                      lambda: ops.sample_weights_bf16(mus[sl], rhos[sl], pm, ps, ids[sl], seed, call0, draws,
+                                                      **_prior_kw(None if tp is None else tp[sl])))
         kl_total = kl if kl_total is None else kl_total + kl
         ws_all += ws
     out, k = {}, 0
@@ -291,13 +313,13 @@ def _variances_all(layers, timers=None):
         out, kl_total = {}, None
         for l in layers:
             m, r, _ = l._param_lists()
-            kl, s2 = ops.kl_only(m, r, l.prior_mu, l.prior_sigma, want_sigma=True, sigma_squared=True)
+            kl, s2 = ops.kl_only(m, r, l.prior_mu, l.prior_sigma, want_sigma=True, sigma_squared=True, **_prior_kw(l._prior_lists()))
             out[l] = (s2[0], s2[1] if l.use_bias else None)
             kl_total = kl if kl_total is None else kl_total + kl
         return out, kl_total
     pm, ps = next(iter(pri))
     kl, s2 = _run(timers, "reparam_kl", sum(m.numel() for m in mus),
-                  lambda: ops.kl_only(mus, rhos, pm, ps, want_sigma=True, sigma_squared=True))
+                  lambda: ops.kl_only(mus, rhos, pm, ps, want_sigma=True, sigma_squared=True, **_prior_kw(_prior_lists(layers))))
     out, k = {}, 0
     for l in layers:
         out[l] = (s2[k], s2[k + 1] if l.use_bias else None)

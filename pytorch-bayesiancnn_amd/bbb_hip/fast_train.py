@@ -199,6 +199,17 @@ def _check_versions(versions):
 # what the four nodes share: the parameter lists, the forward walk, the context they carry to the backward, the backward schedule,
 # the backward walk, how the outputs are packed
 # ---------------------------------------------------------------------------------------------------------------------------
+def _prior_lists(layers):
+    """The tensor priors of the nodes' one parameter pass (ensemble._prior_lists: None when no layer has any)."""
+    from . import ensemble
+    return ensemble._prior_lists(layers)
+
+
+def _prior_kw(tp):
+    from . import ensemble
+    return ensemble._prior_kw(tp)
+
+
 def _param_lists(layers, leaf):
     """(mus, rhos, stream ids) of the layers in forward order -- per layer (W, bias) -- each parameter passed through `leaf`
     (a node's forward: detach; mc_logits_autograd: the alias that roots the graph)."""
@@ -370,10 +381,11 @@ def _pack(dx, grads):
 def _pack_bbb(ctx, dx, gws, g_kl):
     """_pack for the two BBB nodes: the gradients of the sampled weights gws (per layer W, bias) + d loss / d KL through the parameter
     pass's backward -> per layer W_mu, W_rho, bias_mu, bias_rho; frozen parameters: no pass, no gradients."""
-    mus, rhos, ids, pm, ps, _ = ctx.meta
+    mus, rhos, ids, pm, ps, _, tp = ctx.meta
     if not any(ctx.needs_input_grad[2:]):
         return _pack(dx, [None] * (2 * len(mus)))
-    gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, ctx.cfg["seed"], ctx.cfg["call0"], ctx.cfg["draws"])
+    gmu, grho = ops.reparam_kl_backward(mus, rhos, gws, g_kl, pm, ps, ids, ctx.cfg["seed"], ctx.cfg["call0"], ctx.cfg["draws"],
+                                        **_prior_kw(tp))
     grads = []
     for a, b in zip(gmu, grho):
         grads += [a, b]
@@ -398,8 +410,9 @@ class _MCForward(torch.autograd.Function):
         E, seed, call0 = cfg["draws"], cfg["seed"], cfg["call0"]
         layers = [b.layer for b in plan.blocks]
         mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
-        pm, ps = layers[0].prior_mu, layers[0].prior_sigma
-        ws, _, kl = ops.reparam_kl_forward(mus, rhos, pm, ps, ids, seed, call0, draws=E)
+        pm, ps = layers[0].prior_mu, layers[0].prior_sigma         # (the scalar fallbacks agree: _parse) + per-weight tensor priors
+        tp = _prior_lists(layers)
+        ws, _, kl = ops.reparam_kl_forward(mus, rhos, pm, ps, ids, seed, call0, draws=E, **_prior_kw(tp))
 
         def run_layer(blk, x_in):
             w, b = ws[2 * blk.li], ws[2 * blk.li + 1]
@@ -409,7 +422,7 @@ class _MCForward(torch.autograd.Function):
         h = ops.to_batch_innermost(x.detach()).unsqueeze(0)               # [1, C, H, W, B]
         tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn, ops.avgpool_chwn)
         _carry(ctx, cfg, params)
-        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
+        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape), tp)
         ctx.x_nchw = x.detach()
         return h.reshape(E, -1, x.shape[0]), kl
 
@@ -500,7 +513,8 @@ class _MCForwardBF16(torch.autograd.Function):
         layers = [b.layer for b in plan.blocks]
         mus, rhos, ids = _param_lists(layers, torch.Tensor.detach)
         pm, ps = layers[0].prior_mu, layers[0].prior_sigma
-        kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E)
+        tp = _prior_lists(layers)
+        kl, ws = ops.sample_weights_bf16(mus, rhos, pm, ps, ids, seed, call0, E, **_prior_kw(tp))
 
         def run_layer(blk, x_in):                          # (the logits layer, fp32 output: the plan ends in it, bare)
             w, b = ws[2 * blk.li], ws[2 * blk.li + 1]
@@ -511,7 +525,7 @@ class _MCForwardBF16(torch.autograd.Function):
         h = ops.to_batch_innermost_bf16(x.detach()).unsqueeze(0)          # [1, C, H, W, B] bf16
         tape, h = _walk(plan, h, run_layer, ops.maxpool_chwn_bf16, ops.avgpool_chwn_bf16)
         _carry(ctx, cfg, params)
-        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape))
+        ctx.tape, ctx.meta = tape, (mus, rhos, ids, pm, ps, tuple(x.shape), tp)
         # the first layer's fp32 weight gradient reads the input's bf16 values (what the forward contracted); frozen parameters
         # (a backward to x alone, LaunchConfig.bf16_input_grad): there is none
         ctx.x_nchw = (x.detach().to(torch.bfloat16).to(torch.float32)
@@ -908,9 +922,10 @@ def mc_logits_autograd(net, x, draws, seed, call0, alias=None, precision="fp32")
     mus, rhos, _ = _param_lists(layers, A)
     if node is _MCForwardLRT:                # its leaves are (mu, sigma^2) from the KL pass, which carries the gradients to (mu, rho)
         kl, rhos, mus = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True,
-                                    mu_through=True)
+                                    mu_through=True, **_prior_kw(ensemble._prior_lists(layers)))
     elif node is _MCForwardLRTBF16:          # frozen parameters: the inference path's KL pass (fp32), sigma^2 beside it
-        kl, rhos = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True)
+        kl, rhos = ops.kl_only(mus, rhos, layers[0].prior_mu, layers[0].prior_sigma, want_sigma=True, sigma_squared=True,
+                               **_prior_kw(ensemble._prior_lists(layers)))
     params = []
     for li in range(len(layers)):            # per layer: W_mu, W_rho (LRT: W_var), bias_mu, bias_rho (LRT: bias_var)
         params += [mus[2 * li], rhos[2 * li], mus[2 * li + 1], rhos[2 * li + 1]]

@@ -20,7 +20,7 @@ import weakref
 import torch
 
 from . import _lib, rng
-from ._lib import Segment, check, ptr, require_device, cur_stream, on_device
+from ._lib import PriorSegment, Segment, check, ptr, require_device, cur_stream, on_device
 from .pool_desc import (avgpool_bf16_plan, avgpool_of, avgpool_plan, is_avgpool, is_maxpool, is_pool, pool_of,  # noqa: F401
                         pool_plan, pool_desc as _pool_desc)                                    # (ops.pool_of, ops.avgpool_of, ...)
 from .conv_desc import ACT_CODE, _pair, bf16_flags, c8x3_flags, conv_desc, out_map, pool_code, pooled_map, slab_rule  # noqa: F401  (ops.ACT_CODE)
@@ -119,9 +119,47 @@ def _segments(mus, rhos, ws, sigmas, epss, stream_ids, draws):
     return arr
 
 
+def _prior_segments(priors, mus):
+    """Tensor priors of a launch: `priors` is None or one (mu0 | None, sigma0 | None) per tensor of `mus`, each tensor fp32,
+    contiguous, on the parameter's device, with the parameter's numel and no gradient (nothing flows to a prior).  Returns a ctypes
+    array of PriorSegment -- or None when no tensor is set: the launch is then the scalar entry's, as it always was."""
+    if priors is None:
+        return None
+    priors = list(priors)
+    if len(priors) != len(mus):
+        raise _lib.BBBHipError(f"priors: one (mu0, sigma0) pair per tensor, got {len(priors)} for {len(mus)} tensors")
+    if all(p is None or (p[0] is None and p[1] is None) for p in priors):
+        return None
+    arr = (PriorSegment * len(mus))()
+    for seg, p, m in zip(arr, priors, mus):
+        if p is None:
+            continue
+        for name, t in zip(("mu0", "sigma0"), p):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != m.device or t.numel() != m.numel() or not t.is_contiguous():
+                raise _lib.BBBHipError(f"prior {name}: a contiguous fp32 tensor on {m.device} with {m.numel()} elements (the parameter's), "
+                                       f"got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}"
+                                       + (f" {t.dtype} on {t.device}" if torch.is_tensor(t) else ""))
+            if t.requires_grad:
+                raise _lib.BBBHipError(f"prior {name} requires a gradient: nothing flows to a prior, pass a detached tensor")
+            setattr(seg, name, t.data_ptr())
+    return arr
+
+
+def _reparam_fwd(segs, pri, nseg, *args):
+    """bbb_reparam_kl_fwd, or bbb_reparam_kl_tp_fwd when the launch has tensor priors."""
+    L = _lib.lib()
+    if pri is None:
+        check(L.bbb_reparam_kl_fwd(segs, nseg, *args), "bbb_reparam_kl_fwd")
+    else:
+        check(L.bbb_reparam_kl_tp_fwd(segs, pri, nseg, *args), "bbb_reparam_kl_tp_fwd")
+
+
 def reparam_kl_forward(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws=1, sample=True,
-                       want_sigma=False, sigma_squared=False, want_kl=True, eps=None, textbook_kl=False):
-    """Raw (no autograd) fused pass.  mus/rhos: lists of contiguous fp32 device tensors.
+                       want_sigma=False, sigma_squared=False, want_kl=True, eps=None, textbook_kl=False, priors=None):
+    """Raw (no autograd) fused pass.  mus/rhos: lists of contiguous fp32 device tensors.  priors: per-weight Gaussian priors, one
+    (mu0 | None, sigma0 | None) per tensor (see _prior_segments); None entries fall back to the scalars.
     Returns (ws | None, sigmas | None, kl | None); ws[i] has shape [draws, *mus[i].shape]."""
     if len(mus) == 0 or len(mus) > _lib.MAX_SEGMENTS:
         raise _lib.BBBHipError(f"1..{_lib.MAX_SEGMENTS} tensors per launch, got {len(mus)}")
@@ -138,21 +176,21 @@ def reparam_kl_forward(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0
             if e.numel() != draws * m.numel():
                 raise _lib.BBBHipError("external eps must have shape [draws, *param.shape]")
     segs = _segments(mus, rhos, ws, sigmas, eps, stream_ids, draws)
+    pri = _prior_segments(priors, mus)
     kl = torch.empty((), dtype=torch.float32, device=dev) if want_kl else None
     L = _lib.lib()
     nparts = L.bbb_reparam_partials(segs, len(mus))
     parts = _partials(dev, nparts) if want_kl else None
     flags = (_lib.SIGMA_SQUARED if sigma_squared else 0) | (_lib.KL_TEXTBOOK if textbook_kl else 0)
     with on_device(dev):
-        rc = L.bbb_reparam_kl_fwd(segs, len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
-                                  flags, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
-    check(rc, "bbb_reparam_kl_fwd")
+        _reparam_fwd(segs, pri, len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
+                     flags, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
     return ws, sigmas, kl
 
 
 def reparam_kl_backward(mus, rhos, gws, gkl, prior_mu, prior_sigma, stream_ids, seed, call0, draws, eps=None,
-                        textbook_kl=False, gsigmas=None, sigma_squared=False, gws_mean_only=False):
-    """grad_mu[i], grad_rho[i] for every tensor (see bbb_reparam_kl_bwd).  gsigmas: gradients w.r.t. the forward's sigma
+                        textbook_kl=False, gsigmas=None, sigma_squared=False, gws_mean_only=False, priors=None):
+    """grad_mu[i], grad_rho[i] for every tensor (see bbb_reparam_kl_bwd; priors as in reparam_kl_forward: bbb_reparam_kl_tp_bwd).  gsigmas: gradients w.r.t. the forward's sigma
     (sigma_squared: sigma^2) outputs, entries may be None.  gws_mean_only: gws are gradients w.r.t. the means themselves
     (BBB_GW_MEAN_ONLY: added into grad_mu, nothing into grad_rho)."""
     require_device(*mus, *rhos)
@@ -166,6 +204,7 @@ def reparam_kl_backward(mus, rhos, gws, gkl, prior_mu, prior_sigma, stream_ids, 
         gsigmas = [None if g is None else g.to(dtype=torch.float32).contiguous() for g in gsigmas]
         require_device(*gsigmas)
     segs = _segments(mus, rhos, gws, gsigmas, eps, stream_ids, draws)
+    pri = _prior_segments(priors, mus)
     gmu = [torch.empty_like(m) for m in mus]
     grho = [torch.empty_like(m) for m in mus]
     pm = (ctypes.c_void_p * len(mus))(*[g.data_ptr() for g in gmu])
@@ -174,21 +213,26 @@ def reparam_kl_backward(mus, rhos, gws, gkl, prior_mu, prior_sigma, stream_ids, 
         gkl = gkl.to(device=dev, dtype=torch.float32).contiguous()
     flags = (_lib.KL_TEXTBOOK if textbook_kl else 0) | (_lib.SIGMA_SQUARED if (sigma_squared and gsigmas is not None) else 0)
     flags |= _lib.GW_MEAN_ONLY if gws_mean_only else 0
+    tail = (draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF, flags, ptr(gkl), pm, pr, rng.call_dev_ptr(dev),
+            cur_stream(dev))
     with on_device(dev):
-        rc = _lib.lib().bbb_reparam_kl_bwd(segs, len(mus), draws, float(prior_mu), float(prior_sigma), seed,
-                                           call0 & 0xFFFFFFFF, flags, ptr(gkl), pm, pr, rng.call_dev_ptr(dev), cur_stream(dev))
-    check(rc, "bbb_reparam_kl_bwd")
+        if pri is None:
+            check(_lib.lib().bbb_reparam_kl_bwd(segs, len(mus), *tail), "bbb_reparam_kl_bwd")
+        else:
+            check(_lib.lib().bbb_reparam_kl_tp_bwd(segs, pri, len(mus), *tail), "bbb_reparam_kl_tp_bwd")
     return gmu, grho
 
 
 REPARAM_PLAN_FIELDS = ("kernel", "gpt", "nt", "chunks", "n_small", "small_chunk0", "tm_blocks", "grid")
 
 
-def reparam_plan(segs, draws, slots=0, nseg=None):
+def reparam_plan(segs, draws, slots=0, nseg=None, priors=None):
     """What bbb_reparam_kl_fwd launches for `segs` (bbb_reparam_kl_plan: the launch entry's own plan, host only): a dict of
     REPARAM_PLAN_FIELDS with kernel "fast" | "generic" and nt a bool.  segs: a ctypes array of Segment as the launch takes it, or a
     sequence whose items are element counts or dicts of Segment fields (mu, rho and w then get a placeholder address that is never
-    read).  slots <= 0: the current device's resident blocks, as the launcher asks."""
+    read).  slots <= 0: the current device's resident blocks, as the launcher asks.  priors: a ctypes array of PriorSegment, or a
+    sequence of (mu0, sigma0) ADDRESSES (0 / None = the scalar), one per segment: the plan of bbb_reparam_kl_tp_fwd
+    (bbb_reparam_kl_tp_plan) -- the same launch shape, after the checks of the prior pointers."""
     if isinstance(segs, ctypes.Array):
         arr, nseg = segs, (len(segs) if nseg is None else nseg)
     else:
@@ -202,7 +246,18 @@ def reparam_plan(segs, draws, slots=0, nseg=None):
             if "draw_stride" not in fields:
                 s.draw_stride = s.n
     out = [ctypes.c_int32(0) for _ in REPARAM_PLAN_FIELDS]
-    check(_lib.lib().bbb_reparam_kl_plan(arr, nseg, draws, slots, *[ctypes.byref(o) for o in out]), "bbb_reparam_kl_plan")
+    if priors is None:
+        check(_lib.lib().bbb_reparam_kl_plan(arr, nseg, draws, slots, *[ctypes.byref(o) for o in out]), "bbb_reparam_kl_plan")
+    else:
+        if not isinstance(priors, ctypes.Array):
+            pairs = list(priors)
+            if len(pairs) != nseg:
+                raise _lib.BBBHipError(f"priors: one (mu0, sigma0) pair per segment, got {len(pairs)} for {nseg} segments")
+            priors = (PriorSegment * max(len(pairs), 1))()
+            for seg, (m0, s0) in zip(priors, pairs):
+                seg.mu0, seg.sigma0 = m0 or 0, s0 or 0
+        check(_lib.lib().bbb_reparam_kl_tp_plan(arr, priors, nseg, draws, slots, *[ctypes.byref(o) for o in out]),
+              "bbb_reparam_kl_tp_plan")
     plan = {k: o.value for k, o in zip(REPARAM_PLAN_FIELDS, out)}
     plan["kernel"] = ("fast", "generic")[plan["kernel"]]
     plan["nt"] = bool(plan["nt"])
@@ -1124,7 +1179,7 @@ def bf16_tap_major(shape):
     return len(shape) == 4 and shape[1] % 8 == 0 and shape[2] * shape[3] > 1
 
 
-def sample_weights_bf16(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws, eps=None):
+def sample_weights_bf16(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws, eps=None, priors=None):
     """The fused reparam + KL pass with the sampled WEIGHT matrices written as bf16 in the bf16 GEMM's operand layout
     ([draws, rows, pitch], pitch = row length rounded up to 8, pad zero; tap-major column order where bf16_tap_major says
     so) and 1-d tensors (biases) kept fp32.  Inference only.  Returns (kl, [tensors])."""
@@ -1158,13 +1213,12 @@ def sample_weights_bf16(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call
     L = _lib.lib()
     parts = _partials(dev, L.bbb_reparam_partials(segs, len(mus)))
     with on_device(dev):
-        rc = L.bbb_reparam_kl_fwd(segs, len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
-                                  0, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
-    check(rc, "bbb_reparam_kl_fwd")
+        _reparam_fwd(segs, _prior_segments(priors, mus), len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
+                     0, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
     return kl, outs
 
 
-def sample_weights_tm(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws, tap_major):
+def sample_weights_tm(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws, tap_major, priors=None):
     """The fused reparam + KL pass with the conv weights flagged in `tap_major` (one bool per tensor) written TAP-MAJOR, fp32
     [draws, Cout, kh * kw, Cin] (bbb_segment_t::w_tm_cin: the weight operand of conv2d_c8x3_forward), every other tensor dense
     [draws, *shape].  Same noise elements, same KL bits as the dense launch (w_tap_major(dense) == this, bit for bit).
@@ -1192,9 +1246,8 @@ def sample_weights_tm(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0,
     L = _lib.lib()
     parts = _partials(dev, L.bbb_reparam_partials(segs, len(mus)))
     with on_device(dev):
-        rc = L.bbb_reparam_kl_fwd(segs, len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
-                                  0, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
-    check(rc, "bbb_reparam_kl_fwd")
+        _reparam_fwd(segs, _prior_segments(priors, mus), len(mus), draws, float(prior_mu), float(prior_sigma), seed, call0 & 0xFFFFFFFF,
+                     0, ptr(parts), ptr(kl), 0, rng.call_dev_ptr(dev), cur_stream(dev))
     return kl, outs
 
 
@@ -1943,7 +1996,7 @@ class _SampleWeights(torch.autograd.Function):
         mus, rhos = list(params[0::2]), list(params[1::2])
         ws, _, kl = reparam_kl_forward(mus, rhos, cfg["prior_mu"], cfg["prior_sigma"], cfg["stream_ids"], cfg["seed"],
                                        cfg["call0"], cfg["draws"], sample=True, eps=cfg.get("eps"),
-                                       textbook_kl=cfg.get("textbook_kl", False))
+                                       textbook_kl=cfg.get("textbook_kl", False), priors=cfg.get("priors"))
         ctx.cfg = cfg
         ctx.save_for_backward(*params)
         return (kl, *ws)
@@ -1955,7 +2008,7 @@ class _SampleWeights(torch.autograd.Function):
         mus, rhos = list(params[0::2]), list(params[1::2])
         gmu, grho = reparam_kl_backward(mus, rhos, list(gws), gkl, cfg["prior_mu"], cfg["prior_sigma"], cfg["stream_ids"],
                                         cfg["seed"], cfg["call0"], cfg["draws"], eps=cfg.get("eps"),
-                                        textbook_kl=cfg.get("textbook_kl", False))
+                                        textbook_kl=cfg.get("textbook_kl", False), priors=cfg.get("priors"))
         out = [None]
         for a, b in zip(gmu, grho):
             out += [a, b]
@@ -1971,7 +2024,7 @@ class _KLOnly(torch.autograd.Function):
         _, sig, kl = reparam_kl_forward(mus, rhos, cfg["prior_mu"], cfg["prior_sigma"], cfg["stream_ids"], 0, 0, 1,
                                         sample=False, want_sigma=cfg.get("want_sigma", False),
                                         sigma_squared=cfg.get("sigma_squared", False),
-                                        textbook_kl=cfg.get("textbook_kl", False))
+                                        textbook_kl=cfg.get("textbook_kl", False), priors=cfg.get("priors"))
         ctx.cfg = cfg
         ctx.save_for_backward(*params)
         ctx.n_sig = 0 if sig is None else len(sig)
@@ -1998,7 +2051,7 @@ class _KLOnly(torch.autograd.Function):
             gws = [gthru[i] if i < len(gthru) else None for i in range(len(mus))]
         gmu, grho = reparam_kl_backward(mus, rhos, gws, gkl, cfg["prior_mu"], cfg["prior_sigma"],
                                         cfg["stream_ids"], 0, 0, 1, textbook_kl=cfg.get("textbook_kl", False), gsigmas=gs,
-                                        sigma_squared=cfg.get("sigma_squared", False), gws_mean_only=True)
+                                        sigma_squared=cfg.get("sigma_squared", False), gws_mean_only=True, priors=cfg.get("priors"))
         out = [None]
         for a, b in zip(gmu, grho):
             out += [a, b]
@@ -2195,14 +2248,14 @@ def _no_grad_needed(tensors):
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
 
-def sample_weights(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws=1, eps=None, textbook_kl=False):
+def sample_weights(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, draws=1, eps=None, textbook_kl=False, priors=None):
     if _no_grad_needed(list(mus) + list(rhos)):
         # inference: the launch itself -- autograd.Function.apply on 24 tensors costs ~80 us of host time per call
         ws, _, kl = reparam_kl_forward([m.detach() for m in mus], [r.detach() for r in rhos], prior_mu, prior_sigma, list(stream_ids), seed,
-                                       call0, draws, sample=True, eps=eps, textbook_kl=textbook_kl)
+                                       call0, draws, sample=True, eps=eps, textbook_kl=textbook_kl, priors=priors)
         return kl, ws
     cfg = dict(prior_mu=prior_mu, prior_sigma=prior_sigma, stream_ids=list(stream_ids), seed=seed, call0=call0,
-               draws=draws, eps=eps, textbook_kl=textbook_kl)
+               draws=draws, eps=eps, textbook_kl=textbook_kl, priors=priors)
     flat = []
     for m, r in zip(mus, rhos):
         flat += [m, r]
@@ -2210,16 +2263,17 @@ def sample_weights(mus, rhos, prior_mu, prior_sigma, stream_ids, seed, call0, dr
     return out[0], list(out[1:])
 
 
-def kl_only(mus, rhos, prior_mu, prior_sigma, want_sigma=False, sigma_squared=False, textbook_kl=False, mu_through=False):
+def kl_only(mus, rhos, prior_mu, prior_sigma, want_sigma=False, sigma_squared=False, textbook_kl=False, mu_through=False, priors=None):
     """-> (kl, [sigma ...]) -- with mu_through (and want_sigma) -> (kl, [sigma ...], [mu ...]): the means as outputs of the same
     autograd node, so that gradients w.r.t. them are added to d KL / d mu inside its one backward launch."""
     if _no_grad_needed(list(mus) + list(rhos)):
         _, sig, kl = reparam_kl_forward([m.detach() for m in mus], [r.detach() for r in rhos], prior_mu, prior_sigma, [0] * len(mus), 0, 0, 1,
-                                        sample=False, want_sigma=want_sigma, sigma_squared=sigma_squared, textbook_kl=textbook_kl)
+                                        sample=False, want_sigma=want_sigma, sigma_squared=sigma_squared, textbook_kl=textbook_kl,
+                                        priors=priors)
         sig = list(sig) if sig is not None else []
         return (kl, sig, list(mus)) if mu_through else (kl, sig)
     cfg = dict(prior_mu=prior_mu, prior_sigma=prior_sigma, stream_ids=[0] * len(mus), want_sigma=want_sigma,
-               sigma_squared=sigma_squared, textbook_kl=textbook_kl, mu_through=mu_through)
+               sigma_squared=sigma_squared, textbook_kl=textbook_kl, mu_through=mu_through, priors=priors)
     flat = []
     for m, r in zip(mus, rhos):
         flat += [m, r]

@@ -57,6 +57,19 @@ inline int segments(const bbb_segment_t* segs, int nseg, int draws, bool bwd, in
     return (int)chunks;
 }
 
+// Tensor priors (bbb_reparam_kl_tp_*): pri[s].mu0 / .sigma0 are [segs[s].n] fp32 or NULL (= the launch-wide scalar).  Returns how many
+// pointers are set -- 0, also for pri == NULL, means the scalar kernels run -- or an error.  The prior never enters the plan.
+inline int priors(const bbb_segment_t* segs, const bbb_prior_segment_t* pri, int nseg) {
+    if (segs == nullptr || nseg <= 0 || nseg > BBB_MAX_SEGMENTS) return BBB_EINVAL;
+    if (pri == nullptr) return 0;
+    int set = 0;
+    for (int s = 0; s < nseg; ++s) {
+        if ((((uintptr_t)pri[s].mu0 | (uintptr_t)pri[s].sigma0) & 3u) != 0) return BBB_EALIGN;
+        set += (pri[s].mu0 != nullptr) + (pri[s].sigma0 != nullptr);
+    }
+    return set;
+}
+
 // Everything of the forward's plan that does not depend on the device: kernel, gpt, chunks, the tap-major blocks.
 inline int forward_shape(const bbb_segment_t* segs, int nseg, int draws, Plan* p) {
     *p = Plan{};

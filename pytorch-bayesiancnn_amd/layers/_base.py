@@ -13,6 +13,10 @@ _DEFAULT_PRIORS = {
 }
 
 
+# Per-weight Gaussian priors (set_prior): non-persistent buffers, None = the scalar prior_mu / prior_sigma for that quantity.
+_PRIOR_BUFFERS = ("W_prior_mu", "W_prior_sigma", "bias_prior_mu", "bias_prior_sigma")
+
+
 def default_device():
     # the reference pins cuda:0 (layers/BBB/BBBConv.py:27); parameters may later be moved with .to()
     return torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -43,6 +47,8 @@ class BayesianLayer(ModuleWrapper):
         else:
             self.register_parameter("bias_mu", None)
             self.register_parameter("bias_rho", None)
+        for name in _PRIOR_BUFFERS:      # follow .to() / .cuda() / deepcopy, stay out of state_dict(): checkpoints remain the reference's
+            self.register_buffer(name, None, persistent=False)
         self._stream_base = rng.new_stream_base()
         self._kl = None
         self._presampled = None      # (w, bias) handed over by a fused whole-model launch
@@ -96,12 +102,102 @@ class BayesianLayer(ModuleWrapper):
             ids.append(self._stream_base + 1)
         return mus, rhos, ids
 
+    def _prior_lists(self):
+        """Sibling of _param_lists(): [(W_prior_mu, W_prior_sigma), (bias_prior_mu, bias_prior_sigma)] -- entries None where the
+        scalar holds -- or None when this layer has no prior tensor at all."""
+        b = self._buffers
+        wm, ws, bm, bs = (b.get(n) for n in _PRIOR_BUFFERS)
+        if wm is None and ws is None and bm is None and bs is None:
+            return None
+        return [(wm, ws), (bm, bs)] if self.use_bias else [(wm, ws)]
+
+    def _check_prior_tensor(self, who, t, like, positive):
+        if like is None:
+            raise ValueError(f"{who}: the layer has no bias")
+        if tuple(t.shape) != tuple(like.shape):
+            raise ValueError(f"{who}: shape {tuple(t.shape)}, the parameter has {tuple(like.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: dtype {t.dtype}, expected torch.float32")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{who}: non-finite elements")
+        if positive and not bool((t > 0).all()):
+            raise ValueError(f"{who}: every element must be > 0")
+
+    def _set_prior_tensor(self, name, t, like):
+        """Copy into the existing buffer when the shape matches (stable pointer: a captured step sees the new values at its next
+        replay); otherwise a new buffer, which is a change of kind.  -> True when the kind changed."""
+        cur = self._buffers.get(name)
+        src = t.detach()
+        if cur is not None and cur.shape == src.shape:
+            with torch.no_grad():
+                cur.copy_(src)
+            return False
+        setattr(self, name, src.to(device=like.device, dtype=torch.float32, copy=True).contiguous())
+        return True
+
+    def _clear_prior_tensor(self, name):
+        if self._buffers.get(name) is None:
+            return False
+        setattr(self, name, None)
+        return True
+
+    def set_prior(self, mu=None, sigma=None, bias_mu=None, bias_sigma=None, name=None):
+        """Set the Gaussian prior of this layer.  Every argument: None (leave as it is), a Python number, or a tensor of the
+        parameter's shape (fp32, finite, sigma > 0: validated here, once, on the host).
+        mu / sigma: a number sets prior_mu / prior_sigma (the reference's attributes) and drops that quantity's tensors, weight and
+        bias; a tensor becomes the weight's per-element prior.  bias_mu / bias_sigma: a tensor for the bias; a number must equal
+        prior_mu / prior_sigma (the reference has one scalar pair per layer) and drops that bias tensor.
+        A tensor given where a buffer of its shape exists is copied into it; any change of kind (number <-> tensor, new shape)
+        invalidates captured steps and cached structures.  Every argument is validated before anything is applied: a refused call
+        leaves the layer as it was.  name: what the messages call the layer (bbb_hip.priors passes its name in the model; default:
+        the class name)."""
+        who = name or type(self).__name__
+        scalars = {"prior_mu": self.prior_mu, "prior_sigma": self.prior_sigma}           # as they will be after this call
+        todo = []                                                                        # (buffer, tensor | None = clear, like)
+        for what, val, attr, wname, bname, positive in (("mu", mu, "prior_mu", "W_prior_mu", "bias_prior_mu", False),
+                                                        ("sigma", sigma, "prior_sigma", "W_prior_sigma", "bias_prior_sigma", True)):
+            if val is None:
+                continue
+            if torch.is_tensor(val):
+                self._check_prior_tensor(f"{who}: prior {what}", val, self.W_mu, positive)
+                todo.append((wname, val, self.W_mu))
+            else:
+                val = float(val) if not isinstance(val, int) else val
+                if not (val == val and abs(val) != float("inf")) or (positive and not val > 0):
+                    raise ValueError(f"{who}: prior {what} = {val!r}" + (": must be > 0" if positive else ": not finite"))
+                scalars[attr] = val
+                todo += [(wname, None, None), (bname, None, None)]
+        for what, val, attr, bname, positive in (("bias_mu", bias_mu, "prior_mu", "bias_prior_mu", False),
+                                                 ("bias_sigma", bias_sigma, "prior_sigma", "bias_prior_sigma", True)):
+            if val is None:
+                continue
+            if torch.is_tensor(val):
+                self._check_prior_tensor(f"{who}: prior {what}", val, self.bias_mu if self.use_bias else None, positive)
+                todo.append((bname, val, self.bias_mu))
+            else:
+                if float(val) != float(scalars[attr]):
+                    raise ValueError(f"{who}: prior {what} = {val!r} differs from the layer's {attr} = {scalars[attr]!r}: "
+                                     "a layer has one scalar pair; pass a tensor for a bias prior of its own")
+                todo.append((bname, None, None))
+        changed = False
+        for attr, val in scalars.items():
+            if getattr(self, attr) != val:
+                setattr(self, attr, val)
+                changed = True
+        for bname, t, like in todo:
+            changed |= self._clear_prior_tensor(bname) if t is None else self._set_prior_tensor(bname, t, like)
+        self.__dict__["_kl"] = None
+        if changed:
+            from bbb_hip import ensemble
+            ensemble._bump_epoch()
+        return self
+
     def kl_loss(self):
         """KL of this layer in the reference's (swapped-argument) form; computed by the fused kernel during
         forward and cached, or on demand if no forward ran since the parameters changed."""
         if self._kl is None:
             mus, rhos, _ = self._param_lists()
-            kl, _ = ops.kl_only(mus, rhos, self.prior_mu, self.prior_sigma)
+            kl, _ = ops.kl_only(mus, rhos, self.prior_mu, self.prior_sigma, priors=self._prior_lists())
             return kl
         return self._kl
 

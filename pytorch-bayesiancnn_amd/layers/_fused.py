@@ -114,8 +114,8 @@ class _Spec:
     result (the generator offset still advances by one call per net(x)).  Bit-identical to the loop by the noise contract
     (draw j of a batched launch == net(x) number j).  K follows the length of the previous streak of identical inputs
     (a validation loop settles on K = num_ens at the FIRST call of each batch), or doubles 2, 4, 8 while no history exists.
-    The cache is dropped when the input object, its version counter, any parameter's version counter, the generator
-    position, the autograd mode or the model's structure (a replaced layer / Parameter, moved storage) changes."""
+    The cache is dropped when the input object, its version counter, any parameter's version counter, a layer's prior tensors (their version counters and addresses),
+    the generator position, the autograd mode or the model's structure (a replaced layer / Parameter, moved storage) changes."""
     __slots__ = ("xref", "xver", "pver", "grad", "seed", "next_call", "logits", "kl", "idx", "streak", "last_streak", "batches")
 
     def __init__(self):
@@ -298,7 +298,7 @@ def fast_forward(wrapper, x):
     this is the outermost wrapper of the forward.  With autograd enabled the same kernels run behind ONE autograd node
     (bbb_hip.fast_train).  Consecutive calls on the same input are batched speculatively (_Spec).
     Returns (output, kl) or None (-> the reference-layout path below, which also serves input gradients and hooks)."""
-    from ._base import BayesianLayer
+    from ._base import BayesianLayer, _PRIOR_BUFFERS
     if isinstance(wrapper, BayesianLayer) or rng._scope or not torch.is_tensor(x) or not x.is_cuda or x.dim() != 4:
         return None
     if x.requires_grad and torch.is_grad_enabled():
@@ -334,7 +334,10 @@ def fast_forward(wrapper, x):
     st = ensemble._structure(wrapper)
     # parameter versions AND storage addresses (module.to() / .data assignments replace storage without a version bump), plus the
     # identity of the cached structure (a replaced layer or Parameter object rebuilds it)
-    pver = (id(st),) + tuple((p._version, p.data_ptr()) for p in st["params"])
+    # -- and the same of the layers' prior tensors (BayesianLayer.set_prior, or a write into a buffer): an in-place update changes the KL
+    # of draws speculated before it, while a cached GraphedLogits, keyed by the addresses alone, reads the tensors and is kept
+    pver = (id(st),) + tuple((p._version, p.data_ptr()) for p in st["params"]) + tuple(
+        (0, 0) if t is None else (t._version, t.data_ptr()) for l in layers for t in map(l._buffers.get, _PRIOR_BUFFERS))
     mode = (grad, prec)                               # (cached draws belong to one autograd mode and one precision)
     same_x = sp.xref is not None and sp.xref() is x and sp.xver == x._version and sp.pver == pver and sp.grad == mode
     can_spec = speculation["enabled"] and rng._graph_counter["tensor"] is None and not torch.cuda.is_current_stream_capturing()

@@ -23,10 +23,11 @@ class _BBBLayer(BayesianLayer):
             eps = None
             if self.eps_source is not None:      # test / replay entry: external noise, W first then bias
                 eps = [self.eps_source(tuple(m.shape)).to(m.device).unsqueeze(0) for m in mus]
-            kl, ws = ops.sample_weights(mus, rhos, self.prior_mu, self.prior_sigma, ids, seed, call, 1, eps=eps)
+            kl, ws = ops.sample_weights(mus, rhos, self.prior_mu, self.prior_sigma, ids, seed, call, 1, eps=eps,
+                                            priors=self._prior_lists())
             self._take_kl(kl)
             return ws[0], (ws[1] if self.use_bias else None)
-        kl, _ = ops.kl_only(mus, rhos, self.prior_mu, self.prior_sigma)
+        kl, _ = ops.kl_only(mus, rhos, self.prior_mu, self.prior_sigma, priors=self._prior_lists())
         self._take_kl(kl)
         return self.W_mu.unsqueeze(0), (self.bias_mu.unsqueeze(0) if self.use_bias else None)
 
